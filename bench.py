@@ -1,6 +1,6 @@
 """bench.py -- cached-prefill TTFT / tokens-per-second of the prompt-cache hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -21,9 +21,17 @@ the prompt (single-prompt TTFT has no cross-GPU step; "weak" scaling).  Schema e
 path that does shard -- runs before the timed region, sharded over the ranks with one all-gather, and is
 reported under "encode".
 
-Extra objects on the JSON line: "roofline" (the dominant hand-written kernel, HIP-event timed on its launch
-stream inside the timed region), "cpu_baseline" (the numpy oracle on the host cores, bounded sample),
-"parity" (same-run max |delta logit| GPU vs oracle at the true layer shape).
+A plain run sets up (model, one schema encode), warms up, times the K steps and prints the headline line
+("breakdown_ms", "staging" and "roofline_step" come from the timed steps themselves).  --full adds every other
+leg, each with runs of its own: the steady-state "encode" and the schema-library "encode_library", "roofline"
+(the dominant hand-written kernel, HIP-event timed on its launch stream) and the other per-kernel rooflines,
+the context legs (no_cache, decode, cold shapes, host tier, int8), "cpu_baseline" (the numpy oracle on the
+host cores, bounded sample), "parity" (same-run max |delta logit| GPU vs oracle at the true layer shape) and
+"configs" (BASELINE configs 2-4, compact); the --no-* options switch single legs of a --full run off.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32, integer
+ids as float64; a fixed, seeded sample of the staged K/V rows), 64 MB at most: two builds run with the same
+arguments see identical inputs and can be compared output for output.
 """
 from __future__ import annotations
 
@@ -183,6 +191,58 @@ def _pmc_traffic(kernel_key: str, signature: str):
     if not ent or ent.get("signature") != signature:
         return None, None
     return ent.get("hbm_bytes_per_launch"), ent.get("source")
+
+
+DUMP_LIMIT_BYTES = 64_000_000       # --dump-outputs: all arrays together
+
+
+def step_outputs(out, ids, pos, seed: int = 1234) -> dict:
+    """What one step of the timed path hands its caller, for ``--dump-outputs``: the ids / positions ``process()`` assembled, the
+    logits of the new rows and, from the ``past_key_values`` the forward returned, the K / V it appended for the new rows and a
+    fixed, seeded sample of the staged rows it attended to (every layer; rows are key indices).  Row counts shrink with the model
+    so that the whole dump stays under DUMP_LIMIT_BYTES; more than 64 new rows are sampled the same way."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(seed)
+
+    def pick(n, k):
+        return np.arange(n) if n <= k else np.sort(rng.choice(n, k, replace=False))
+    logits = out.logits.reshape(-1, out.logits.shape[-1])
+    lrows = pick(logits.shape[0], 64)
+    res = {"input_ids": np.asarray(ids), "position_ids": np.asarray(pos), "logits_rows": lrows,
+           "logits": logits[torch.as_tensor(lrows, device=logits.device)]}
+    kv = out.past_key_values
+    L = len(kv)
+    _, Hkv, n, D = kv[0][0].shape
+    q = len(ids)
+    S = n - q
+    row_bytes = L * 2 * Hkv * D * 4
+    budget = max(2, int((DUMP_LIMIT_BYTES * 0.9 - res["logits"].numel() * 4) // row_bytes))
+    new_rows = S + pick(q, min(16, budget // 2))
+    staged_rows = pick(S, min(16, budget - len(new_rows)))
+    for name, rows in (("kv_new", new_rows), ("kv_staged_sample", staged_rows)):
+        r = torch.as_tensor(rows, device=kv[0][0].device)
+        res[name] = torch.stack([torch.stack([kv[i][0][0][:, r], kv[i][1][0][:, r]]) for i in range(L)])   # [L, 2, Hkv, rows, D]
+        res[name + "_rows"] = rows
+    return res
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write every array as ``out_dir/<name>.npy``: floating point as float32, integers as float64 (exact)."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy() if a.is_floating_point() else a.detach().cpu().double().numpy()
+        a = np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def gemm_rooflines(lm, T: int):
@@ -434,17 +494,19 @@ def config_workload(cfg: int):
 
 
 def run_config(args, device, world, rank, barrier):
-    result = measure_config(args.config, args.steps, args.warmup, device, world, rank, barrier)
+    result = measure_config(args.config, args.steps, args.warmup, device, world, rank, barrier,
+                            dump_dir=args.dump_outputs if rank == 0 else None)
     if rank == 0:
         print(json.dumps(result))
 
 
-def measure_config(cfg, steps, warmup, device, world, rank, barrier, lm=None, repeats: int = 3, attention_leg: bool = True):
+def measure_config(cfg, steps, warmup, device, world, rank, barrier, lm=None, repeats: int = 3, attention_leg: bool = True,
+                   dump_dir=None):
     """BASELINE.json configs 2-4 with the reference's latency recipe (eval.py:172-219, eval_sys.py:29): for every entry
     add_schema -> process -> first lm() call, the cached run and the no_cache run, ``repeats`` repeats each.  The timed region
     is K cached steps (one step = CacheEngine.process + first forward of the next entry, entries cycled, schemas resident).
     ``lm``: a resident model of the config's shape to reuse (the default run's ``configs`` leg reuses the headline 7b model for
-    config 2)."""
+    config 2).  ``dump_dir``: ``--dump-outputs`` of the last timed step."""
     import torch
     import torch.distributed as dist
     from promptcache_amd import CacheEngine, Prompt
@@ -462,16 +524,18 @@ def measure_config(cfg, steps, warmup, device, world, rank, barrier, lm=None, re
     t_enc = time.perf_counter() - t0
     prompts = [Prompt(pp, [fmt]) for _, pp in entries]
     pc = eng.prompt_cache
+    last = {}
 
     def one(prompt, no_cache):
         pc.reset()
         ids, pos, cache_ms, cache = eng.process(prompt, no_cache=no_cache)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        lm(input_ids=torch.tensor([list(ids)], dtype=torch.long), position_ids=torch.tensor([pos], dtype=torch.long),
-           past_key_values=cache, use_cache=True)
+        last["out"] = lm(input_ids=torch.tensor([list(ids)], dtype=torch.long), position_ids=torch.tensor([pos], dtype=torch.long),
+                         past_key_values=cache, use_cache=True)
         e1.record()
         torch.cuda.synchronize()
+        last["ids"], last["pos"] = ids, pos
         return len(ids), (0 if cache is None else len(pc)), cache_ms, e0.elapsed_time(e1)
 
     per_entry = []
@@ -498,6 +562,8 @@ def measure_config(cfg, steps, warmup, device, world, rank, barrier, lm=None, re
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir:
+        dump_outputs(dump_dir, step_outputs(last["out"], last["ids"], last["pos"]))
     ms = elapsed / args.steps * 1e3
     L, Hkv, D = lm.get_cache_shape()
     c = lm.hf_model.config
@@ -672,89 +738,12 @@ def plan_only(args):
     print(json.dumps(out))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3, 4],
-                    help="BASELINE.json config: 1 = the headline (llama2-7b shape, persona-structured schema); 2 = game-like "
-                         "schema (7b, max_ctx 5000); 3 = SQuAD-like entries (CodeLlama-7b); 4 = LongBench-like 8k context (13b). "
-                         "2-4 follow the reference's latency recipe (eval.py:172-219): every entry, cached and no_cache")
-    ap.add_argument("--model", default="llama2-7b")
-    ap.add_argument("--max-ctx", type=int, default=4096)        # config/llm_config_llama2_7b.json of the reference
-    ap.add_argument("--cpu-layers", type=int, default=8, help="layers the cpu_baseline TIMING runs (scaled by L/k)")
-    ap.add_argument("--parity-layers", type=int, default=0, help="layers of the parity leg (0 = all)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-library", action="store_true", help="skip the schema-library encode leg (BASELINE config 5)")
-    ap.add_argument("--no-int8", action="store_true", help="skip the int8-weight context leg (builds a second model)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the compact BASELINE config 2-4 legs of the default run")
-    ap.add_argument("--no-context", action="store_true", help="skip the extra (untimed) no-cache / decode / GEMM-roofline runs")
-    ap.add_argument("--plan-only", action="store_true",
-                    help="CPU only: print the predicted 1/2/4/8-GPU schedule of the schema-library encode and exit")
-    ap.add_argument("--plan-rate", type=float, default=72000.0, help="--plan-only: 1-GPU library encode rate, scaffold tokens/s")
-    ap.add_argument("--plan-link-gbs", type=float, default=153.0, help="--plan-only: one xGMI link, GB/s per direction")
-    ap.add_argument("--plan-curve", default="", help="--plan-only: JSON of measured (rows per forward, seconds) points "
-                                                      "(default profiles/r04_encode_rate_curve.json when present)")
-    args = ap.parse_args()
-    if args.plan_only:
-        plan_only(args)
-        return
-
+def encode_legs(args, eng, lm, fmt, schema_pml, t_first, world, rank, device, barrier):
+    """--full: the persona schema's encode again in steady state (``encode``) and the schema-library encode of BASELINE config 5
+    (``encode_library``, unless --no-library), both sharded over the ranks."""
     import torch
     import torch.distributed as dist
-
-    if os.environ.get("PC_BENCH_FAULT_S"):          # dev: dump every thread's stack and exit if the run is still going after N seconds
-        import faulthandler
-        faulthandler.dump_traceback_later(int(os.environ["PC_BENCH_FAULT_S"]), exit=True)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run for N > 1")
-    # test hooks (1-GPU smoke of the N > 1 code path): PC_BENCH_SAME_DEVICE=1 puts every rank on cuda:0 and
-    # PC_BENCH_BACKEND=gloo replaces RCCL (which refuses two ranks on one device)
-    if os.environ.get("PC_BENCH_SAME_DEVICE") == "1":
-        local_rank = 0
-    torch.cuda.set_device(local_rank)
-    device = f"cuda:{local_rank}"
-    if world > 1 or os.environ.get("PC_BENCH_FORCE_DIST") == "1":     # (test hook: a one-rank RCCL group runs the collectives below)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        backend = os.environ.get("PC_BENCH_BACKEND", "nccl")
-        if backend == "nccl":
-            dist.init_process_group(backend="nccl", device_id=torch.device(device))
-        else:
-            dist.init_process_group(backend=backend)
-
-    def barrier():
-        if dist.is_initialized():
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    import __graft_entry__ as ge
-    if rank == 0:
-        ge.build()
-    barrier()
-    from promptcache_amd import CacheEngine, Prompt, synth
-    from promptcache_amd.model import Llama2
-
-    if args.config != 1:
-        run_config(args, device, world, rank, barrier)
-        if dist.is_initialized():
-            barrier()
-            dist.destroy_process_group()
-        return
-    lm = Llama2(args.model, device=device, random_init=True, seed=0)
-    eng = CacheEngine(args.max_ctx, lm)
-    fmt = lm.get_formatter()
-    schema_pml, prompt_pml = synth.persona_like()
-
-    # ---- schema encode (module KV precompute): sharded over ranks + one all-gather ----
-    barrier()
-    t0 = time.perf_counter()
-    eng.add_schema(fmt(schema_pml))
-    barrier()
-    t_first = time.perf_counter() - t0           # includes hipBLASLt kernel selection / allocator warm-up
+    from promptcache_amd import synth
     eng.remove_schema("persona")
     barrier()
     t0 = time.perf_counter()
@@ -871,6 +860,100 @@ def main():
                            "broadcast from their owners at exact size, exchange of schema k overlapped with the encode of k+1"}
         for n in names:
             eng.remove_schema(n)
+    return encode, library
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3, 4],
+                    help="BASELINE.json config: 1 = the headline (llama2-7b shape, persona-structured schema); 2 = game-like "
+                         "schema (7b, max_ctx 5000); 3 = SQuAD-like entries (CodeLlama-7b); 4 = LongBench-like 8k context (13b). "
+                         "2-4 follow the reference's latency recipe (eval.py:172-219): every entry, cached and no_cache")
+    ap.add_argument("--model", default="llama2-7b")
+    ap.add_argument("--max-ctx", type=int, default=4096)        # config/llm_config_llama2_7b.json of the reference
+    ap.add_argument("--cpu-layers", type=int, default=8, help="layers the cpu_baseline TIMING runs (scaled by L/k)")
+    ap.add_argument("--parity-layers", type=int, default=0, help="layers of the parity leg (0 = all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-library", action="store_true", help="skip the schema-library encode leg (BASELINE config 5)")
+    ap.add_argument("--no-int8", action="store_true", help="skip the int8-weight context leg (builds a second model)")
+    ap.add_argument("--no-configs", action="store_true", help="skip the compact BASELINE config 2-4 legs of the default run")
+    ap.add_argument("--no-context", action="store_true", help="skip the extra (untimed) no-cache / decode / GEMM-roofline runs")
+    ap.add_argument("--plan-only", action="store_true",
+                    help="CPU only: print the predicted 1/2/4/8-GPU schedule of the schema-library encode and exit")
+    ap.add_argument("--plan-rate", type=float, default=72000.0, help="--plan-only: 1-GPU library encode rate, scaffold tokens/s")
+    ap.add_argument("--plan-link-gbs", type=float, default=153.0, help="--plan-only: one xGMI link, GB/s per direction")
+    ap.add_argument("--plan-curve", default="", help="--plan-only: JSON of measured (rows per forward, seconds) points "
+                                                      "(default profiles/r04_encode_rate_curve.json when present)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (encode, library, rooflines, context, int8, cpu_baseline, parity, "
+                         "configs 2-4); a plain run only sets up, warms up, times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (logits, new and sampled staged K/V, ids) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.plan_only:
+        plan_only(args)
+        return
+
+    import torch
+    import torch.distributed as dist
+
+    if os.environ.get("PC_BENCH_FAULT_S"):          # dev: dump every thread's stack and exit if the run is still going after N seconds
+        import faulthandler
+        faulthandler.dump_traceback_later(int(os.environ["PC_BENCH_FAULT_S"]), exit=True)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run for N > 1")
+    # test hooks (1-GPU smoke of the N > 1 code path): PC_BENCH_SAME_DEVICE=1 puts every rank on cuda:0 and
+    # PC_BENCH_BACKEND=gloo replaces RCCL (which refuses two ranks on one device)
+    if os.environ.get("PC_BENCH_SAME_DEVICE") == "1":
+        local_rank = 0
+    torch.cuda.set_device(local_rank)
+    device = f"cuda:{local_rank}"
+    if world > 1 or os.environ.get("PC_BENCH_FORCE_DIST") == "1":     # (test hook: a one-rank RCCL group runs the collectives below)
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        backend = os.environ.get("PC_BENCH_BACKEND", "nccl")
+        if backend == "nccl":
+            dist.init_process_group(backend="nccl", device_id=torch.device(device))
+        else:
+            dist.init_process_group(backend=backend)
+
+    def barrier():
+        if dist.is_initialized():
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    import __graft_entry__ as ge
+    if rank == 0:
+        ge.build()
+    barrier()
+    from promptcache_amd import CacheEngine, Prompt, synth
+    from promptcache_amd.model import Llama2
+
+    if args.config != 1:
+        run_config(args, device, world, rank, barrier)
+        if dist.is_initialized():
+            barrier()
+            dist.destroy_process_group()
+        return
+    lm = Llama2(args.model, device=device, random_init=True, seed=0)
+    eng = CacheEngine(args.max_ctx, lm)
+    fmt = lm.get_formatter()
+    schema_pml, prompt_pml = synth.persona_like()
+
+    # ---- schema encode (module KV precompute): sharded over ranks + one all-gather ----
+    barrier()
+    t0 = time.perf_counter()
+    eng.add_schema(fmt(schema_pml))
+    barrier()
+    t_first = time.perf_counter() - t0           # includes hipBLASLt kernel selection / allocator warm-up
+    encode = library = None
+    if args.full:
+        encode, library = encode_legs(args, eng, lm, fmt, schema_pml, t_first, world, rank, device, barrier)
 
     prompt = Prompt(prompt_pml, [fmt])
     pc = eng.prompt_cache
@@ -907,33 +990,16 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(out, ids, pos))
 
     S, q = len(pc), len(ids)
     ttft_ms = elapsed / args.steps * 1e3
     L, Hkv, D = lm.get_cache_shape()
     fused_gather = len(gather_evs) == 0          # the timed steps staged inside their attention launches: no copy launch to time
-    if fused_gather:
-        # pc_kv_gather itself (host tier, callers that look at `cache`, decode-only entries), on the same staging plan, eagerly
-        # after the timed region
-        segs = [(m.store.data_ptr(), len(m)) for m in pc.staged]
-        offs, o = [], 0
-        for _, ln in segs:
-            offs.append(o); o += ln
-        from promptcache_amd import _native as _n
-        for i in range(12):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _n.kv_gather([p_ for p_, _ in segs], [ln for _, ln in segs], offs, pc.arena.buf, pc.arena.L, pc.arena.Hkv, pc.arena.D, pc.arena.cap)
-            e1.record()
-            if i >= 2:
-                gather_evs.append((e0, e1))
-        torch.cuda.synchronize()
-    gather_us = sorted(a.elapsed_time(b) * 1e3 for a, b in gather_evs)
-    gather_avg_us = sum(gather_us) / len(gather_us)
     prefill_ms = sorted(a.elapsed_time(b) for a, b, _ in prefill_evs)
     process_ms = sorted(c for _, _, c in prefill_evs)
     alg_bytes = 2 * S * (2 * L * Hkv * D * 2)                # read once + write once
-    achieved = alg_bytes / (gather_avg_us * 1e-6) / 1e9
 
     result = {
         "metric": "cached_prefill_tokens_per_s", "value": world * (S + q) / (ttft_ms * 1e-3), "unit": "tokens/s",
@@ -947,20 +1013,41 @@ def main():
         "breakdown_ms": {"process_incl_gather_median": process_ms[len(process_ms) // 2],
                          "prefill_median": prefill_ms[len(prefill_ms) // 2],
                          "new_token_tokens_per_s": world * q / (ttft_ms * 1e-3)},
-        "roofline_gather": {"kernel": "kv_copy_kernel (pc_kv_gather)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                            "traffic": _pmc_traffic("kv_copy_kernel", f"S={S},L={L},Hkv={Hkv},D={D}")[0],
-                            "traffic_source": _pmc_traffic("kv_copy_kernel", f"S={S},L={L},Hkv={Hkv},D={D}")[1],
-                            "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": gather_avg_us,
-                            "min_launch_us": gather_us[0], "launches_timed": len(gather_us),
-                            "in_timed_step": not fused_gather,
-                            "how": ("HIP events around eager pc_kv_gather launches on the step's staging plan AFTER the timed region: the "
-                                    "timed steps stage inside their attention launches (pc_attn gather_rows) and launch no copy; "
-                                    "pc_kv_gather serves the host tier and callers that inspect the staged views") if fused_gather else
-                                   "HIP events recorded on the launch stream immediately around the launch, every timed step"},
-        "encode": encode,
-        "encode_library": library,
     }
+    if args.full:
+        if fused_gather:
+            # pc_kv_gather itself (host tier, callers that look at `cache`, decode-only entries), on the same staging plan, eagerly
+            # after the timed region
+            segs = [(m.store.data_ptr(), len(m)) for m in pc.staged]
+            offs, o = [], 0
+            for _, ln in segs:
+                offs.append(o); o += ln
+            from promptcache_amd import _native as _n
+            for i in range(12):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                _n.kv_gather([p_ for p_, _ in segs], [ln for _, ln in segs], offs, pc.arena.buf, pc.arena.L, pc.arena.Hkv, pc.arena.D, pc.arena.cap)
+                e1.record()
+                if i >= 2:
+                    gather_evs.append((e0, e1))
+            torch.cuda.synchronize()
+        gather_us = sorted(a.elapsed_time(b) * 1e3 for a, b in gather_evs)
+        gather_avg_us = sum(gather_us) / len(gather_us)
+        achieved = alg_bytes / (gather_avg_us * 1e-6) / 1e9
+        result["roofline_gather"] = {
+            "kernel": "kv_copy_kernel (pc_kv_gather)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": _pmc_traffic("kv_copy_kernel", f"S={S},L={L},Hkv={Hkv},D={D}")[0],
+            "traffic_source": _pmc_traffic("kv_copy_kernel", f"S={S},L={L},Hkv={Hkv},D={D}")[1],
+            "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": gather_avg_us,
+            "min_launch_us": gather_us[0], "launches_timed": len(gather_us),
+            "in_timed_step": not fused_gather,
+            "how": ("HIP events around eager pc_kv_gather launches on the step's staging plan AFTER the timed region: the "
+                    "timed steps stage inside their attention launches (pc_attn gather_rows) and launch no copy; "
+                    "pc_kv_gather serves the host tier and callers that inspect the staged views") if fused_gather else
+                   "HIP events recorded on the launch stream immediately around the launch, every timed step"}
+        result["encode"] = encode
+        result["encode_library"] = library
     # whole step against the HBM roof: every weight byte once + the gather (read + write) + the staged K/V once
     cfgm = lm.hf_model.config
     w_bytes = 2 * (cfgm.num_hidden_layers * (cfgm.hidden_size * (lm.hf_model.H + 2 * Hkv) * D + lm.hf_model.H * D * cfgm.hidden_size +
@@ -981,15 +1068,16 @@ def main():
                          "fused_gather_forwards": int(lm.hf_model.stats.get("fused_gather", 0)),
                          "host_glue_ms": ttft_ms - (process_ms[len(process_ms) // 2] + prefill_ms[len(prefill_ms) // 2]),
                          "what": "host_glue_ms = ms_per_step - (median process interval + median first-lm() interval)"}
+    context = args.full and not args.no_context              # the legs outside the timed region (--full)
     # `roofline` = the time-dominant hand-written kernel of the timed step (largest share in profiles/r03_bench_kernel_stats.txt)
-    if rank == 0 and not args.no_context:
+    if rank == 0 and context:
         result["roofline"], extra_rf = gemm_rooflines(lm, q)
         result.update(extra_rf)
         result["roofline_gemm"] = result["roofline"]          # (round 1-2 key of the gate|up figure)
-    if result.get("roofline") is None:
+    if result.get("roofline") is None and "roofline_gather" in result:
         result["roofline"] = dict(result["roofline_gather"], note="context legs off: the event-timed gather stands in; the "
                                                                    "dominant kernel needs the eager legs (drop --no-context)")
-    if rank == 0 and not args.no_context:
+    if rank == 0 and context:
         # context (outside the timed region): the same prompt WITHOUT the prompt cache (cache_engine.py:476-493:
         # every token re-encoded, positions range(N)) and the hipGraph-captured decode rate after the prefill
         nids, npos, _, _ = eng.process(prompt, no_cache=True)
@@ -1041,7 +1129,7 @@ def main():
                                             "how": "GreedyLoop: one hipGraph replay per token (forward + pc_greedy_advance), no "
                                                    "host round trip; what GenerationEngine.generate uses for greedy decoding"}
             del loop
-    if rank == 0 and not args.no_context:
+    if rank == 0 and context:
         # context: TTFT of a prompt whose new-token count has not been seen yet (an eager pass + hipGraph capture before
         # the first replay), then the same prompt again (replay): what a serving mix of question lengths pays once per length
         cold = []
@@ -1058,7 +1146,7 @@ def main():
                 torch.cuda.synchronize(); ts2.append((time.perf_counter() - t0) * 1e3)
             cold.append({"new_tokens": len(i2), "first_call_ms": ts2[0], "warm_ms": min(ts2[1:])})
         result["cold_shape_ttft"] = cold
-    if rank == 0 and not args.no_context:
+    if rank == 0 and context:
         # context: the same step with this prompt's modules in the HOST tier (pinned host memory, the reference's default
         # placement, cache_engine.py:283-296) -- pc_kv_gather then reads them in place over PCIe.  Never `value`.
         used = list(pc.staged)
@@ -1081,7 +1169,7 @@ def main():
         for m in used:
             m.upload(device)
         torch.cuda.synchronize()
-    if rank == 0 and not args.no_context and not args.no_int8:
+    if rank == 0 and context and not args.no_int8:
         # context: the reference's GPU configs load the model with load_in_8bit=True (config/llm_config_llama2_7b.json:5) =
         # LLM.int8() through bitsandbytes.  Here: the published algorithm (int8 weights, vector-wise
         # int8 activations, fp16 outlier columns at threshold 6.0), same prompt, same staged module KV (bit-identical
@@ -1169,11 +1257,11 @@ def main():
                                           "decode_device_loop_tokens_per_s is GreedyLoop (compare decode_device_loop); "
                                           "PC_INT8_WEIGHT_ONLY=1 selects round 1's weight-only mode"})
         result["int8_weights"] = i8
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         base, parity = cpu_baseline_and_parity(lm, eng, prompt, ids, pos, args.cpu_layers, parity_layers=args.parity_layers)
         result["cpu_baseline"] = base
         result["parity"] = parity
-    if rank == 0 and world == 1 and not args.no_context and not args.no_configs:
+    if rank == 0 and world == 1 and context and not args.no_configs:
         eng.remove_all_schemas()
         torch.cuda.empty_cache()
         result["configs"] = configs_leg(device, world, rank, barrier, lm)

@@ -159,7 +159,7 @@ def test_bench_py_two_ranks_on_one_gpu_plumbing():
     env = dict(os.environ, PC_BENCH_SAME_DEVICE="1", PC_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--model", "mid", "--max-ctx", "2048", "--no-context", "--no-cpu-baseline"]
+           "--model", "mid", "--max-ctx", "2048", "--full", "--no-context", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -239,7 +239,7 @@ def test_bench_py_collectives_run_on_rccl_with_one_rank():
     env.pop("PC_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--model", "mid", "--max-ctx", "2048", "--no-context", "--no-cpu-baseline"]
+           "--model", "mid", "--max-ctx", "2048", "--full", "--no-context", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,7 +1,7 @@
 # Round-6 evidence in one gpurun call: bash tools/collect_r06.sh   (writes gpurun_out/r06/*; summaries are copied to profiles/r06_* by hand)
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r06; mkdir -p $OUT
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 python bench.py --plan-only > $OUT/plan_only.json 2>/dev/null
 PC_ATTN_NO_WIDE=1 python bench.py --config 4 --steps 20 --warmup 3 2>/dev/null > $OUT/config4_ring_only.json
 python bench.py --config 4 --steps 20 --warmup 3 2>/dev/null > $OUT/config4_wide.json

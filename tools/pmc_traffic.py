@@ -21,7 +21,7 @@ for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
     d = os.path.join(OUT, ctr)
     if "--reuse" not in sys.argv:                       # (--reuse: only re-read the CSVs of an earlier run)
         subprocess.run(["rocprofv3", "--kernel-trace", "--pmc", ctr, "-d", d, "-o", "p", "-f", "csv", "--", sys.executable,
-                        os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-context", "--no-cpu-baseline",
+                        os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full", "--no-context", "--no-cpu-baseline",
                         "--no-library"], cwd="/tmp", env=env, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     f = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)[0]
     agg = collections.defaultdict(list)

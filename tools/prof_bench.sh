@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$1
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats -d $OUT/prof -o b -f csv -- python $R/bench.py --steps 40 --warmup 5 --no-context --no-cpu-baseline --no-library > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/prof -o b -f csv -- python $R/bench.py --steps 40 --warmup 5 --full --no-context --no-cpu-baseline --no-library > $OUT/bench.json 2> $OUT/bench.err
 python3 - <<PY
 import csv,glob
 f=glob.glob("$OUT/prof/**/*kernel_stats.csv", recursive=True)[0]
