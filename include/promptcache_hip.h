@@ -559,6 +559,27 @@ int pc_prefill_prologue(const void* host_block, void* dev_block, int32_t nbytes,
 int pc_greedy_advance(const float* logits, int32_t vocab, int64_t* ids, int32_t* pos, int32_t* past_len, int32_t* ring,
                       int32_t* counter, int32_t ring_cap, void* stream);
 
+/* Sampled decode without a host round trip per token: the sampled counterpart of pc_greedy_advance, the last node of a
+ * captured decode step.  The reference's chain (generation_engine.py:32-42: temperature, repetition penalty, top-p, top-k,
+ * in that order, with their thresholds) applied to logits[0..vocab) and the draw of :149-168 (greedy rule :159: argmax when
+ * temperature < 1e-5 or top_p < 1e-8; otherwise one sample of softmax over the kept tokens, taken here as Gumbel-max with
+ * Philox4x32-10 keyed by `seed`, counter (token / 4, *counter, 0, 0)).  The penalty applies to tokens whose bit is set in
+ * history_bits (ceil(vocab / 32) words); the drawn token's bit is set.  Then exactly pc_greedy_advance's contract: ids[0] =
+ * token, pos[0] += 1, past_len[0] += 1, ring[counter % ring_cap] = token, counter += 1.  The parameters live in device memory
+ * so that one captured graph serves every parameter set.  processed_out (optional, [vocab] fp32): the processed row, filtered
+ * tokens as -inf.  logits need only be 4-byte aligned; vocab < 2^24. */
+typedef struct pc_sample_params {
+    float temperature;
+    float repetition_penalty;
+    float top_p;
+    int32_t top_k;               /* <= 0: off */
+    uint64_t seed;
+} pc_sample_params;
+
+int pc_sample_advance(const float* logits, int32_t vocab, const pc_sample_params* params_dev, uint32_t* history_bits, int64_t* ids,
+                      int32_t* pos, int32_t* past_len, int32_t* ring, int32_t* counter, int32_t ring_cap, float* processed_out,
+                      void* stream);
+
 /* Diagnostics used by the GPU test-suite: dumps the MFMA C/D lane map and the LDS transpose-read
  * map the attention kernel relies on (probe_kernel in csrc/pc_misc.hip). */
 /* dev hook (tools/gemm_trace.py): weight-streaming launches issued by this thread stamp per-wave wall-clock times

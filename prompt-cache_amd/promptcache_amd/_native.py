@@ -46,6 +46,11 @@ class KvRow(C.Structure):
     _fields_ = [("base", C.c_uint64), ("plane_stride16", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class SampleParams(C.Structure):
+    """``pc_sample_params``: the device-resident parameter block of pc_sample_advance."""
+    _fields_ = [("temperature", _f32), ("repetition_penalty", _f32), ("top_p", _f32), ("top_k", _i32), ("seed", C.c_uint64)]
+
+
 KV_ROW_STAGED = 1
 KV_ROW_TABLE_MAX_SEG = 1024
 
@@ -144,6 +149,7 @@ SIGNATURES = {
     "pc_rope_append_var": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp,
                                      _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pc_greedy_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "pc_sample_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pc_quant_act_i8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_rmsnorm_quant_i8": (C.c_int, [_vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_outlier_corr": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -683,6 +689,21 @@ def greedy_advance(logits, vocab: int, ids, pos, past, ring, counter, stream: Op
     rc = load().pc_greedy_advance(logits.data_ptr(), vocab, ids.data_ptr(), pos.data_ptr(), past.data_ptr(), ring.data_ptr(),
                                   counter.data_ptr(), ring.numel(), current_stream() if stream is None else stream)
     check(rc, "pc_greedy_advance")
+
+
+def sample_params_bytes(temperature: float, repetition_penalty: float, top_p: float, top_k: int, seed: int) -> bytes:
+    """The ``pc_sample_params`` image of one parameter set (what the device-resident block of pc_sample_advance holds)."""
+    return bytes(SampleParams(float(temperature), float(repetition_penalty), float(top_p), int(top_k), int(seed) & (2 ** 64 - 1)))
+
+
+def sample_advance(logits, vocab: int, params, history, ids, pos, past, ring, counter, processed_out=None,
+                   stream: Optional[int] = None) -> None:
+    """Tail of a captured sampled decode step (pc_sample_advance): the reference's logits chain + one draw -> the graph's own
+    input words, the token ring and the history bitmap.  ``params``: a device tensor holding one ``SampleParams``."""
+    rc = load().pc_sample_advance(logits.data_ptr(), vocab, params.data_ptr(), history.data_ptr(), ids.data_ptr(), pos.data_ptr(),
+                                  past.data_ptr(), ring.data_ptr(), counter.data_ptr(), ring.numel(), _ptr(processed_out),
+                                  current_stream() if stream is None else stream)
+    check(rc, "pc_sample_advance")
 
 
 # ---- LLM.int8 (pc_int8.hip) -------------------------------------------------------------------------------------------

@@ -89,6 +89,9 @@ class _Timer:
 class GenerationEngine:
     # decode greedy generations as a device-side loop when the model offers one (PC_DEVICE_GREEDY=0: step through lm())
     device_greedy_loop = os.environ.get("PC_DEVICE_GREEDY", "1") != "0"
+    # ... and every other generation (sampled, or greedy with a repetition penalty) as the sampled device loop
+    # (model/llama_hip.py SampleLoop; PC_DEVICE_SAMPLE=0: step through lm() and torch's sampler)
+    device_sample_loop = os.environ.get("PC_DEVICE_SAMPLE", "1") != "0"
 
     def __init__(self, lm: LanguageModel, verbose: bool = False):
         self.lm = lm
@@ -139,9 +142,17 @@ class GenerationEngine:
         # hipGraph replay that also picks the token and feeds it to the next replay (model/llama_hip.py GreedyLoop).
         # The host keeps ONE replay in flight ahead of the token it is looking at, so stop conditions are evaluated
         # exactly as below while the GPU never waits for the host; a step enqueued past a stop is simply discarded.
+        #
+        # Every other generation runs as the sampled device loop (model/llama_hip.py SampleLoop): the last node of each replay
+        # applies the reference's logits chain and draws the token on the GPU (pc_sample_advance).  The first token is drawn
+        # from the prefill logits by the same kernel at step 0 of the same random stream, whose seed comes from torch's default
+        # generator, so torch.manual_seed governs reproducibility.
         loop = None
-        want_loop = params.greedy and params.repetition_penalty <= 1.0 and not use_full_position_ids and \
-            hasattr(getattr(self.lm, "hf_model", None), "greedy_loop") and self.device_greedy_loop
+        hf = getattr(self.lm, "hf_model", None)
+        plain_greedy = params.greedy and params.repetition_penalty <= 1.0
+        want_loop = plain_greedy and not use_full_position_ids and hasattr(hf, "greedy_loop") and self.device_greedy_loop
+        want_sample = not plain_greedy and not use_full_position_ids and hasattr(hf, "sample_loop") and self.device_sample_loop
+        seed = int(torch.randint(0, 2 ** 62, (1,))) if want_sample else 0
 
         try:
             for step in range(params.max_new_tokens):
@@ -175,8 +186,13 @@ class GenerationEngine:
                     logits, past, ms = self._forward([new_ids[-1]], positions, past)
                 total_ms += ms
 
-                history = torch.as_tensor([output_ids], device=self.lm.device) if params.repetition_penalty > 1.0 else None
-                token = self._pick(processors(history, logits[:, -1, :])[0], params.greedy)
+                if step == 0 and want_sample:
+                    want_sample = hf.can_loop(past)
+                if want_sample:                                    # (step 0 only: the loop draws every later token)
+                    token = hf.sample_token(logits[0, -1], params, seed, output_ids)
+                else:
+                    history = torch.as_tensor([output_ids], device=self.lm.device) if params.repetition_penalty > 1.0 else None
+                    token = self._pick(processors(history, logits[:, -1, :])[0], params.greedy)
                 output_ids.append(token)
                 new_ids.append(token)
 
@@ -188,9 +204,12 @@ class GenerationEngine:
                         yield Output(text, new_text, total_ms, ttft_ms)
                 if done:
                     break
-                if step == 0 and want_loop and params.max_new_tokens > 1:
+                if step == 0 and (want_loop or want_sample) and params.max_new_tokens > 1:
                     # the first decoded token sits at position first_free + 1 (the reference's loop index starts at 1, :132)
-                    loop = self.lm.hf_model.greedy_loop(past, token, first_free + 1, params.max_new_tokens)
+                    if want_loop:
+                        loop = hf.greedy_loop(past, token, first_free + 1, params.max_new_tokens)
+                    else:
+                        loop = hf.sample_loop(past, token, first_free + 1, params.max_new_tokens, params, seed, output_ids)
                     if loop is not None:
                         loop.enqueue()
         finally:

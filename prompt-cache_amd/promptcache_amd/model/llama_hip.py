@@ -24,6 +24,7 @@ There is no CPU / eager fallback: without the HIP extension this module raises.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from dataclasses import dataclass
@@ -132,7 +133,7 @@ class GreedyLoop:
     RING = 4096
 
     @torch.inference_mode()
-    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int):
+    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, ctr0: int = 0):
         self.m = model
         past_len = arena.length
         need = past_len + max_new + 2
@@ -148,7 +149,8 @@ class GreedyLoop:
         dev = model.device
         st["ids"].copy_(torch.tensor([token], dtype=torch.int64), non_blocking=True)
         st["pos"].copy_(torch.tensor([position], dtype=torch.int32), non_blocking=True)
-        st["ctr"].zero_()
+        st["ctr"].fill_(ctr0)
+        self.ctr0 = ctr0                 # the device step counter at slot 0 (slot i's token lands in ring[(ctr0 + i) % RING])
         self.len0 = past_len
         self.n = 0                       # replays enqueued
         self._last_ent = None
@@ -164,7 +166,7 @@ class GreedyLoop:
                                "GenerationEngine.device_greedy_loop = False to interleave generations)")
         past_len = self.len0 + self.n
         m._lo_mode = m._tail_mode(a, 1, past_len)
-        ent = m._loop_graph(a, past_len)
+        ent = self._graph(a, past_len)
         # host-known words of the step (the kernels read past_len / tail base from the device)
         if self.n == 0 or ent is not self._last_ent:
             st["past"][0:1].fill_(past_len)
@@ -176,7 +178,8 @@ class GreedyLoop:
         ent[0].replay()
         e1.record()
         i = self.n
-        self.host[i % self.RING: i % self.RING + 1].copy_(st["ring"][i % self.RING: i % self.RING + 1], non_blocking=True)
+        r = (self.ctr0 + i) % self.RING
+        self.host[r: r + 1].copy_(st["ring"][r: r + 1], non_blocking=True)
         done = torch.cuda.Event()
         done.record()
         self.events.append((e0, e1, done))
@@ -187,7 +190,7 @@ class GreedyLoop:
 
     def token(self, i: int) -> int:
         self.events[i][2].synchronize()
-        return int(self.host[i % self.RING])
+        return int(self.host[(self.ctr0 + i) % self.RING])
 
     def close(self, consumed: int) -> None:
         """The generation ended after ``consumed`` of the enqueued steps were used: a look-ahead replay enqueued past the
@@ -203,6 +206,36 @@ class GreedyLoop:
         e0, e1, done = self.events[i]
         done.synchronize()
         return e0.elapsed_time(e1)
+
+    def _graph(self, arena: KVArena, past_len: int):
+        return self.m._loop_graph(arena, past_len)
+
+
+def _history_bits(ids, vocab: int) -> torch.Tensor:
+    """Host bitmap (int32 [ceil(vocab / 32)]) with the bit of every id in ``ids`` set (ids outside the vocabulary ignored)."""
+    bits = np.zeros((vocab + 31) // 32, dtype=np.uint32)
+    a = np.asarray(list(ids), dtype=np.int64)
+    a = a[(a >= 0) & (a < vocab)]
+    np.bitwise_or.at(bits, a >> 5, (np.uint32(1) << (a & 31).astype(np.uint32)))
+    return torch.from_numpy(bits.view(np.int32))
+
+
+class SampleLoop(GreedyLoop):
+    """Sampled decode steps that never leave the GPU (reference loop: generation_engine.py:123-168, sampling branch :149-163).
+
+    GreedyLoop's protocol and state, with ``pc_sample_advance`` as the graph's last node: the reference's logits chain and one
+    draw per step from the parameter block and the history bitmap of the loop state (device words, so one captured graph
+    serves every parameter set).  The first token was drawn from the prefill logits at step 0 (``LlamaHIP.sample_token``);
+    the loop's steps continue that random stream at 1, 2, ..."""
+
+    @torch.inference_mode()
+    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, params, seed: int,
+                 history_ids):
+        super().__init__(model, arena, token, position, max_new, ctr0=1)
+        model._sample_state_fill(self.st, params, seed, history_ids)
+
+    def _graph(self, arena: KVArena, past_len: int):
+        return self.m._loop_graph(arena, past_len, sample=True)
 
 
 class LlamaHIP:
@@ -1335,20 +1368,46 @@ class LlamaHIP:
         residual-tail base}, the token ring and its counter (see GreedyLoop)."""
         st = getattr(self, "_loop_st", None)
         if st is None:
-            dev = self.device
-            st = dict(ids=torch.zeros(1, dtype=torch.int64, device=dev), pos=torch.zeros(1, dtype=torch.int32, device=dev),
-                      past=torch.zeros(2, dtype=torch.int32, device=dev), ring=torch.zeros(GreedyLoop.RING, dtype=torch.int32, device=dev),
-                      ctr=torch.zeros(1, dtype=torch.int32, device=dev))
+            st = self._new_loop_state(GreedyLoop.RING)
             self._loop_st = st
         return st
 
-    def _loop_graph(self, arena: KVArena, past_len: int):
-        """The captured graph of ONE greedy decode step over ``arena`` (forward of the token in the loop state + argmax +
-        state advance), keyed like ``_graphed_skinny``."""
+    def _new_loop_state(self, ring: int) -> dict:
+        dev = self.device
+        return dict(ids=torch.zeros(1, dtype=torch.int64, device=dev), pos=torch.zeros(1, dtype=torch.int32, device=dev),
+                    past=torch.zeros(2, dtype=torch.int32, device=dev), ring=torch.zeros(ring, dtype=torch.int32, device=dev),
+                    ctr=torch.zeros(1, dtype=torch.int32, device=dev),
+                    # pc_sample_advance's parameter block (pc_sample_params) and history bitmap
+                    params=torch.zeros(ctypes.sizeof(_native.SampleParams), dtype=torch.uint8, device=dev),
+                    hist=torch.zeros((self.config.vocab_size + 31) // 32, dtype=torch.int32, device=dev))
+
+    def _sample_state_fill(self, st: dict, params, seed: int, history_ids) -> None:
+        """Parameter block and history bitmap of a sampled generation into the state ``st`` (ordered on the current stream)."""
+        blk = _native.sample_params_bytes(params.temperature, params.repetition_penalty, params.top_p, params.top_k, seed)
+        st["params"].copy_(torch.frombuffer(bytearray(blk), dtype=torch.uint8))
+        st["hist"].copy_(_history_bits(history_ids, self.config.vocab_size))
+
+    @torch.inference_mode()
+    def sample_token(self, logits_row: torch.Tensor, params, seed: int, history_ids, step: int = 0) -> int:
+        """One eager draw of pc_sample_advance from a [vocab] fp32 row (the prefill's last row), at ``step`` of the random
+        stream of ``seed``, on a scratch state of its own (the device loop's words are not touched)."""
+        V = self.config.vocab_size
+        assert logits_row.dtype == torch.float32 and logits_row.numel() == V and logits_row.stride(-1) == 1
+        st = getattr(self, "_draw_st", None)
+        if st is None:
+            st = self._draw_st = self._new_loop_state(1)
+        self._sample_state_fill(st, params, seed, history_ids)
+        st["ctr"].fill_(step)
+        _native.sample_advance(logits_row, V, st["params"], st["hist"], st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
+        return int(st["ids"][0])
+
+    def _loop_graph(self, arena: KVArena, past_len: int, sample: bool = False):
+        """The captured graph of ONE greedy (``sample``: sampled) decode step over ``arena`` (forward of the token in the loop
+        state + argmax / draw + state advance), keyed like ``_graphed_skinny``."""
         n = _native
         nsplit_key = n.attn_workspace_bytes(1, self.H, self.D, 1, past_len + 1)
         mode = self._lo_mode
-        key = ("loop", arena.buf.data_ptr(), arena.cap, nsplit_key, self.fuse_norm, self.use_chain, mode,
+        key = ("loop",) + (("sample",) if sample else ()) + (arena.buf.data_ptr(), arena.cap, nsplit_key, self.fuse_norm, self.use_chain, mode,
                arena.tail_lo.data_ptr() if mode else 0, arena.tail_lo.shape[4] if mode else 0)
         ent = self._graphs.pop(key, None)
         if ent is not None:
@@ -1369,14 +1428,15 @@ class LlamaHIP:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             out = self._forward_skinny(st["ids"], st["pos"], st["past"], arena, 1, 1, past_len, False, None)
-            n.greedy_advance(out, V, st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
+            if sample:
+                n.sample_advance(out, V, st["params"], st["hist"], st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
+            else:
+                n.greedy_advance(out, V, st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
         ent = (g, out)
         self._graphs[key] = ent
         return ent
 
-    def greedy_loop(self, past, token: int, position: int, max_new: int) -> Optional["GreedyLoop"]:
-        """A device-side greedy decode loop over the arena behind ``past`` (None when this model / cache cannot host one:
-        the caller then steps through ``__call__``)."""
+    def _loop_arena(self, past) -> Optional[KVArena]:
         if not (self.skinny and self.use_graphs and self.supports_greedy_loop):
             return None
         found = arena_from_past(past, self.L, self.Hkv, self.D)
@@ -1384,7 +1444,24 @@ class LlamaHIP:
             return None
         arena, S = found
         arena.length = S
-        return GreedyLoop(self, arena, token, position, max_new)
+        return arena
+
+    def can_loop(self, past) -> bool:
+        """Whether ``greedy_loop`` / ``sample_loop`` over ``past`` would give a loop (not None)."""
+        return self._loop_arena(past) is not None
+
+    def greedy_loop(self, past, token: int, position: int, max_new: int) -> Optional["GreedyLoop"]:
+        """A device-side greedy decode loop over the arena behind ``past`` (None when this model / cache cannot host one:
+        the caller then steps through ``__call__``)."""
+        arena = self._loop_arena(past)
+        return None if arena is None else GreedyLoop(self, arena, token, position, max_new)
+
+    def sample_loop(self, past, token: int, position: int, max_new: int, params, seed: int, history_ids) -> Optional["SampleLoop"]:
+        """A device-side sampled decode loop (``params``: temperature, repetition_penalty, top_p, top_k as in
+        GenerationParameters; ``history_ids``: the ids the repetition penalty sees, ``token`` included) over the arena
+        behind ``past``, continuing the random stream of ``seed`` at step 1.  None where ``greedy_loop`` gives None."""
+        arena = self._loop_arena(past)
+        return None if arena is None else SampleLoop(self, arena, token, position, max_new, params, seed, history_ids)
 
     def _ks_buffers(self, hid: int):
         """Scratch slabs + arrival counters of pc_gemm_skinny_ks (shared by every such launch of the model: they run one
