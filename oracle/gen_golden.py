@@ -18,6 +18,9 @@ Fixtures
   model_<case>.npz   tensors from the reference CacheEngine / GenerationEngine / LlamaForCausalLM on CPU:
                      cached-prefill logits, no-cache logits, layer-0 attention output, sampled rows of the
                      staged KV and of the stored module KV, greedy tokens, inv_freq
+  sampling_chain.npz, sampling_chain_vocab.npz
+                     the reference's logits-processor chain (--sampling-only): processed rows at V = 96, kept sets at
+                     V = 1001 .. 128 256
 """
 from __future__ import annotations
 
@@ -733,6 +736,148 @@ def sampling_goldens(pc):
     np.savez(os.path.join(GOLD, "sampling_chain.npz"), params=np.array(SAMPLING_CASES, dtype=np.float64), logits=logits,
              history=history, processed=out)
     print(f"[golden] sampling_chain: {len(SAMPLING_CASES)} parameter sets, V={V}")
+    sampling_vocab_goldens(pc)
+
+
+# sampling_chain_vocab.npz: the same chain at real vocabulary sizes.  A row is int16 codes x 2^exp2 (exact in fp32); four codes
+# are sentinels for the values a code times a power of two cannot spell (the format: tests/sample_ref.py vocab_cases()).
+VOCAB_SIZES = (1001, 32000, 32016, 50432, 65024, 65537, 128256)
+VOCAB_TOP_P = (1e-8, 1e-7, 0.1, 0.5, 0.9, 0.95, 0.999, 0.99999997)
+VOCAB_TEMPERATURE = (1e-5, 0.05, 0.7, 1.0, 2.0, 100.0)
+VOCAB_PENALTY = (1.0, 1.1, 2.0)
+
+
+# the families each vocabulary size carries besides "equal" and "two_level" (which cost nothing to store), and the resolution
+# of their Gaussian bodies (codes per standard deviation): the fixture's size budget is the int16 codes of the large rows
+VOCAB_FAMILIES = {
+    1001: {f: 256 for f in ("gauss_0.5", "gauss_3", "gauss_30", "quarter", "dominant", "half_ninf_nan", "one_to_two",
+                            "signed_zero", "pinf")},
+    32000: {"gauss_0.5": 16, "quarter": 0, "dominant": 1, "pinf": 1},
+    32016: {"gauss_3": 16, "one_to_two": 0, "half_ninf_nan": 2, "signed_zero": 4},
+    50432: {"gauss_30": 4},
+    65024: {"gauss_3": 4},
+    65537: {"gauss_0.5": 2, "half_ninf_nan": 1},
+    128256: {"gauss_30": 2, "signed_zero": 1},
+}
+
+
+def _vocab_rows(V: int, rng):
+    """(family, codes int16 [V], exp2) of the rows at one vocabulary size."""
+    from tests.sample_ref import CODE_NAN, CODE_NEGZERO, CODE_NINF, CODE_PINF
+    def gauss(sigma_log2, res):
+        return np.clip(np.rint(rng.standard_normal(V) * res), -32000, 32000).astype(np.int16), sigma_log2 - int(np.log2(res))
+
+    def scatter(c, code, n):
+        c = c.copy()
+        c[rng.choice(V, n, replace=False)] = code
+        return c
+
+    rows = [("equal", (np.full(V, 3, dtype=np.int16), -1))]                                  # 1.5 everywhere
+    two = np.zeros(V, dtype=np.int16)
+    two[rng.choice(V, min(V // 4, 700), replace=False)] = 1
+    rows.append(("two_level", (two, 0)))                                                      # 1.0 x some hundreds, else 0.0
+    for fam, res in VOCAB_FAMILIES[V].items():
+        if fam.startswith("gauss_"):
+            row = gauss({"0.5": -1, "3": 2, "30": 5}[fam[6:]], res)                          # sigma 0.5, 4, 32
+        elif fam == "quarter":
+            row = (np.rint(rng.standard_normal(V) * 12).astype(np.int16), -2)                 # multiples of 1/4, sigma 3: ties
+        elif fam == "dominant":
+            c, e = gauss(0, res)
+            c[rng.integers(V)] = res * 50
+            row = (c, e)
+        elif fam == "half_ninf_nan":
+            c, e = gauss(1, res)
+            c[rng.permutation(V)[:V // 2]] = CODE_NINF
+            row = (scatter(c, CODE_NAN, 5), e)
+        elif fam == "one_to_two":
+            row = ((16384 + 513 * rng.integers(0, 32, V)).astype(np.int16), -14)            # [1, 2): one top key byte
+        elif fam == "signed_zero":
+            c = -(rng.geometric(0.5, V) * res).astype(np.int16)                               # negatives, -1 .. -16 ...
+            idx = rng.permutation(V)
+            c[idx[:20]] = 2 * res                                                             # ... 20 tokens at +2 ...
+            c[idx[20:620]] = 0                                                                # ... and 600 zeros, half of them -0
+            c[idx[20:320]] = CODE_NEGZERO
+            row = (c, -int(np.log2(res)))
+        else:                                                                                 # pinf
+            c, e = gauss(1, res)
+            row = (scatter(c, CODE_PINF, 3), e)
+        rows.append((fam, row))
+    return rows
+
+
+def _vocab_params(V: int, fam: str, x: np.ndarray, r: int, rng):
+    """Parameter sets (T, rp, top_p, top_k) and their history kinds for one row; r: the row's running number (rotates the
+    lists so that every value meets every vocabulary size over the fixture)."""
+    TP, TT, RP = VOCAB_TOP_P, VOCAB_TEMPERATURE, VOCAB_PENALTY
+    TK = (1, 2, 40, V - 1, V, V + 1)
+    out = [((1.0, 1.0, TP[r % 8], -1), "few"),
+           ((TT[r % 6], RP[r % 3], 1.0, TK[r % 6]), "most" if r % 2 else "few"),
+           ((TT[(r + 2) % 6], RP[(r + 1) % 3], TP[(r + 3) % 8], TK[(r + 2) % 6]), "few"),
+           ((0.7, 1.1, 0.95, -1), "most"),
+           ((TT[(r + 4) % 6], RP[(r + 2) % 3], TP[(r + 5) % 8], -1), "few")]
+    fin = np.where(np.isnan(x), -np.inf, x)
+    if fam in ("quarter", "gauss_3", "two_level", "equal"):
+        # a k whose kth value is shared by hundreds of tokens (the k-th largest sits inside its tie run)
+        s = np.sort(fin)[::-1]
+        vals, first, counts = np.unique(-s, return_index=True, return_counts=True)
+        j = int(np.argmax(counts >= 200))
+        out.append(((1.0, 2.0, 1.0, int(first[j] + counts[j] // 2)), "few"))
+        out.append(((0.7, 1.0, 0.9, int(first[j] + counts[j] // 3)), "few"))
+    if fam == "signed_zero":
+        # top-k and top-p boundaries on the zeros: k inside the run, top_p halfway through its mass
+        e = np.exp(fin.astype(np.float64) - fin.max())
+        e /= e.sum()
+        pos, zero = e[fin > 0].sum(), e[fin == 0].sum()
+        out.append(((1.0, 1.0, 1.0, 20 + 300), "few"))
+        out.append(((1.0, 1.0, float(pos + zero / 2), -1), "few"))
+        out.append(((1.0, 1.0, float(pos + zero / 3), 20 + 450), "few"))
+    return out
+
+
+def _vocab_history(V: int, kind: str, rng) -> np.ndarray:
+    if kind == "few":
+        return np.concatenate([[31, 32, V - 1], rng.integers(0, V, 37)]).astype(np.int64)
+    ids = np.arange(V - V // 10)                      # most of the vocabulary: all but every seventh id and the top tenth
+    return ids[ids % 7 != 5]
+
+
+def sampling_vocab_goldens(pc):
+    """The reference's chain (generation_engine.py:32-42, applied as at :150-155) at real vocabulary sizes: value families
+    that put the top-p and top-k boundaries inside tie runs, on signed zeros, next to -inf / NaN / +inf entries; histories
+    that hold ids 31, 32, V - 1 or most of the vocabulary.  Kept sets as bits (kept values are IEEE functions of the row)."""
+    import torch
+    from tests.sample_ref import decode_vocab_row, rank_order
+    GP = pc.generation_engine.GenerationParameters
+    rng = np.random.default_rng(2024)
+    vs, exps, fams, codes = [], [], [], []
+    case_row, params, hist_bits, kept_bits = [], [], [], []
+    r = 0
+    for V in VOCAB_SIZES:
+        for fam, (c, e) in _vocab_rows(V, rng):
+            x = decode_vocab_row(c, e)
+            for (t, rp, tp, tk), kind in _vocab_params(V, fam, x, r, rng):
+                h = _vocab_history(V, kind, rng)
+                chain = GP(temperature=t, repetition_penalty=rp, top_p=tp, top_k=tk).get_logits_processor()
+                hist = torch.as_tensor(h[None]) if rp > 1.0 else None
+                got = chain(hist, torch.from_numpy(x[None].copy()))[0].numpy()
+                hb = np.zeros(V, dtype=bool)
+                hb[h] = True
+                case_row.append(len(vs))
+                params.append((t, rp, tp, tk))
+                hist_bits.append(np.packbits(hb))
+                kept_bits.append(np.packbits((got != -np.inf)[rank_order(x)]))
+            vs.append(V)
+            exps.append(e)
+            fams.append(fam)
+            codes.append(c)
+            r += 1
+    path = os.path.join(GOLD, "sampling_chain_vocab.npz")
+    np.savez_compressed(path, vocab=np.array(vs, dtype=np.int32), exp2=np.array(exps, dtype=np.int8), family=np.array(fams),
+                        codes=np.concatenate(codes), case_row=np.array(case_row, dtype=np.int32),
+                        params=np.array(params, dtype=np.float64), history_bits=np.concatenate(hist_bits),
+                        kept_bits=np.concatenate(kept_bits))
+    print(f"[golden] sampling_chain_vocab: {len(vs)} rows, {len(params)} cases, {os.path.getsize(path)} bytes")
+
 
 def falcon_goldens(pc):
     """Falcon adapter fixtures (reference FalconForCausalLM, multi-query cache shape (L, 1, D))."""

@@ -6,8 +6,9 @@ Follows ``promptcache/generation_engine.py``:
   * application to the last row of logits             :150-155 (history ids only when repetition_penalty > 1)
   * greedy rule                                       :159     (temperature < 1e-5 or top_p < 1e-8 -> argmax)
 The four processors are ``transformers`` classes (pinned 4.34.0 in the reference's requirements.txt:13, 5.x installed
-here); their published semantics are restated below.  Pinned by tests/golden/sampling_chain.npz, which
-``oracle/gen_golden.py --sampling-only`` produced by running the REFERENCE's own ``GenerationParameters`` chain.
+here); their published semantics are restated below.  Pinned by tests/golden/sampling_chain.npz (V = 96) and
+sampling_chain_vocab.npz (V = 1001 .. 128 256), which ``oracle/gen_golden.py --sampling-only`` produced by running the
+REFERENCE's own ``GenerationParameters`` chain.
 """
 from __future__ import annotations
 
@@ -29,11 +30,15 @@ def process_logits(logits: np.ndarray, history: Optional[Sequence[int]], tempera
         v = x[idx]
         x[idx] = np.where(v < 0, v * np.float32(repetition_penalty), v / np.float32(repetition_penalty))
     if 1e-8 <= top_p < 1.0:                                        # TopPLogitsWarper (min_tokens_to_keep = 1)
-        order = np.argsort(x, kind="stable")                       # ascending, as torch.sort(descending=False)
-        sx = x[order]
-        e = np.exp(sx - sx.max())
-        cum = np.cumsum((e / e.sum()).astype(np.float32), dtype=np.float32)
-        remove = cum <= np.float32(1.0 - top_p)
+        # The cut is the reference's fp32 arithmetic: torch's softmax and cumsum over the ascending sorted row.  numpy's exp,
+        # sum and fp32 cumsum round differently, and at 10^5 tokens that moves the cut by up to a hundred tokens of a tie run
+        # (tests/golden/sampling_chain_vocab.npz).  Equal values add equal mass, so HOW MANY tokens of each value go does not
+        # depend on how the sort orders ties; WHICH go does, and torch.sort(stable=False) on the CPU leaves that unspecified.
+        # Here, as on the device, the lower indices of a tie run go first (a stable ascending sort).
+        import torch
+        order = np.argsort(x, kind="stable")
+        cum = torch.from_numpy(x[order]).softmax(-1).cumsum(-1)
+        remove = (cum <= (1.0 - top_p)).numpy()
         remove[-1] = False                                         # always keep the most probable token
         x[order[remove]] = NEG_INF
     if top_k > 0:                                                  # TopKLogitsWarper

@@ -220,6 +220,25 @@ def _history_bits(ids, vocab: int) -> torch.Tensor:
     return torch.from_numpy(bits.view(np.int32))
 
 
+def sample_params_block(params, seed: int) -> bytes:
+    """The ``pc_sample_params`` image of a generation's ``GenerationParameters``, canonical: every decision the reference takes
+    in double (generation_engine.py:32-42 and the greedy rule of :159) is taken here, so that the kernel's fp32 re-tests of
+    the same thresholds cannot decide otherwise.  Greedy -> T = 0; no temperature warper -> T = 1; no top-p warper -> top_p = 1;
+    no penalty processor -> rp = 1; top_k clamped into [-1, 2^31 - 1] (<= 0: off).  What stays is a top_p in [1e-8, 1) that
+    rounds to 1.0f (top-p off on the device; the mass involved is below 1e-7)."""
+    T, rp, top_p, top_k = float(params.temperature), float(params.repetition_penalty), float(params.top_p), int(params.top_k)
+    if params.greedy:
+        T = 0.0
+    elif not (T >= 1e-5 and T != 1.0):
+        T = 1.0
+    if not (1e-8 <= top_p < 1.0):
+        top_p = 1.0
+    if not rp > 1.0:
+        rp = 1.0
+    top_k = -1 if top_k <= 0 else min(top_k, 2 ** 31 - 1)
+    return _native.sample_params_bytes(T, rp, top_p, top_k, seed)
+
+
 class SampleLoop(GreedyLoop):
     """Sampled decode steps that never leave the GPU (reference loop: generation_engine.py:123-168, sampling branch :149-163).
 
@@ -1383,7 +1402,7 @@ class LlamaHIP:
 
     def _sample_state_fill(self, st: dict, params, seed: int, history_ids) -> None:
         """Parameter block and history bitmap of a sampled generation into the state ``st`` (ordered on the current stream)."""
-        blk = _native.sample_params_bytes(params.temperature, params.repetition_penalty, params.top_p, params.top_k, seed)
+        blk = sample_params_block(params, seed)
         st["params"].copy_(torch.frombuffer(bytearray(blk), dtype=torch.uint8))
         st["hist"].copy_(_history_bits(history_ids, self.config.vocab_size))
 

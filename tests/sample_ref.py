@@ -6,6 +6,7 @@ uniform u_i = ((word[i & 3] >> 8) + 0.5) * 2^-24, the Gumbel-max draw argmax_i (
 the greedy rule (temperature < 1e-5 or top_p < 1e-8: argmax of the processed row, the lowest index among equal maxima)."""
 from __future__ import annotations
 
+import os
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -64,3 +65,66 @@ def draw(logits: np.ndarray, history: Optional[Sequence[int]], temperature: floa
     rest = np.delete(s, tok)
     second = rest.max() if rest.size else -np.inf
     return tok, float(s[tok] - second), proc
+
+
+# ---- tests/golden/sampling_chain_vocab.npz (oracle/gen_golden.py sampling_vocab_goldens) ----------------------------------
+# A row is int16 codes x 2^exp2 (exact in fp32), with four sentinel codes; a case is one row, a parameter set, a history (bits
+# over the vocabulary) and the reference's kept set (bits in rank_order of the row: a prefix, whatever the row, packs to nothing).
+CODE_NINF, CODE_NAN, CODE_NEGZERO, CODE_PINF = -32768, -32767, -32766, 32767
+VOCAB_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sampling_chain_vocab.npz")
+
+
+def decode_vocab_row(codes: np.ndarray, exp2: int) -> np.ndarray:
+    x = codes.astype(np.float32) * np.float32(2.0 ** int(exp2))
+    x[codes == CODE_NINF] = -np.inf
+    x[codes == CODE_PINF] = np.inf
+    x[codes == CODE_NAN] = np.nan
+    x[codes == CODE_NEGZERO] = -0.0
+    return x
+
+
+def rank_order(x: np.ndarray) -> np.ndarray:
+    """Token ids in top-p rank order: value descending, the higher index first among equal values (-0 == +0), NaN ahead of
+    everything (torch's ascending sort puts it last)."""
+    nan = np.isnan(x)
+    v = np.where(nan, np.inf, x).astype(np.float64)
+    return np.lexsort((-np.arange(x.size), -v, -nan.astype(np.int8)))
+
+
+def vocab_cases(path: str = VOCAB_GOLD):
+    """-> dicts: row, family, logits (fp32 [V]), history (int64 ids), T, rp, top_p, top_k, kept (bool [V], the reference's)."""
+    z = np.load(path, allow_pickle=False)
+    V = z["vocab"].astype(np.int64)
+    row_off = np.concatenate([[0], np.cumsum(V)])
+    rows = [decode_vocab_row(z["codes"][row_off[i]:row_off[i + 1]], z["exp2"][i]) for i in range(V.size)]
+    orders = {}
+    hb, kb = z["history_bits"], z["kept_bits"]
+    off = 0
+    for c, r in enumerate(z["case_row"]):
+        v, x, nb = int(V[r]), rows[r], (int(V[r]) + 7) // 8
+        hist = np.nonzero(np.unpackbits(hb[off:off + nb], count=v))[0]
+        if r not in orders:
+            orders[r] = rank_order(x)
+        kept = np.zeros(v, dtype=bool)
+        kept[orders[r]] = np.unpackbits(kb[off:off + nb], count=v).astype(bool)
+        off += nb
+        t, rp, tp, tk = z["params"][c]
+        yield dict(row=int(r), family=str(z["family"][r]), logits=x, history=hist, T=float(t), rp=float(rp), top_p=float(tp),
+                   top_k=int(tk), kept=kept)
+    assert off == hb.size == kb.size
+
+
+def tie_canonical(pre: np.ndarray, kept: np.ndarray) -> np.ndarray:
+    """``kept`` with the kept count of every value moved to that value's highest indices (-0 == +0, NaN one value).  The
+    reference's top-p sort is not stable, so which tokens of a tie run it keeps is unspecified; how many is not (equal values
+    add equal mass).  The device and the oracle keep the highest indices: this is the reference's set in that reading."""
+    v = np.where(np.isnan(pre), np.inf, pre).astype(np.float64) + 0.0
+    order = np.lexsort((-np.arange(v.size), -v))                 # value descending, index descending
+    sv = v[order]
+    new = np.r_[True, sv[1:] != sv[:-1]]
+    gid = np.cumsum(new) - 1
+    starts = np.nonzero(new)[0]
+    count = np.bincount(gid, weights=kept[order].astype(np.float64)).astype(np.int64)
+    out = np.zeros_like(kept)
+    out[order] = (np.arange(v.size) - starts[gid]) < count[gid]
+    return out

@@ -1,6 +1,7 @@
 """The device sampler (csrc/pc_sample.hip, pc_sample_advance) and the sampled decode loop (model/llama_hip.py SampleLoop) on the
-GPU: the processed row against the REFERENCE's chain (tests/golden/sampling_chain.npz), the draw against its numpy restatement
-(tests/sample_ref.py), the distribution of draws, the loop-state contract, and generate() end to end."""
+GPU: the processed row against the REFERENCE's chain (tests/golden/sampling_chain.npz, and sampling_chain_vocab.npz at real
+vocabulary sizes), the draw against its numpy restatement (tests/sample_ref.py), every draw of a long replayed stream, the
+loop-state contract, and generate() end to end."""
 import os
 from collections import Counter
 
@@ -327,3 +328,281 @@ def test_greedy_with_a_repetition_penalty_equals_stepping():
     assert len(dev_ids) == 100
     assert [o.new_text for o in dev] == [o.new_text for o in step]
     assert max(Counter(dev_ids).values()) < 100
+
+
+# ---- the processed row at real vocabulary sizes (tests/golden/sampling_chain_vocab.npz) ------------------------------------
+TOL_P = 1e-5        # top-p: the device's fp32 mass against the reference's fp32 cumsum; bounds |D| by mass, not by count
+
+
+def _product_block_draw(x, history, T, rp, tp, tk, seed=1, step=0, offset=0):
+    """The device's processed row and token for one GenerationParameters, through the product's block (sample_params_block)."""
+    from promptcache_amd.generation_engine import GenerationParameters
+    from promptcache_amd.model.llama_hip import sample_params_block
+    st = _State(len(x), list(history), step)
+    st.params.copy_(torch.frombuffer(bytearray(sample_params_block(
+        GenerationParameters(temperature=T, repetition_penalty=rp, top_p=tp, top_k=tk), seed)), dtype=torch.uint8))
+    proc = torch.empty(len(x), dtype=torch.float32, device="cuda")
+    st.advance(_row(x, offset), proc)
+    torch.cuda.synchronize()
+    return int(st.ids[0]), proc.cpu().numpy()
+
+
+def _reference_mass_error(pre):
+    """|1 - sum p| of the reference's own fp32 softmax (torch's, over the ascending sorted row, as TopPLogitsWarper takes it):
+    how far its cut can sit from the exact one.  Up to ~6e-5 at 128 256 tokens (a two-level row), far above TOL_P."""
+    fin = pre[np.isfinite(pre)]
+    if fin.size == 0:
+        return 0.0
+    return abs(1.0 - torch.from_numpy(np.sort(pre)).softmax(-1).double().sum().item())
+
+
+def _check_kept(tag, x, history, T, rp, tp, tk, ref_kept, got, pre=None):
+    """The acceptance rule against a reference kept set: (a) tokens kept by both are bit-equal to the chain without top-p and
+    the top token is kept; (b) top-p off: the sets are equal; (c) top-p on: every differing token lies within TOL_P + err of
+    the cut by the float64 mass ranked above it, and the differing mass is at most TOL_P + err, or D is that one token; err:
+    the reference's own softmax error (_reference_mass_error).  -> (|D|, mass of D, err)."""
+    if pre is None:
+        pre = so.process_logits(x, history, T, rp, 1.0, -1)
+    dev = got != -np.inf
+    both = dev & ref_kept
+    assert np.array_equal(got[both].view(np.uint32), pre[both].view(np.uint32)), (tag, "kept values differ")
+    fin = np.isfinite(pre)
+    if ref_kept.any():
+        top = np.nonzero(pre == pre.max())[0][-1]                   # rank order's first: the highest index of the maxima
+        assert dev[top], (tag, "the top token was dropped", int(top))
+    D = np.nonzero(dev != ref_kept)[0]
+    mass = 0.0
+    topp = 1e-8 <= tp < 1.0 and not np.isposinf(pre).any()
+    if D.size and fin.any():
+        p = np.zeros(pre.size)
+        e = np.exp(pre[fin].astype(np.float64) - pre[fin].max())
+        p[fin] = e / e.sum()
+        mass = float(p[D].sum())
+    if not topp:
+        assert D.size == 0, (tag, "top-p off: temperature, penalty and top-k are exact", D[:10])
+    elif D.size:
+        err = _reference_mass_error(pre)
+        above = _mass_above(np.where(fin, pre, -np.inf).astype(np.float32))
+        far = D[np.abs(above[D] - tp) > TOL_P + err]
+        assert far.size == 0, (tag, "differs away from the cut", err, far[:10], above[far[:10]])
+        # one token of a coarse row (p_i > TOL_P) can flip where the exact cut falls within rounding of its edge
+        assert mass <= TOL_P + err or D.size == 1, (tag, mass, err)
+        return D.size, mass, err
+    return D.size, mass, 0.0
+
+
+def test_processed_row_matches_the_vocab_fixture():
+    """Every case of the reference's chain at V = 1001 .. 128 256, through the product's parameter block.  The reference's tie
+    order at the cut is unspecified (its CPU sort is not stable): its kept count per value, at the highest indices
+    (sample_ref.tie_canonical), is the set compared.  Rows holding NaN: the device reads NaN as -inf, the reference has no
+    defined result there (its softmax is NaN), so those rows are compared with the oracle on the NaN-free row."""
+    n, nd, worst = 0, 0, 0.0
+    for c in sr.vocab_cases():
+        x, h, T, rp, tp, tk = c["logits"], c["history"], c["T"], c["rp"], c["top_p"], c["top_k"]
+        _, got = _product_block_draw(x, h, T, rp, tp, tk, seed=n, step=n, offset=n % 4)
+        if np.isnan(x).any():
+            xc = np.where(np.isnan(x), np.float32(-np.inf), x)
+            pre = so.process_logits(xc, h, T, rp, 1.0, -1)
+            ref = so.process_logits(xc, h, T, rp, tp, tk) != -np.inf
+        else:
+            pre = so.process_logits(x, h, T, rp, 1.0, -1)
+            ref = sr.tie_canonical(pre, c["kept"])
+        tag = (c["row"], c["family"], x.size, T, rp, tp, tk)
+        d, mass, err = _check_kept(tag, x, h, T, rp, tp, tk, ref, got, pre)
+        print(f"[vocab] row {c['row']:2d} {c['family']:13s} V={x.size:6d} T={T:g} rp={rp:g} top_p={tp:.8g} top_k={tk}: "
+              f"|D|={d} mass={mass:.3g} ref_err={err:.2g}")
+        n += 1
+        nd += d
+        worst = max(worst, mass)
+    assert n >= 200
+    print(f"[vocab] {n} cases: differing tokens {nd}, largest differing mass {worst:.3g}")
+
+
+def test_exact_top_p_and_top_k_constructions():
+    """Rows where every mass is exact in fp32 and float64 (all equal: p = 1/V): the cut is an exact decision and the kept set
+    must equal the reference's (the oracle's) token for token.  The tie run spans all three index bytes at V = 131 072."""
+    for V, js in ((1024, (1, 3, 255, 256, 257, 1000, 1023)), (131072, (1, 2, 255, 256, 257, 65535, 65536, 65537, 131071))):
+        for interleave in (False, True):
+            x = np.full(V, 0.75, dtype=np.float32)
+            if interleave:
+                x[1::2] = -np.inf
+            live = V // 2 if interleave else V
+            for j in js:
+                if j >= live:
+                    continue
+                tp = j / live
+                _, got = _product_block_draw(x, [], 1.0, 1.0, tp, -1)
+                want = so.process_logits(x, [], 1.0, 1.0, tp, -1) != -np.inf
+                assert want.sum() == j
+                kept = np.nonzero(got != -np.inf)[0]
+                assert np.array_equal(got != -np.inf, want), (V, interleave, j, kept.size, kept[:4], kept[-4:])
+    # two-level rows at top-k boundaries: k inside, at and past the high level's run
+    rng = np.random.default_rng(21)
+    for V in (1024, 32000, 131072):
+        x = np.zeros(V, dtype=np.float32)
+        hi = rng.choice(V, 300, replace=False)
+        x[hi] = 1.0
+        for k in (1, 299, 300, 301, V - 1, V):
+            _, got = _product_block_draw(x, [], 0.7, 1.0, 1.0, k)
+            want = so.process_logits(x, [], 0.7, 1.0, 1.0, k) != -np.inf
+            assert np.array_equal(got != -np.inf, want), (V, k, int((got != -np.inf).sum()), int(want.sum()))
+
+
+@pytest.mark.parametrize("V", [1, 2, 3, 4, 5, 7, 33])
+def test_tiny_vocabularies_against_the_oracle(V):
+    """Fewer tokens than one group of 4 per thread, at row offsets 0..3 floats (16-, 4-byte aligned rows)."""
+    rng = np.random.default_rng(V)
+    for j in range(24):
+        T, rp, tp, tk = PARAM_SETS[j % len(PARAM_SETS)]
+        x = (rng.standard_normal(V) * 2).astype(np.float32)
+        if j % 3 == 1:
+            x = np.round(x)
+        h = rng.integers(0, V, 3).tolist()
+        seed, step = int(rng.integers(0, 2 ** 62)), j
+        tok, got = _product_block_draw(x, h, T, rp, tp, tk, seed, step, offset=j % 4)
+        ref = so.process_logits(x, h, T, rp, tp, tk) != -np.inf
+        _check_kept((V, j), x, h, T, rp, tp, tk, ref, got)
+        want, margin, _ = sr.draw(x, h, T, rp, tp, tk, seed, step)
+        if margin > MARGIN:
+            assert tok == want, (V, j, tok, want)
+
+
+def test_vocabulary_at_the_abi_limit():
+    """V = 2^24 - 1: the tie run at the cut spans ids above 2^16, so the top byte of the index select is not zero."""
+    V = (1 << 24) - 1
+    rng = np.random.default_rng(24)
+    x = (np.round(rng.standard_normal(V) * 2) / 2).astype(np.float32)          # multiples of 1/2: runs of millions
+    h = [31, 32, V - 1, 1 << 23, (1 << 24) - 33]
+    for off, (T, rp, tp, tk) in enumerate(((1.0, 1.3, 0.3, -1), (0.7, 1.0, 1.0, 3_000_000))):
+        tok, got = _product_block_draw(x, h, T, rp, tp, tk, seed=5, step=off, offset=off)
+        ref = so.process_logits(x, h, T, rp, tp, tk) != -np.inf
+        d, mass, err = _check_kept(("2^24-1", T, rp, tp, tk), x, h, T, rp, tp, tk, ref, got)
+        print(f"[abi-limit] T={T} rp={rp} top_p={tp} top_k={tk}: kept {int(ref.sum())}, |D|={d} mass={mass:.3g} ref_err={err:.2g}")
+        assert np.isfinite(got[tok])
+
+
+def _draws_of_steps(proc, seed, steps, greedy=False):
+    """sample_ref's race at every step of ``steps`` for one fixed processed row: (token, margin) per step (vectorised)."""
+    V = proc.size
+    keep = np.isfinite(proc)
+    x = proc.astype(np.float64)
+    G = (V + 3) // 4
+    toks, margins = [], []
+    for s0 in range(0, len(steps), 256):
+        st = np.asarray(steps[s0:s0 + 256], dtype=np.uint64)
+        ctr = np.zeros((st.size * G, 4), dtype=np.uint64)
+        ctr[:, 0] = np.tile(np.arange(G, dtype=np.uint64), st.size)
+        ctr[:, 1] = np.repeat(st & np.uint64(0xFFFFFFFF), G)
+        w = sr.philox4x32_10(ctr, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)).reshape(st.size, -1)[:, :V]
+        u = ((w >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+        s = np.where(keep, x - np.log(-np.log(u)), -np.inf)
+        top2 = np.sort(s, axis=1)[:, -2:]
+        toks.append(np.argmax(s, axis=1))
+        margins.append(top2[:, 1] - top2[:, 0])
+    return np.concatenate(toks), np.concatenate(margins)
+
+
+@pytest.mark.parametrize("V,n,start", [(512, 20000, (1 << 31) - 2 - 10000), (32000, 1500, (1 << 31) - 2)])
+def test_every_draw_of_a_replayed_stream(V, n, start):
+    """A graph holding one pc_sample_advance node, replayed n times from a counter that crosses the int32 sign bit: every ring
+    entry is sample_ref's draw at the same (seed, step) wherever the race is not a near tie."""
+    rng = np.random.default_rng(V)
+    x = (rng.standard_normal(V) * 2.0).astype(np.float32)
+    T, tp, tk, seed = 0.9, 0.95, 200, 0x0fed_cba9_8765_4321
+    st = _State(V, (), 0, ring=n)
+    st.set_params(T, 1.0, tp, tk, seed)
+    row = _row(x)
+    st.advance(row)
+    st.ctr.fill_(start - (1 << 32) if start >= (1 << 31) else start)
+    st.ring.fill_(-1)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        st.advance(row)
+    for _ in range(n):
+        g.replay()
+    torch.cuda.synchronize()
+    assert (int(st.ctr[0]) & 0xFFFFFFFF) == (start + n) & 0xFFFFFFFF
+    steps = [(start + k) & 0xFFFFFFFF for k in range(n)]
+    ring = st.ring.cpu().numpy()
+    got = np.array([ring[s % n] for s in steps])
+    proc = so.process_logits(x, [], T, 1.0, tp, tk)
+    want, margin = _draws_of_steps(proc, seed, steps)
+    sure = margin > MARGIN
+    bad = np.nonzero(sure & (got != want))[0]
+    assert bad.size == 0, (V, bad[:5], got[bad[:5]], want[bad[:5]], [steps[i] for i in bad[:5]])
+    assert sure.sum() >= 0.97 * n, int(sure.sum())
+    print(f"[stream] V={V}: {int(sure.sum())} of {n} draws checked, steps {steps[0]:#x} .. {steps[-1]:#x}")
+
+
+def test_rows_with_positive_infinity():
+    """+inf entries: the reference's top-p keeps everything (its softmax is NaN), top-k counts them; the kept set equals the
+    oracle's and the token is a +inf token -- the lowest such index in greedy mode and, the race being inf + g = inf, in
+    sampled mode too."""
+    rng = np.random.default_rng(8)
+    for V in (1000, 32000):
+        x = (rng.standard_normal(V) * 2).astype(np.float32)
+        inf_at = np.sort(rng.choice(V, 3, replace=False))
+        x[inf_at] = np.inf
+        for T, rp, tp, tk in ((1.0, 1.0, 0.9, -1), (0.7, 1.1, 0.95, 40), (0.0, 1.2, 1.0, -1), (1.0, 1.0, 0.5, 2), (2.0, 1.0, 1.0, 1)):
+            h = [int(inf_at[0]), 5]
+            tok, got = _product_block_draw(x, h, T, rp, tp, tk, seed=3, step=4)
+            ref = so.process_logits(x, h, T, rp, tp, tk) != -np.inf
+            assert np.array_equal(got != -np.inf, ref), (V, T, rp, tp, tk)
+            assert tok == inf_at[0], (V, T, tok, inf_at)
+
+
+def test_generate_at_a_real_vocabulary():
+    """generate() through SampleLoop at V = 32 000 with a repetition penalty and a prompt history above id 2047: the
+    teacher-forced helper picks every emitted token; and T = 9.9999999e-6 (greedy in the reference, 1e-5f in fp32) with a
+    penalty gives the stepped greedy tokens."""
+    import dataclasses
+
+    from promptcache_amd import CacheEngine, GenerationEngine, GenerationParameters, Prompt, synth
+    from promptcache_amd.model import Llama2
+    from promptcache_amd.model.config import SHAPES
+    from promptcache_amd.model.weights import make_weights_np
+    shape = dataclasses.replace(SHAPES["mid_gqa"], vocab_size=32000)
+    lm = Llama2(name="x", shape=shape, weights=make_weights_np(shape, 4, 3.0), device="cuda:0")
+    sp, pp = synth.flat_docs("gv", 12, (40, 33), 9, seed=6)
+    fmt = lm.get_formatter()
+    eng = CacheEngine(200, lm)
+    eng.add_schema(fmt(sp))
+    prompt = Prompt(pp, [fmt])
+    T, rp, tp, tk, N = 0.8, 1.3, 0.95, -1, 60
+    params = GenerationParameters(temperature=T, repetition_penalty=rp, top_p=tp, top_k=tk, max_new_tokens=N, stop_token_ids=[],
+                                  stop_str=[])
+    outs, emitted, ids, pos = _generate(lm, eng, prompt, params, 9)
+    assert len(emitted) == N and max(ids) > 2047, max(ids)
+    torch.manual_seed(9)
+    seed = int(torch.randint(0, 2 ** 62, (1,)))
+    ids2, pos2, _, cache = eng.process(prompt)
+    out = lm(input_ids=torch.tensor([ids2], device="cuda"), position_ids=torch.tensor([pos2], device="cuda"), past_key_values=cache,
+             use_cache=True)
+    past, p0, history, close = out.past_key_values, max(pos2) + 1, list(ids2), 0
+    logits = out.logits[0, -1].float().cpu().numpy()
+    for k in range(N):
+        want, margin, _ = sr.draw(logits, history, T, rp, tp, tk, seed, k)
+        if margin > MARGIN:
+            assert emitted[k] == want, (k, emitted[k], want, margin)
+        else:
+            close += 1
+        history.append(emitted[k])
+        if k == N - 1:
+            break
+        o = lm(input_ids=torch.tensor([[emitted[k]]], device="cuda"), position_ids=torch.tensor([[p0 + 1 + k]], device="cuda"),
+               past_key_values=past, use_cache=True)
+        past, logits = o.past_key_values, o.logits[0, -1].float().cpu().numpy()
+    del past, out
+    assert close <= 3, close
+
+    g = GenerationParameters(temperature=9.9999999e-6, repetition_penalty=1.2, max_new_tokens=40, stop_token_ids=[], stop_str=[])
+    assert g.greedy
+    dev, dev_ids, _, _ = _generate(lm, eng, prompt, g, 0)
+    try:
+        GenerationEngine.device_sample_loop = False
+        step, _, _, _ = _generate(lm, eng, prompt, g, 0, engine=GenerationEngine)
+    finally:
+        GenerationEngine.device_sample_loop = True
+    assert len(dev_ids) == 40
+    assert [o.new_text for o in dev] == [o.new_text for o in step]

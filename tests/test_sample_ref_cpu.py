@@ -94,3 +94,100 @@ def test_sample_advance_argument_errors_need_no_gpu():
     lib = _native.load()
     assert lib.pc_sample_advance(None, 10, None, None, None, None, None, None, None, 4, None, None) == -1001
     assert b"pc_sample_advance" in lib.pc_last_error_string()
+
+
+# ---- the parameter block the sampled loop writes (LlamaHIP._sample_state_fill) ---------------------------------------------
+def _filled_block(T, rp, tp, tk, seed=12345, V=1000):
+    """The pc_sample_params bytes _sample_state_fill writes for one GenerationParameters (host tensors: no GPU)."""
+    import types
+
+    import torch
+    from promptcache_amd import _native
+    from promptcache_amd.generation_engine import GenerationParameters
+    from promptcache_amd.model.llama_hip import LlamaHIP
+    st = dict(params=torch.zeros(ctypes.sizeof(_native.SampleParams), dtype=torch.uint8),
+              hist=torch.zeros((V + 31) // 32, dtype=torch.int32))
+    params = GenerationParameters(temperature=T, repetition_penalty=rp, top_p=tp, top_k=tk)
+    LlamaHIP._sample_state_fill(types.SimpleNamespace(config=types.SimpleNamespace(vocab_size=V)), st, params, seed, [3, 999])
+    return params, bytes(st["params"].numpy())
+
+
+def _kernel_reads(blk, V):
+    """What pc_sample_advance decides from a block, restated in fp32 (csrc/pc_sample.hip: greedy, tdiv, pen, want_p, want_k)."""
+    T, rp, tp = (np.float32(v) for v in np.frombuffer(blk[:12], dtype=np.float32))
+    tk = int.from_bytes(blk[12:16], "little", signed=True)
+    return dict(greedy=bool(T < np.float32(1e-5) or tp < np.float32(1e-8)), tdiv=bool(T >= np.float32(1e-5) and T != 1),
+                pen=bool(rp > 1), want_p=bool(tp >= np.float32(1e-8) and tp < 1), k=min(tk, V) if tk > 0 else V,
+                T=T, rp=rp, tp=tp, seed=int.from_bytes(blk[16:24], "little"))
+
+
+def _reference_decides(params, V):
+    return dict(greedy=params.greedy, tdiv=params.temperature >= 1e-5 and params.temperature != 1.0,
+                pen=params.repetition_penalty > 1.0, want_p=1e-8 <= params.top_p < 1.0,
+                k=min(params.top_k, V) if params.top_k > 0 else V)
+
+
+EDGE_T = (0.0, 9.9999999e-6, np.nextafter(1e-5, 0.0), 1e-5, np.nextafter(1e-5, 1.0), 0.7, np.nextafter(1.0, 0.0), 1.0,
+          np.nextafter(1.0, 2.0), 1.0 + 1e-9, 100.0, float("nan"))
+EDGE_P = (0.0, np.nextafter(1e-8, 0.0), 1e-8, np.nextafter(1e-8, 1.0), 0.5, 0.95, np.nextafter(1.0, 0.0), 1.0, 1.5)
+EDGE_RP = (0.5, np.nextafter(1.0, 0.0), 1.0, np.nextafter(1.0, 2.0), 1.0 + 1e-9, 1.1, 2.0)
+EDGE_K = (-(2 ** 40), -1, 0, 1, 40, 999, 1000, 1001, 2 ** 31 - 1, 2 ** 31, 2 ** 32 + 5, 2 ** 40)
+
+
+def test_sampled_loop_block_decides_as_the_reference_in_double():
+    """Every threshold the kernel re-tests in fp32 decides as the reference decided in double, at the neighbours of T = 1e-5,
+    T = 1, top_p = 1e-8, top_p = 1 and rp = 1.  The one accepted exception: a top_p in [1e-8, 1) that rounds to 1.0f (top-p
+    off on the device, mass below 1e-7)."""
+    V, n = 1000, 0
+    for T in EDGE_T:
+        for tp in EDGE_P:
+            for rp in EDGE_RP[::2] if tp not in (0.5, 1.0) else EDGE_RP:
+                params, blk = _filled_block(T, rp, tp, 40)
+                got, want = _kernel_reads(blk, V), _reference_decides(params, V)
+                if want["want_p"] and not got["want_p"]:
+                    assert np.float32(tp) == 1.0, (T, rp, tp)
+                    got["want_p"] = True
+                if want["greedy"]:
+                    got.pop("tdiv"), want.pop("tdiv")                 # greedy: no division either way (kernel T = 0)
+                    assert got["T"] == 0.0
+                # a warper whose fp32 factor is 1.0 is the identity: skipping it decides the same
+                for key, v in (("tdiv", T), ("pen", rp)):
+                    if want.get(key) and not got[key] and np.float32(v) == 1.0:
+                        want[key] = False
+                for key in ("greedy", "tdiv", "pen", "want_p", "k"):
+                    assert got.get(key) == want.get(key), (key, T, rp, tp, got, want)
+                if want.get("tdiv"):
+                    assert got["T"] == np.float32(T)
+                if want["pen"]:
+                    assert got["rp"] == np.float32(rp)
+                assert got["seed"] == 12345
+                n += 1
+    assert n > 300
+
+
+def test_sampled_loop_block_canonical_values():
+    # case 1: T just below 1e-5 is greedy in the reference; the fp32 1e-5f would sample
+    assert np.float32(9.9999999e-6) == np.float32(1e-5)
+    params, blk = _filled_block(9.9999999e-6, 1.2, 1.0, -1)
+    assert params.greedy and _kernel_reads(blk, 1000)["greedy"]
+    assert np.frombuffer(blk[:12], dtype=np.float32).tolist() == [0.0, np.float32(1.2), 1.0]
+    # case 2: a top_k past int32 keeps everything (the reference: min(top_k, V)), not top_k mod 2^32
+    for tk in (2 ** 31, 2 ** 32 + 5, 2 ** 40):
+        _, blk = _filled_block(0.7, 1.0, 1.0, tk)
+        assert int.from_bytes(blk[12:16], "little", signed=True) == 2 ** 31 - 1
+    for tk in (0, -5, -(2 ** 40)):
+        _, blk = _filled_block(0.7, 1.0, 1.0, tk)
+        assert int.from_bytes(blk[12:16], "little", signed=True) == -1
+    # no warper in the reference -> the neutral value on the device
+    _, blk = _filled_block(1.0 + 1e-9, 0.9, 1.5, 40)
+    assert np.frombuffer(blk[:12], dtype=np.float32).tolist() == [1.0, 1.0, 1.0]
+    _, blk = _filled_block(0.7, 1.0, np.nextafter(1e-8, 0.0), 40)       # greedy by top_p: T = 0, no top-p warper
+    assert np.frombuffer(blk[:12], dtype=np.float32).tolist() == [0.0, 1.0, 1.0]
+    # the raw block stays raw (kernel tests feed edge values through it)
+    raw = _native_raw(9.9999999e-6, 1.2, 1.0, 2 ** 31 - 1)
+    assert np.frombuffer(raw[:4], dtype=np.float32)[0] == np.float32(1e-5)
+
+
+def _native_raw(T, rp, tp, tk):
+    from promptcache_amd import _native
+    return _native.sample_params_bytes(T, rp, tp, tk, 0)

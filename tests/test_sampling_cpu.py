@@ -40,3 +40,34 @@ def test_greedy_rule_and_defaults():
     assert not GenerationParameters().greedy
     assert len(GenerationParameters().get_logits_processor()) == 0          # all defaults: empty chain (:32-42)
     assert len(GenerationParameters(temperature=0.7, repetition_penalty=1.1, top_p=0.9, top_k=3).get_logits_processor()) == 4
+
+
+def test_processor_chain_and_oracle_reproduce_the_vocab_fixture():
+    """The reference's chain at V = 1001 .. 128 256 (tests/golden/sampling_chain_vocab.npz): ties, signed zeros, -inf / NaN /
+    +inf rows, top-k at V - 1 .. V + 1 and inside tie runs, top-p down to 1e-8.  The product's chain keeps exactly the
+    reference's set; the oracle keeps the same count of every value, at the highest indices of a tie run (tie_canonical), with
+    values bit-equal to the chain's."""
+    from tests import sample_ref as sr
+    n, rows, sizes, ties = 0, set(), set(), 0
+    for c in sr.vocab_cases():
+        x, hist, t, rp, tp, tk = c["logits"], c["history"], c["T"], c["rp"], c["top_p"], c["top_k"]
+        params = GenerationParameters(temperature=t, repetition_penalty=rp, top_p=tp, top_k=tk)
+        h = torch.as_tensor(hist[None]) if rp > 1.0 else None
+        got = params.get_logits_processor()(h, torch.from_numpy(x[None].copy()))[0].numpy()
+        orc = so.process_logits(x, hist, t, rp, tp, tk)
+        pre = so.process_logits(x, hist, t, rp, 1.0, -1)
+        want = c["kept"]
+        assert np.array_equal(got != -np.inf, want), (c["row"], c["family"], x.size, t, rp, tp, tk)
+        canon = sr.tie_canonical(pre, want)
+        ties += int(np.sum(canon != want))
+        assert np.array_equal(orc != -np.inf, canon), (c["row"], c["family"], x.size, t, rp, tp, tk,
+                                                       int(want.sum()), int((orc != -np.inf).sum()))
+        k = want & canon
+        assert np.array_equal(got[k].view(np.uint32), orc[k].view(np.uint32)), (c["row"], t, rp)
+        assert np.array_equal(pre[k].view(np.uint32), orc[k].view(np.uint32))
+        n += 1
+        rows.add(c["row"])
+        sizes.add(x.size)
+    assert n >= 200 and len(rows) >= 30 and sizes == {1001, 32000, 32016, 50432, 65024, 65537, 128256}
+    assert ties > 0            # the fixture does hold boundaries inside tie runs that torch's sort orders otherwise
+    print(f"[sampling_chain_vocab] {n} cases over {len(rows)} rows; tokens the tie reading moves: {ties}")
