@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--max-ctx", type=int, default=5000)
     ap.add_argument("--max-tokens", type=int, default=800)
     ap.add_argument("--max-new-tokens", type=int, default=32)
+    ap.add_argument("--module-kv", choices=("fp16", "int8"), default=None,
+                    help="module KV store format (default: PC_MODULE_KV, else fp16); int8 = 0.516 of the fp16 bytes")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
@@ -42,7 +44,7 @@ def main():
         cls, shape = ADAPTERS[a.model]
         lm = cls(shape, random_init=True)
     preproc = [lm.get_formatter()]
-    cache_engine = CacheEngine(a.max_ctx, lm)
+    cache_engine = CacheEngine(a.max_ctx, lm, module_kv=a.module_kv)
     gen_engine = GenerationEngine(lm)
     if a.schema:
         cache_engine.add_schema(read_file(a.schema, preproc), max_tokens=a.max_tokens)
@@ -50,6 +52,8 @@ def main():
     else:
         schema_text, prompt_text = synth.flat_docs("code-generation-game", 30, (306, 76, 800, 800, 800, 800, 800), 12)
         cache_engine.add_schema(lm.get_formatter()(schema_text), max_tokens=a.max_tokens)
+    print(f"module KV ({cache_engine.module_kv}, {cache_engine.module_memory} tier): " +
+          ", ".join(f"{nm} {b / 2 ** 20:.1f} MiB" for nm, b in cache_engine.module_bytes().items()))
     params = GenerationParameters(temperature=1.0, repetition_penalty=1.0, top_p=0.95, top_k=-1,
                                   max_new_tokens=a.max_new_tokens, stop_token_ids=lm.stop_token_ids, stop_str=lm.stop_str)
     prompt = Prompt(prompt_text, preproc)

@@ -90,6 +90,31 @@ int pc_kv_slice_store(const void* src, int32_t src_cap, const int32_t* seg_src_o
                       int32_t head_dim, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Int8 module KV store (opt-in, CacheEngine(module_kv="int8")): a segment's module KV kept as ONE contiguous byte image
+ *
+ *     int8  codes [P][n][D]      P = n_layers * 2 * n_kv_heads planes in pc_kv_gather's plane order, n rows, D = head_dim
+ *     fp32  scale [P][n]         starts at byte P*n*D (a multiple of 16)
+ *
+ *   P*n*(D+4) bytes against the fp16 store's P*n*2D (0.516 at D = 128).  One (plane, row) of D fp16 values x is quantised with
+ *   every step in fp32, round to nearest even:  s = max|x|;  inv = 127.0f / s (0 when s == 0);  code = (int8) rintf(x * inv);
+ *   scale = s / 127.0f;  and dequantised as  fp16_rn((float) code * scale).  A row holding a NaN or an infinity stores
+ *   scale = NaN and codes 0, so it dequantises to NaN.  head_dim must be 32, 64 or 128; pointers 16-byte aligned.
+ *
+ * pc_kv_quant_q8 -- what SchemaCache._process keeps of a stored slice, cache_engine.py:283-296 (there: fp16 tensors moved to
+ *   the CPU): the fp16 segment store [n_planes][n_rows][head_dim] (pc_kv_slice_store's seg_dst) -> its image.
+ *
+ * pc_kv_gather_q8 -- replaces PromptCache.update's copy loop, cache_engine.py:135-151, as pc_kv_gather does, for segments held
+ *   as images: ONE launch over a segment table that writes dequantised fp16 rows into the staged buffer
+ *   [n_layers][2][n_kv_heads][max_ctx][head_dim].
+ *   segs      HOST array of nseg descriptors: src = the segment's image (HBM or pinned host memory, mixed freely),
+ *             dst_row = its first staged row, len = its rows.  Rows that no segment covers are not written.
+ *   A segment with dst_row + len > max_ctx -> PC_ERR_BOUNDS (nothing is launched).
+ * ------------------------------------------------------------------------------------------- */
+int pc_kv_quant_q8(const void* src, int32_t n_rows, int32_t n_planes, int32_t head_dim, void* dst_image, void* stream);
+int pc_kv_gather_q8(const pc_kv_seg* segs, int32_t nseg, void* dst, int32_t n_layers, int32_t n_kv_heads, int32_t head_dim,
+                    int32_t max_ctx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * pc_rope_table -- replaces LlamaRotaryEmbedding's cos/sin table + the `cos[position_ids]` gather,
  *   llama2.py:129-147 and :204-207.  Only the rows the supplied position ids select are produced
  *   (fp32, angle = float(pos) * inv_freq, as the reference builds them before its dtype cast).

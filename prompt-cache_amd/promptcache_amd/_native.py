@@ -123,6 +123,8 @@ SIGNATURES = {
     "pc_last_error_string": (C.c_char_p, []),
     "pc_kv_gather": (C.c_int, [C.POINTER(_vp), _pi32, _pi32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pc_kv_slice_store": (C.c_int, [_vp, _i32, _pi32, _pi32, C.POINTER(_vp), _i32, _i32, _i32, _i32, _vp]),
+    "pc_kv_quant_q8": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "pc_kv_gather_q8": (C.c_int, [C.POINTER(KvSeg), _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pc_kv_row_table": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "pc_attn_gather_ok": (C.c_int, [C.POINTER(AttnArgs)]),
     "pc_rope_table": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
@@ -253,6 +255,32 @@ def kv_slice_store(src, src_cap: int, seg_src_off: Sequence[int], seg_lens: Sequ
     rc = load().pc_kv_slice_store(src.data_ptr(), src_cap, a_off, a_len, a_ptr, n, n_layers, n_kv_heads, head_dim,
                                   current_stream() if stream is None else stream)
     check(rc, "pc_kv_slice_store")
+
+
+def kv_q8_image_bytes(n_rows: int, n_planes: int, head_dim: int) -> int:
+    """Bytes of an int8 segment image: codes ``[P][n][D]`` followed by fp32 scales ``[P][n]``."""
+    return n_planes * n_rows * (head_dim + 4)
+
+
+def kv_quant_q8(src, n_rows: int, n_planes: int, head_dim: int, dst_image, stream: Optional[int] = None) -> None:
+    """fp16 segment store ``[n_planes][n_rows][head_dim]`` -> its int8 image (``dst_image``: uint8, kv_q8_image_bytes long)."""
+    if dst_image.numel() * dst_image.element_size() < kv_q8_image_bytes(n_rows, n_planes, head_dim):
+        raise ValueError("kv_quant_q8: the image tensor is too small")
+    rc = load().pc_kv_quant_q8(src.data_ptr(), n_rows, n_planes, head_dim, dst_image.data_ptr(),
+                               current_stream() if stream is None else stream)
+    check(rc, "pc_kv_quant_q8")
+
+
+def kv_gather_q8(seg_ptrs: Sequence[int], seg_lens: Sequence[int], seg_dst_rows: Sequence[int], dst,
+                 n_layers: int, n_kv_heads: int, head_dim: int, max_ctx: int, stream: Optional[int] = None) -> None:
+    """Int8 counterpart of ``kv_gather``: ``seg_ptrs`` are segment images (HBM or pinned host memory)."""
+    n = len(seg_ptrs)
+    if dst.numel() < n_layers * 2 * n_kv_heads * max_ctx * head_dim or dst.element_size() != 2:
+        raise ValueError("kv_gather_q8: dst is not an fp16 buffer of [n_layers][2][n_kv_heads][max_ctx][head_dim]")
+    segs = (KvSeg * n)(*[KvSeg(p, r, ln) for p, ln, r in zip(seg_ptrs, seg_lens, seg_dst_rows)])
+    rc = load().pc_kv_gather_q8(segs, n, dst.data_ptr(), n_layers, n_kv_heads, head_dim, max_ctx,
+                                current_stream() if stream is None else stream)
+    check(rc, "pc_kv_gather_q8")
 
 
 def kv_row_table(segs_dev, nseg_dev, max_seg: int, total_rows_dev, dst, n_kv_heads: int, head_dim: int, max_ctx: int, rows,

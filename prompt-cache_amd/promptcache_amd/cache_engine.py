@@ -47,12 +47,20 @@ class TokenSequenceCache:
     defaults turned around for a 288 GB part: the store is born in HBM and stays there; a library that does not fit
     moves segments to PINNED host memory (``offload``), from where ``pc_kv_gather`` reads them in place over PCIe --
     pinned allocations are mapped into the device address space, so a staged prompt may mix HBM and host segments
-    in the one gather launch.  ``upload`` brings a segment back, ``free`` drops the HBM copy."""
+    in the one gather launch.  ``upload`` brings a segment back, ``free`` drops the HBM copy.
 
-    def __init__(self, seq: TokenSequence, store: torch.Tensor):
+    Int8 format (``CacheEngine(module_kv="int8")``; ``quantize_``): the store, in either tier, is ONE uint8 image -- int8 codes
+    ``[P][len][D]`` followed by fp32 per-row scales ``[P][len]``, ``P = L * 2 * Hkv`` (csrc/pc_kv_q8.hip) -- of
+    ``(D + 4) / 2D`` of the fp16 bytes.  ``store`` / ``offload`` / ``upload`` / ``free`` move the image as they move the fp16
+    tensor; ``cache`` / ``host_cache`` / ``device_cache`` still return per-layer fp16 ``(K, V)`` of shape ``[Hkv, len, D]``, but as
+    dequantised COPIES (writes to them do not reach the store)."""
+
+    def __init__(self, seq: TokenSequence, store: torch.Tensor, q8_shape: Optional[Tuple[int, int, int]] = None):
+        """``q8_shape = (L, Hkv, D)``: ``store`` is an int8 image of that geometry (default: the fp16 store itself)."""
         self.token_sequence = seq
         self._n = len(seq)
         self.usage_counter = 0
+        self.q8_shape = q8_shape
         self.device_store: Optional[torch.Tensor] = store if store.is_cuda else None
         self.host_store: Optional[torch.Tensor] = None if store.is_cuda else self._pinned(store)
 
@@ -88,8 +96,42 @@ class TokenSequenceCache:
         if self.device_store is not None:
             self.offload()
 
-    @staticmethod
-    def _views(store: torch.Tensor) -> KVCache:
+    @property
+    def format(self) -> str:
+        return "fp16" if self.q8_shape is None else "int8"
+
+    def nbytes(self) -> int:
+        """Bytes of the store a gather reads (one tier; a segment resident in both tiers holds them twice)."""
+        st = self.store
+        return st.numel() * st.element_size()
+
+    @torch.inference_mode()
+    def quantize_(self) -> None:
+        """Replace the fp16 store by its int8 image (``pc_kv_quant_q8``), in the tier(s) it lives in; the fp16 tensor is dropped."""
+        if self.q8_shape is not None:
+            return
+        st = self.store
+        L, _, Hkv, n, D = st.shape
+        src = st if st.is_cuda else st.to("cuda")
+        image = torch.empty(_native.kv_q8_image_bytes(n, L * 2 * Hkv, D), dtype=torch.uint8, device=src.device)
+        _native.kv_quant_q8(src.contiguous(), n, L * 2 * Hkv, D, image)
+        self.q8_shape = (L, Hkv, D)
+        had_host = self.host_store is not None
+        self.host_store = self._pinned(image) if had_host else None
+        self.device_store = image if st.is_cuda else None
+
+    def _views(self, store: torch.Tensor) -> KVCache:
+        if self.q8_shape is not None:
+            # the image expanded into a scratch [L][2][Hkv][len][D] by the gather kernel (it reads pinned host images in place);
+            # a host image gives host tensors, as the reference's host_cache does
+            L, Hkv, D = self.q8_shape
+            dev = store.device if store.is_cuda else torch.device("cuda")
+            out = torch.empty((L, 2, Hkv, self._n, D), dtype=torch.float16, device=dev)
+            with torch.cuda.device(dev):
+                _native.kv_gather_q8([store.data_ptr()], [self._n], [0], out, L, Hkv, D, self._n)
+                if not store.is_cuda:
+                    torch.cuda.current_stream().synchronize()      # the kernel was reading `store` (the caller may drop it)
+            store = out if store.is_cuda else out.cpu()
         return [(store[i, 0], store[i, 1]) for i in range(store.shape[0])]
 
     @property
@@ -102,7 +144,8 @@ class TokenSequenceCache:
 
     @property
     def cache(self) -> KVCache:
-        """Per-layer ``(K, V)`` views ``[Hkv, len, D]``, device copy first (the reference's ``cache``, :75-80)."""
+        """Per-layer ``(K, V)`` views ``[Hkv, len, D]``, device copy first (the reference's ``cache``, :75-80); dequantised
+        copies when the segment is held as an int8 image."""
         return self._views(self.store)
 
     def __len__(self):
@@ -155,6 +198,10 @@ class PromptCache:
             else:
                 break
         offset = sum(len(m) for m in ordered[:keep])
+        q8 = bool(ordered) and ordered[0].q8_shape is not None
+        if any((m.q8_shape is not None) != q8 for m in ordered):
+            raise ValueError("the prompt's modules mix fp16 and int8 stores: one staging takes one format "
+                             "(TokenSequenceCache.quantize_ the remaining fp16 segments, or re-encode the schema)")
         ptrs, lens, offs = [], [], []
         for m in ordered[keep:]:
             ptrs.append(m.store.data_ptr())
@@ -164,7 +211,7 @@ class PromptCache:
         if offset > self.max_ctx_length:
             raise ValueError(f"prompt modules need {offset} staged tokens but max_ctx_length is {self.max_ctx_length}")
         a = self.arena
-        if self.defer_gather and ptrs and all(m.device_store is not None for m in ordered[keep:]):
+        if self.defer_gather and not q8 and ptrs and all(m.device_store is not None for m in ordered[keep:]):
             # module KV in HBM: the first forward stages (segments in the host tier keep the explicit gather: the copy kernel
             # streams them over PCIe, the attention would fetch them in latency-bound pieces)
             a.pending = StagingPlan(list(zip(ptrs, lens, offs)), offset, [m.device_store for m in ordered[keep:]])
@@ -173,7 +220,9 @@ class PromptCache:
             if self.record_events:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            _native.kv_gather(ptrs, lens, offs, a.buf, a.L, a.Hkv, a.D, a.cap)
+            # int8 images are expanded on their way in (pc_kv_gather_q8) and never take the deferred plan above: the attention
+            # that stages while it reads (StagingPlan / gather_rows) reads fp16 rows in place
+            (_native.kv_gather_q8 if q8 else _native.kv_gather)(ptrs, lens, offs, a.buf, a.L, a.Hkv, a.D, a.cap)
             if self.record_events:
                 ev[1].record()
                 self.last_gather_events = ev
@@ -193,10 +242,11 @@ class PromptCache:
 
 class SchemaCache:
     def __init__(self, schema: Schema, lm: LanguageModel, batch_size: int = 1, target_device=None, no_cache=False,
-                 module_memory: str = "device"):
+                 module_memory: str = "device", module_kv: str = "fp16"):
         self.schema = schema
         self.lm = lm
         self.module_memory = module_memory
+        self.module_kv = module_kv
         self.cache_l1: Dict[int, TokenSequenceCache] = {}
         self.cache_l2: Dict[Tuple[int, int], Tuple[TokenSequenceCache, TokenSequenceCache]] = {}
         self.target_device = lm.device if target_device is None else target_device
@@ -213,6 +263,14 @@ class SchemaCache:
         others only receive); neither: this schema's passes are levelled over all ranks.
         ``async_exchange``: leave the module-KV exchange in flight (``wait_exchange`` before the segments are read)."""
         self._process(batch_size, owner_rank, async_exchange, shards)
+        if self.module_kv == "int8":
+            # every segment's fp16 store exists on its final rank once the exchange has landed: convert it there and drop
+            # the fp16 slab (transient peak: this schema's fp16 slab plus its images, 1.52 x the slab)
+            self.wait_exchange()
+            self._exchange = None               # (it kept the slab alive for reexchange_seconds)
+            for c in self.cache_l1.values():
+                c.quantize_()
+            gc.collect()
         if self.module_memory == "host":
             self.wait_exchange()
             for c in self.cache_l1.values():
@@ -680,14 +738,22 @@ class SchemaCache:
 
 
 class CacheEngine:
-    def __init__(self, max_ctx_length: int, lm: LanguageModel, target_device=None, module_memory: Optional[str] = None):
+    def __init__(self, max_ctx_length: int, lm: LanguageModel, target_device=None, module_memory: Optional[str] = None,
+                 module_kv: Optional[str] = None):
         """``module_memory``: where add_schema leaves the module KV -- ``"device"`` (HBM, default) or ``"host"`` (pinned
         host memory, gathered over PCIe: the reference's default placement, :283-296; for libraries beyond HBM).
-        Individual segments move with ``TokenSequenceCache.upload`` / ``free``.  Env default: PC_MODULE_MEMORY."""
+        Individual segments move with ``TokenSequenceCache.upload`` / ``free``.  Env default: PC_MODULE_MEMORY.
+        ``module_kv``: the format add_schema leaves the module KV in, in either tier -- ``"fp16"`` (default) or ``"int8"``
+        (codes + one fp32 scale per row and plane, 0.516 of the fp16 bytes at head_dim 128; every prompt's segments are
+        dequantised into the fp16 staged arena by one ``pc_kv_gather_q8`` launch, so the model sees fp16 K/V of the
+        format's accuracy).  Env default: PC_MODULE_KV."""
         _native.load()
         self.module_memory = module_memory or os.environ.get("PC_MODULE_MEMORY", "device")
         if self.module_memory not in ("device", "host"):
             raise ValueError(f"module_memory must be 'device' or 'host', not {self.module_memory!r}")
+        self.module_kv = module_kv or os.environ.get("PC_MODULE_KV", "fp16")
+        if self.module_kv not in ("fp16", "int8"):
+            raise ValueError(f"module_kv must be 'fp16' or 'int8', not {self.module_kv!r}")
         self.lm = lm
         self.schemas: Dict[str, SchemaCache] = {}
         self.target_device = lm.device if target_device is None else target_device
@@ -705,7 +771,8 @@ class CacheEngine:
         if schema.name in self.schemas:
             raise ValueError(f"There is already a schema named {schema.name} in the cache")
         self.schemas[schema.name] = SchemaCache(schema, self.lm, batch_size, target_device=self.target_device,
-                                                no_cache=no_cache, module_memory=self.module_memory)
+                                                no_cache=no_cache, module_memory=self.module_memory,
+                                                module_kv=self.module_kv)
 
     def add_schemas(self, schemas: Sequence[Union[str, Schema]], batch_size: int = 1, max_tokens: Optional[int] = None) -> None:
         """Encode a whole module LIBRARY (the reference loops ``add_schema`` over its schema files, eval.py:172-181).
@@ -723,7 +790,7 @@ class CacheEngine:
                 raise ValueError(f"There is already a schema named {nm} in the cache")
         rank, world = parallel.rank_world()
         caches = [SchemaCache(sc, self.lm, batch_size, target_device=self.target_device, no_cache=True,
-                              module_memory=self.module_memory) for sc in parsed]
+                              module_memory=self.module_memory, module_kv=self.module_kv) for sc in parsed]
         order, shards = self.library_schedule(caches, world)
         for k in order:
             caches[k].encode(batch_size, shards=shards[k] if world > 1 else None, async_exchange=world > 1)
@@ -745,6 +812,15 @@ class CacheEngine:
         members = [sum(1 for sh in shards[k] if sh) for k in range(len(caches))]
         order = sorted(range(len(caches)), key=lambda k: (members[k] > 1, k))
         return order, shards
+
+    def module_bytes(self, name: Optional[str] = None) -> Union[int, Dict[str, int]]:
+        """Bytes the module KV of schema ``name`` holds in the tier its gathers read (fp16 stores or int8 images); without a
+        name, ``{schema: bytes}`` for every loaded schema."""
+        if name is not None:
+            if name not in self.schemas:
+                raise ValueError(f"There is no such schema named {name} in the cache")
+            return sum(c.nbytes() for c in self.schemas[name].cache_l1.values())
+        return {nm: self.module_bytes(nm) for nm in self.schemas}
 
     def get_schema(self, name: str) -> Optional[Schema]:
         return self.schemas[name].schema if name in self.schemas else None
