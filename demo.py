@@ -14,6 +14,8 @@ import argparse
 import os
 import sys
 
+import torch
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "prompt-cache_amd"))
 
@@ -34,6 +36,8 @@ def main():
     ap.add_argument("--max-new-tokens", type=int, default=32)
     ap.add_argument("--module-kv", choices=("fp16", "int8"), default=None,
                     help="module KV store format (default: PC_MODULE_KV, else fp16); int8 = 0.516 of the fp16 bytes")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="also decode N copies of the prompt with different questions together (generate_batch; N <= 16)")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
@@ -44,7 +48,7 @@ def main():
         cls, shape = ADAPTERS[a.model]
         lm = cls(shape, random_init=True)
     preproc = [lm.get_formatter()]
-    cache_engine = CacheEngine(a.max_ctx, lm, module_kv=a.module_kv)
+    cache_engine = CacheEngine(a.max_ctx, lm, module_kv=a.module_kv, slots=max(1, a.batch))
     gen_engine = GenerationEngine(lm)
     if a.schema:
         cache_engine.add_schema(read_file(a.schema, preproc), max_tokens=a.max_tokens)
@@ -69,6 +73,28 @@ def main():
               f"gather {cache_time:7.3f} ms | first forward {last.elapsed_time:8.3f} ms | "
               f"TTFT {cache_time + last.elapsed_time:8.3f} ms | {a.max_new_tokens} tokens in {last.response_time:8.2f} ms")
     print("Assistant:", (last.new_text[:120] + " ...") if last else "")
+    if a.batch:
+        import time
+        # the same module selection with N different questions, one staged buffer (slot) each, decoded in one device loop
+        cut = prompt_text.rfind("</prompt>")
+        reqs = []
+        for k in range(a.batch):
+            pk = Prompt(prompt_text[:cut] + f"<user>{synth.words(4 + k % 5, 4000 + k)}</user>" + prompt_text[cut:], preproc)
+            ids, pos, _, cache = cache_engine.process(pk, return_full_position_ids=lm.use_full_position_ids, slot=k)
+            reqs.append((ids, pos, cache))
+        batched, why = gen_engine.batch_plan(len(reqs), params)
+        for _pass in ("warm", "timed"):              # (the first pass captures the batched step)
+            lasts = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2):
+                lasts[k] = out
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+        n_tok = a.batch * a.max_new_tokens               # (fewer where a stop token or stop string ended a sequence early)
+        print(f"batch of {a.batch} ({'one device loop' if batched else 'one after another: ' + why}): up to {n_tok} tokens in "
+              f"{dt * 1e3:8.2f} ms, prefills included: {n_tok / dt:8.1f} tokens/s aggregate")
+        print("Assistant[0]:", lasts[0].new_text[:120] + " ...")
 
 
 if __name__ == "__main__":

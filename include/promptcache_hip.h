@@ -605,6 +605,45 @@ int pc_sample_advance(const float* logits, int32_t vocab, const pc_sample_params
                       int32_t* pos, int32_t* past_len, int32_t* ring, int32_t* counter, int32_t ring_cap, float* processed_out,
                       void* stream);
 
+/* ---- batched decode over slots (csrc/pc_slots.hip, csrc/pc_sample.hip) ---------------------------------------------------------
+ * A slot is one running sequence in a batch-1 KV arena of its own ([n_layers][2][Hkv][cap][head_dim] fp16, pc_kv_gather's dst).
+ * Its state is one element of each of these DEVICE arrays over S <= 16 slots, so that one captured step serves every replay:
+ *   kv_base uint64[S]  address of the slot's arena          cap  int32[S]  rows per plane of that arena
+ *   len     int32[S]   rows the arena holds                 pos  int32[S]  position id of the token the slot feeds next
+ *   ids     int64[S]   that token                           live int32[S]  0: the slot is idle -- every launch below skips it
+ * A live slot with len >= cap is skipped like an idle one (nothing is written, nothing is read) and pc_sample_advance_slots
+ * switches it off.  No slot's result depends on any other slot's data, on its index or on how many slots are live.
+ *
+ * pc_rope_append_slots: for every live slot b, RoPE with row b of cs [S][head_dim/2][2] (pc_rope_table) on the query and key
+ * of row b of qkv (fp32 [S][ld], q | k | v head-major; in_layout 1: every head in the rotary-pair tile order of pc_gemm's
+ * q|k|v weight image, i.e. a plain projection over that image), q to the split-precision pair q_hi / q_lo [S][q_token_stride],
+ * K / V (rounded to fp16 once) to row len[b] of layer `layer` of the slot's arena -- the bits pc_rope_append_ex writes.
+ *
+ * pc_attn_decode_slots: for every live slot b and head, softmax(q k^T * softmax_scale) v over keys [0, len[b]] of the slot's
+ * arena (the row pc_rope_append_slots just wrote included), fp32 softmax, K / V as stored.  The key axis is cut into `nsplit`
+ * (1..32, chosen by the host from an upper bound of the lengths) equal shares of len[b] + 1 read from the device; partials go
+ * to `workspace` (pc_attn_decode_slots_workspace_bytes) and are merged by a second launch into the fragment planes
+ * out_frag_hi / out_frag_lo [1][H*head_dim/32][64][8] (row = slot) that pc_gemm's o_proj consumes.  head_dim 64 or 128; the
+ * H / Hkv query heads of a kv head share its K / V reads.  Rows of idle slots are left as they are.
+ *
+ * pc_sample_advance_slots: pc_sample_advance per live slot, all slots concurrently: the chain of the ONE parameter block and
+ * the draw on logits[b * logits_row_stride ..] with the random stream seeds[b], the step counters[b] and the history bitmap
+ * history_bits[b * ceil(vocab/32) ..]; then ids[b] = token, pos[b] += 1, len[b] += 1, ring[b * ring_cap + counters[b] %
+ * ring_cap] = token, counters[b] += 1, budget[b] -= 1, and live[b] = 0 when the token is one of stop_ids[0..8) (unused
+ * entries: -1), budget[b] reached 0 or len[b] + 1 >= cap[b].  processed_out (optional, [S][vocab]) as in pc_sample_advance. */
+int pc_rope_append_slots(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
+                         const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live,
+                         int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, void* stream);
+int64_t pc_attn_decode_slots_workspace_bytes(int32_t S, int32_t H, int32_t D, int32_t nsplit);
+int pc_attn_decode_slots(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base, const int32_t* cap,
+                         const int32_t* len, const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                         float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
+                         void* out_frag_lo, void* stream);
+int pc_sample_advance_slots(const float* logits, int64_t logits_row_stride, int32_t vocab, const pc_sample_params* params_dev,
+                            const uint64_t* seeds, uint32_t* history_bits, int64_t* ids, int32_t* pos, int32_t* len,
+                            const int32_t* cap, int32_t* live, int32_t* budget, const int32_t* stop_ids, int32_t* ring,
+                            int32_t* counters, int32_t ring_cap, int32_t S, float* processed_out, void* stream);
+
 /* Diagnostics used by the GPU test-suite: dumps the MFMA C/D lane map and the LDS transpose-read
  * map the attention kernel relies on (probe_kernel in csrc/pc_misc.hip). */
 /* dev hook (tools/gemm_trace.py): weight-streaming launches issued by this thread stamp per-wave wall-clock times

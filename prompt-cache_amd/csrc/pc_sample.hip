@@ -184,10 +184,10 @@ __device__ __forceinline__ void reduce_columns(const float* __restrict__ c, floa
     out[b] = s;
 }
 
-__global__ __launch_bounds__(kThreads) void sample_advance_kernel(const float* __restrict__ logits, int V,
-                                                                  const pc_sample_params* __restrict__ prm, uint32_t* hist,
-                                                                  int64_t* ids, int32_t* pos, int32_t* past, int32_t* ring,
-                                                                  int32_t* ctr, int ring_cap, float* processed_out) {
+// The chain and the draw for ONE row, by one workgroup of kThreads threads: the token, valid in thread 0 (every thread of the
+// workgroup must call it).  `hist` is read only.
+__device__ __forceinline__ int sample_row(const float* __restrict__ logits, int V, const pc_sample_params* __restrict__ prm,
+                                          const uint32_t* hist, uint64_t seed, uint32_t step, float* processed_out) {
     __shared__ uint32_t cp[256 * kCols];  // top-p select: counts per digit and column
     __shared__ float mp[256 * kCols];     //               exp(x - max) mass per digit and column
     __shared__ uint32_t ck[256 * kCols];  // top-k select, then the boundary-tie index select: counts per digit and column
@@ -201,8 +201,6 @@ __global__ __launch_bounds__(kThreads) void sample_advance_kernel(const float* _
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = tid & (kCols - 1);
     const float T = prm->temperature, rp = prm->repetition_penalty, top_p = prm->top_p;
     const int top_k = prm->top_k;
-    const uint64_t seed = prm->seed;
-    const uint32_t step = (uint32_t)ctr[0];
     const bool greedy = T < 1e-5f || top_p < 1e-8f;
     const Row row{logits, hist, V, ((uintptr_t)logits & 15) == 0, T >= 1e-5f && T != 1.0f, rp > 1.0f, T, rp};
     const int G = (V + 3) >> 2;
@@ -392,12 +390,57 @@ __global__ __launch_bounds__(kThreads) void sample_advance_kernel(const float* _
         for (int w = 1; w < kWaves; ++w)
             if (s_red[w] > best || (s_red[w] == best && s_idx[w] < bi)) { best = s_red[w]; bi = s_idx[w]; }
         if (bi == 0x7fffffff) bi = 0;                 // all -inf / NaN: token 0, as greedy_advance_kernel
+    }
+    return bi;
+}
+
+__global__ __launch_bounds__(kThreads) void sample_advance_kernel(const float* __restrict__ logits, int V,
+                                                                  const pc_sample_params* __restrict__ prm, uint32_t* hist,
+                                                                  int64_t* ids, int32_t* pos, int32_t* past, int32_t* ring,
+                                                                  int32_t* ctr, int ring_cap, float* processed_out) {
+    const uint32_t step = (uint32_t)ctr[0];
+    const int bi = sample_row(logits, V, prm, hist, prm->seed, step, processed_out);
+    if (threadIdx.x == 0) {
         ids[0] = bi;
         pos[0] += 1;
         past[0] += 1;
         ring[step % (uint32_t)ring_cap] = bi;
         ctr[0] = (int32_t)(step + 1u);
         hist[bi >> 5] |= 1u << (bi & 31);
+    }
+}
+
+// One workgroup per slot (pc_sample_advance_slots): the row, random stream, history bitmap and state words of slot b.  An idle
+// slot changes nothing; a live slot whose arena is full (len >= cap: nothing was appended for it) only goes idle.
+__global__ __launch_bounds__(kThreads) void sample_advance_slots_kernel(
+    const float* __restrict__ logits, int64_t ldl, int V, const pc_sample_params* __restrict__ prm,
+    const uint64_t* __restrict__ seeds, uint32_t* hist, int64_t* ids, int32_t* pos, int32_t* len, const int32_t* __restrict__ cap,
+    int32_t* live, int32_t* budget, const int32_t* __restrict__ stop_ids, int32_t* ring, int32_t* ctr, int ring_cap,
+    float* processed_out) {
+    const int b = blockIdx.x;
+    if (live[b] == 0) return;                          // (uniform over the workgroup)
+    if (len[b] < 0 || len[b] >= cap[b]) {
+        if (threadIdx.x == 0) live[b] = 0;
+        return;
+    }
+    const int hw = (V + 31) >> 5;
+    uint32_t* hb = hist + (int64_t)b * hw;
+    const uint32_t step = (uint32_t)ctr[b];
+    const int bi = sample_row(logits + (int64_t)b * ldl, V, prm, hb, seeds[b], step, processed_out ? processed_out + (int64_t)b * V : nullptr);
+    if (threadIdx.x == 0) {
+        ids[b] = bi;
+        pos[b] += 1;
+        const int n = len[b] + 1;
+        len[b] = n;
+        ring[(int64_t)b * ring_cap + step % (uint32_t)ring_cap] = bi;
+        ctr[b] = (int32_t)(step + 1u);
+        hb[bi >> 5] |= 1u << (bi & 31);
+        const int left = budget[b] - 1;
+        budget[b] = left;
+        bool stop = left <= 0 || n + 1 >= cap[b];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) stop |= stop_ids[j] == bi;
+        if (stop) live[b] = 0;
     }
 }
 
@@ -414,4 +457,22 @@ PC_EXPORT int pc_sample_advance(const float* logits, int32_t vocab, const pc_sam
     hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, logits, vocab, params_dev,
                        history_bits, ids, pos, past_len, ring, counter, ring_cap, processed_out);
     return pc_check_launch("sample_advance_kernel");
+}
+
+PC_EXPORT int pc_sample_advance_slots(const float* logits, int64_t logits_row_stride, int32_t vocab,
+                                      const pc_sample_params* params_dev, const uint64_t* seeds, uint32_t* history_bits,
+                                      int64_t* ids, int32_t* pos, int32_t* len, const int32_t* cap, int32_t* live, int32_t* budget,
+                                      const int32_t* stop_ids, int32_t* ring, int32_t* counters, int32_t ring_cap, int32_t S,
+                                      float* processed_out, void* stream) {
+    PC_REQUIRE(logits && params_dev && seeds && history_bits && ids && pos && len && cap && live && budget && stop_ids && ring &&
+                   counters && ring_cap > 0, PC_ERR_ARG, "pc_sample_advance_slots: null pointer or bad sizes");
+    PC_REQUIRE(S >= 1 && S <= 16, PC_ERR_ARG, "pc_sample_advance_slots: 1 <= S <= 16");
+    PC_REQUIRE(vocab > 0 && vocab < (1 << 24) && logits_row_stride >= vocab, PC_ERR_ARG,
+               "pc_sample_advance_slots: vocab must be in [1, 2^24) and the row stride at least vocab");
+    PC_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)params_dev & 7) == 0 && ((uintptr_t)seeds & 7) == 0, PC_ERR_ARG,
+               "pc_sample_advance_slots: logits must be 4-byte, params and seeds 8-byte aligned");
+    hipLaunchKernelGGL(sample_advance_slots_kernel, dim3(S), dim3(kThreads), 0, (hipStream_t)stream, logits, logits_row_stride,
+                       vocab, params_dev, seeds, history_bits, ids, pos, len, cap, live, budget, stop_ids, ring, counters, ring_cap,
+                       processed_out);
+    return pc_check_launch("sample_advance_slots_kernel");
 }

@@ -1,0 +1,332 @@
+// Batched decode over SLOTS: several running sequences, each in a batch-1 KV arena of its own, advanced by one captured step.
+//
+// Replaces, for S sequences at once, what the B = 1 decode step does per layer between the q|k|v projection and o_proj:
+//           apply_rotary_pos_emb + torch.cat([past, new])        promptcache/model/llama2.py:202-210, :361-364
+//           softmax(q k^T / sqrt(d)) v over the sequence's keys  promptcache/model/llama2.py:366-400
+//
+// A slot is described by device words -- arena base address, capacity, length, live flag -- so that one captured graph serves
+// every step: the advance launch (pc_sample_advance_slots, pc_sample.hip) rewrites them.  Nothing a slot computes depends on
+// another slot: every workgroup works for exactly one slot, the split of the key axis is a function of that slot's own length
+// and of the host-fixed split count, and every reduction runs in a fixed order.  A slot's output is therefore bit-identical
+// whatever the other slots hold and whichever index it sits at.
+//
+// The attention is the memory-bound one-row case: K / V rows go from global memory straight to registers (16 bytes per lane,
+// D / 8 lanes per key), scores and P.V are fp32 VALU work on q = hi + lo (at least the precision of the split-precision MFMA
+// form of attn_small_kernel), and the query heads of one kv head share every K / V load (GQ heads per workgroup pass).
+#include <hip/hip_fp16.h>
+#include <math.h>
+
+#include "pc_common.h"
+
+namespace {
+
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+constexpr float kNegBig = -1.0e30f;   // finite "-inf" of the running maxima
+constexpr int kThreads = 256;
+constexpr int kMaxSplit = 32;
+
+// position of element (row m, feature k) in a fragment-major plane with KS k-steps (pc_gemm.hip)
+__device__ __forceinline__ int64_t frag_off(int m, int k, int KS) {
+    return ((((int64_t)(m >> 4) * KS + (k >> 5)) * 64) + ((k & 31) >> 3) * 16 + (m & 15)) * 8 + (k & 7);
+}
+
+__device__ __forceinline__ void load8(const float* p, float (&x)[8]) {
+    const f4 a = *(const f4*)p, b = *(const f4*)(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x[e] = a[e]; x[e + 4] = b[e]; }
+}
+
+// ---- RoPE + append, one workgroup per slot -----------------------------------------------------------------------------
+// The work items and the arithmetic are rope_append_kernel<float>'s (pc_rope.hip): the rows written are bit-identical to what
+// pc_rope_append_ex writes for the same projection row and position.  layout 1: the projection row is in the row order of the
+// q|k|v fragment image (_native.qkv_rope_row_perm: inside a head, 16-column tile j = features 8j.. then D/2 + 8j..).
+__global__ __launch_bounds__(kThreads) void rope_append_slots_kernel(
+    const float* __restrict__ qkv, int64_t ld, int layout, _Float16* __restrict__ q_hi, _Float16* __restrict__ q_lo, int64_t q_ts,
+    const float2* __restrict__ cs, const uint64_t* __restrict__ kv_base, const int32_t* __restrict__ cap,
+    const int32_t* __restrict__ len, const int32_t* __restrict__ live, int layer, int H, int Hkv, int D) {
+    const int b = blockIdx.x;
+    if (live[b] == 0) return;
+    const int past = len[b], c = cap[b];
+    if (past < 0 || past >= c) return;
+    const int half = D >> 1;
+    const int cph = D >> 4;  // 8-pair chunks per head
+    const int nq = H * cph, nk = Hkv * cph, nv = Hkv * (D >> 3);
+    const float2* csr = cs + (int64_t)b * half;
+    const float* row = qkv + (int64_t)b * ld;
+    _Float16* k_plane = (_Float16*)(uintptr_t)kv_base[b] + (int64_t)(layer * 2) * Hkv * c * D;
+    _Float16* v_plane = k_plane + (int64_t)Hkv * c * D;
+    for (int it = threadIdx.x; it < nq + nk + nv; it += blockDim.x) {
+        if (it < nq + nk) {
+            const bool is_q = it < nq;
+            const int j = is_q ? it : it - nq;
+            const int h = j / cph, ch = j - h * cph;
+            const float* src = row + (int64_t)(is_q ? h : H + h) * D;
+            _Float16* dst = is_q ? q_hi + (int64_t)b * q_ts + (int64_t)h * D : k_plane + ((int64_t)h * c + past) * D;
+            float lo[8], hi[8];
+            load8(src + (layout ? ch * 16 : ch * 8), lo);
+            load8(src + (layout ? ch * 16 + 8 : half + ch * 8), hi);
+            h8 olo, ohi, rlo, rhi;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float2 w = csr[ch * 8 + e];
+                const float a = lo[e] * w.x - hi[e] * w.y, b2 = hi[e] * w.x + lo[e] * w.y;
+                _Float16 t0, t1, t2, t3;
+                pc_split(a, t0, t1);
+                pc_split(b2, t2, t3);
+                olo[e] = t0; rlo[e] = t1;
+                ohi[e] = t2; rhi[e] = t3;
+            }
+            *(h8*)(dst + ch * 8) = olo;
+            *(h8*)(dst + half + ch * 8) = ohi;
+            if (is_q) {
+                _Float16* dl = q_lo + (int64_t)b * q_ts + (int64_t)h * D;
+                *(h8*)(dl + ch * 8) = rlo;
+                *(h8*)(dl + half + ch * 8) = rhi;
+            }
+        } else {
+            const int j = it - nq - nk;
+            const int cpv = D >> 3;
+            const int h = j / cpv, ch = j - h * cpv;
+            float x[8];
+            load8(row + (int64_t)(H + Hkv + h) * D + (layout ? (ch < cph ? ch * 16 : (ch - cph) * 16 + 8) : ch * 8), x);
+            h8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (_Float16)x[e];
+            *(h8*)(v_plane + ((int64_t)h * c + past) * D + ch * 8) = o;
+        }
+    }
+}
+
+// ---- one-row attention per slot, split over the key axis ---------------------------------------------------------------
+// grid (split, kv head x pass, slot).  A pass takes GQ query heads of the kv head's group; D / 8 lanes hold one key row, a wave
+// 64 / (D / 8) keys at a time, four keys per lane group in flight.  Every lane group keeps an online softmax of its own
+// keys; the groups of a wave are merged through lane exchanges, the four waves through LDS, always in the same order.
+template <int D, int GQ>
+__global__ __launch_bounds__(kThreads) void attn_decode_slots_kernel(
+    const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo, int64_t q_ts, const uint64_t* __restrict__ kv_base,
+    const int32_t* __restrict__ cap, const int32_t* __restrict__ len, const int32_t* __restrict__ live, int layer, int H, int Hkv,
+    float scale_log2, int nsplit, float* __restrict__ part_o, float* __restrict__ part_ml) {
+    constexpr int LPK = D / 8;          // lanes per key row
+    constexpr int GPW = 64 / LPK;       // key groups per wave
+    constexpr int NG = 4 * GPW;         // key groups per workgroup
+    constexpr int U = 4;                // keys in flight per group
+    __shared__ float sm[4][GQ][D + 2];
+
+    const int split = blockIdx.x, b = blockIdx.z;
+    if (live[b] == 0) return;
+    const int past = len[b], c = cap[b];
+    if (past < 0 || past >= c) return;
+    const int G = H / Hkv, passes = (G + GQ - 1) / GQ;
+    const int kvh = blockIdx.y / passes, g0 = (blockIdx.y - kvh * passes) * GQ;
+    const int n = past + 1;                       // keys of this slot: its staged and decoded rows and the row just appended
+    const int chunk = (n + nsplit - 1) / nsplit;
+    const int k0 = split * chunk, k1 = min(n, k0 + chunk);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sub = lane % LPK, grp = wave * GPW + lane / LPK;
+    const _Float16* kp = (const _Float16*)(uintptr_t)kv_base[b] + ((int64_t)(layer * 2) * Hkv + kvh) * c * D + sub * 8;
+    const _Float16* vp = kp + (int64_t)Hkv * c * D;
+
+    float q[GQ][8], acc[GQ][8], m[GQ], l[GQ];
+#pragma unroll
+    for (int g = 0; g < GQ; ++g) {
+        const int h = kvh * G + min(g0 + g, G - 1);
+        const int64_t qo = (int64_t)b * q_ts + (int64_t)h * D + sub * 8;
+        const h8 a = *(const h8*)(q_hi + qo), r = *(const h8*)(q_lo + qo);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            q[g][e] = ((float)a[e] + (float)r[e]) * scale_log2;
+            acc[g][e] = 0.0f;
+        }
+        m[g] = kNegBig;
+        l[g] = 0.0f;
+    }
+
+    for (int base = k0; base < k1; base += NG * U) {
+        h8 kk[U], vv[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int key = base + u * NG + grp;
+            ok[u] = key < k1;
+            const int64_t off = (int64_t)min(key, k1 - 1) * D;
+            kk[u] = *(const h8*)(kp + off);
+            vv[u] = *(const h8*)(vp + off);
+        }
+#pragma unroll
+        for (int g = 0; g < GQ; ++g) {
+            float s[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float d = 0.0f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d = fmaf(q[g][e], (float)kk[u][e], d);
+#pragma unroll
+                for (int o = 1; o < LPK; o <<= 1) d += __shfl_xor(d, o);
+                s[u] = ok[u] ? d : -INFINITY;
+            }
+            float mn = m[g];
+#pragma unroll
+            for (int u = 0; u < U; ++u) mn = fmaxf(mn, s[u]);
+            const float sc = exp2f(m[g] - mn);
+            float ll = l[g] * sc;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[g][e] *= sc;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float p = exp2f(s[u] - mn);
+                ll += p;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[g][e] = fmaf(p, (float)vv[u][e], acc[g][e]);
+            }
+            m[g] = mn;
+            l[g] = ll;
+        }
+    }
+
+    // the key groups of a wave -> its first group
+#pragma unroll
+    for (int g = 0; g < GQ; ++g) {
+#pragma unroll
+        for (int o = LPK; o < 64; o <<= 1) {
+            const float mo = __shfl_xor(m[g], o), lo = __shfl_xor(l[g], o);
+            const float mn = fmaxf(m[g], mo);
+            const float wa = exp2f(m[g] - mn), wb = exp2f(mo - mn);
+            l[g] = l[g] * wa + lo * wb;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[g][e] = acc[g][e] * wa + __shfl_xor(acc[g][e], o) * wb;
+            m[g] = mn;
+        }
+        if (lane < LPK) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sm[wave][g][sub * 8 + e] = acc[g][e];
+            if (sub == 0) { sm[wave][g][D] = m[g]; sm[wave][g][D + 1] = l[g]; }
+        }
+    }
+    __syncthreads();
+    // the four waves -> this split's partial (unnormalised sum, maximum, denominator)
+    for (int i = tid; i < GQ * D; i += kThreads) {
+        const int g = i / D, d = i - g * D;
+        if (g0 + g >= G) break;
+        float ms = sm[0][g][D];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) ms = fmaxf(ms, sm[w][g][D]);
+        float num = 0.0f, den = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float wt = exp2f(sm[w][g][D] - ms);
+            den = fmaf(wt, sm[w][g][D + 1], den);
+            num = fmaf(wt, sm[w][g][d], num);
+        }
+        const int64_t slot = ((int64_t)b * H + kvh * G + g0 + g) * nsplit + split;
+        part_o[slot * D + d] = num;
+        if (d == 0) { part_ml[slot * 2] = ms; part_ml[slot * 2 + 1] = den; }
+    }
+}
+
+// merge of the split partials, one workgroup per (head, slot), one thread per head dim, splits in index order
+template <int D>
+__global__ __launch_bounds__(D) void attn_merge_slots_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                             const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
+                                                             const int32_t* __restrict__ live, int H, int nsplit,
+                                                             _Float16* __restrict__ of_hi, _Float16* __restrict__ of_lo) {
+    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    if (live[b] == 0) return;
+    const int past = len[b];
+    if (past < 0 || past >= cap[b]) return;
+    const int64_t base = ((int64_t)b * H + h) * nsplit;
+    float ms = kNegBig;
+    for (int s = 0; s < nsplit; ++s) ms = fmaxf(ms, part_ml[(base + s) * 2]);
+    float num = 0.0f, den = 0.0f;
+    for (int s = 0; s < nsplit; ++s) {
+        const float wt = exp2f(part_ml[(base + s) * 2] - ms);
+        den = fmaf(wt, part_ml[(base + s) * 2 + 1], den);
+        num = fmaf(wt, part_o[(base + s) * D + d], num);
+    }
+    _Float16 hi, lo;
+    pc_split(num / den, hi, lo);
+    const int64_t off = frag_off(b, h * D + d, H * D / 32);
+    of_hi[off] = hi;
+    of_lo[off] = lo;
+}
+
+template <int D, int GQ>
+void launch_decode(int S, int H, int Hkv, int nsplit, hipStream_t st, const _Float16* q_hi, const _Float16* q_lo, int64_t q_ts,
+                   const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live, int layer,
+                   float scale_log2, float* part_o, float* part_ml) {
+    const int passes = (H / Hkv + GQ - 1) / GQ;
+    hipLaunchKernelGGL((attn_decode_slots_kernel<D, GQ>), dim3(nsplit, Hkv * passes, S), dim3(kThreads), 0, st, q_hi, q_lo, q_ts,
+                       kv_base, cap, len, live, layer, H, Hkv, scale_log2, nsplit, part_o, part_ml);
+}
+
+template <int D>
+void launch_decode_d(int S, int H, int Hkv, int nsplit, hipStream_t st, const _Float16* q_hi, const _Float16* q_lo, int64_t q_ts,
+                     const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live, int layer,
+                     float scale_log2, float* part_o, float* part_ml) {
+    const int G = H / Hkv;
+    if (G == 1)
+        launch_decode<D, 1>(S, H, Hkv, nsplit, st, q_hi, q_lo, q_ts, kv_base, cap, len, live, layer, scale_log2, part_o, part_ml);
+    else if (G <= 4)
+        launch_decode<D, 4>(S, H, Hkv, nsplit, st, q_hi, q_lo, q_ts, kv_base, cap, len, live, layer, scale_log2, part_o, part_ml);
+    else
+        launch_decode<D, 8>(S, H, Hkv, nsplit, st, q_hi, q_lo, q_ts, kv_base, cap, len, live, layer, scale_log2, part_o, part_ml);
+}
+
+bool slot_shape_ok(int S, int H, int Hkv, int D) {
+    return S >= 1 && S <= 16 && H > 0 && Hkv > 0 && H % Hkv == 0 && (D == 64 || D == 128);
+}
+
+}  // namespace
+
+PC_EXPORT int pc_rope_append_slots(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
+                                   const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len,
+                                   const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, void* stream) {
+    PC_REQUIRE(S >= 1 && S <= 16 && layer >= 0 && H > 0 && Hkv > 0, PC_ERR_ARG, "pc_rope_append_slots: bad sizes (1 <= S <= 16)");
+    PC_REQUIRE(D > 0 && D % 16 == 0, PC_ERR_ARG, "pc_rope_append_slots: head_dim must be a multiple of 16");
+    PC_REQUIRE(qkv && q_hi && q_lo && cs && kv_base && cap && len && live, PC_ERR_ARG, "pc_rope_append_slots: null pointer");
+    PC_REQUIRE(in_layout == 0 || in_layout == 1, PC_ERR_ARG, "pc_rope_append_slots: in_layout is 0 (natural) or 1 (rotary-pair tiles)");
+    PC_REQUIRE(ld >= (int64_t)(H + 2 * Hkv) * D && ld % 4 == 0 && q_token_stride % 8 == 0 && ((uintptr_t)qkv & 15) == 0 &&
+                   ((uintptr_t)q_hi & 15) == 0 && ((uintptr_t)q_lo & 15) == 0,
+               PC_ERR_ARG, "pc_rope_append_slots: rows must keep 16-byte alignment");
+    hipLaunchKernelGGL(rope_append_slots_kernel, dim3(S), dim3(kThreads), 0, (hipStream_t)stream, qkv, ld, in_layout,
+                       (_Float16*)q_hi, (_Float16*)q_lo, q_token_stride, (const float2*)cs, kv_base, cap, len, live, layer, H, Hkv, D);
+    return pc_check_launch("rope_append_slots_kernel");
+}
+
+PC_EXPORT int64_t pc_attn_decode_slots_workspace_bytes(int32_t S, int32_t H, int32_t D, int32_t nsplit) {
+    if (S < 1 || H < 1 || D < 1 || nsplit < 1) return 0;
+    return (int64_t)S * H * nsplit * (D + 2) * (int64_t)sizeof(float);
+}
+
+PC_EXPORT int pc_attn_decode_slots(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                                   const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t layer, int32_t H,
+                                   int32_t Hkv, int32_t D, float softmax_scale, int32_t nsplit, void* workspace,
+                                   int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, void* stream) {
+    PC_REQUIRE(slot_shape_ok(S, H, Hkv, D) && layer >= 0, PC_ERR_ARG,
+               "pc_attn_decode_slots: 1 <= S <= 16, H a multiple of Hkv, head_dim 64 or 128");
+    PC_REQUIRE(nsplit >= 1 && nsplit <= kMaxSplit, PC_ERR_ARG, "pc_attn_decode_slots: nsplit must be in [1, 32]");
+    PC_REQUIRE(q_hi && q_lo && kv_base && cap && len && live && workspace && out_frag_hi && out_frag_lo, PC_ERR_ARG,
+               "pc_attn_decode_slots: null pointer");
+    PC_REQUIRE(q_token_stride % 8 == 0 && ((uintptr_t)q_hi & 15) == 0 && ((uintptr_t)q_lo & 15) == 0 && (H * D) % 32 == 0, PC_ERR_ARG,
+               "pc_attn_decode_slots: q rows must keep 16-byte alignment and H * head_dim be a multiple of 32");
+    PC_REQUIRE(workspace_bytes >= pc_attn_decode_slots_workspace_bytes(S, H, D, nsplit) && ((uintptr_t)workspace & 7) == 0, PC_ERR_ARG,
+               "pc_attn_decode_slots: workspace too small (pc_attn_decode_slots_workspace_bytes) or misaligned");
+    float* part_o = (float*)workspace;
+    float* part_ml = part_o + (int64_t)S * H * nsplit * D;
+    const float scale_log2 = softmax_scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    if (D == 128) {
+        launch_decode_d<128>(S, H, Hkv, nsplit, st, (const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len,
+                             live, layer, scale_log2, part_o, part_ml);
+        hipLaunchKernelGGL(attn_merge_slots_kernel<128>, dim3(H, S), dim3(128), 0, st, part_o, part_ml, cap, len, live, H, nsplit,
+                           (_Float16*)out_frag_hi, (_Float16*)out_frag_lo);
+    } else {
+        launch_decode_d<64>(S, H, Hkv, nsplit, st, (const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len,
+                            live, layer, scale_log2, part_o, part_ml);
+        hipLaunchKernelGGL(attn_merge_slots_kernel<64>, dim3(H, S), dim3(64), 0, st, part_o, part_ml, cap, len, live, H, nsplit,
+                           (_Float16*)out_frag_hi, (_Float16*)out_frag_lo);
+    }
+    return pc_check_launch("attn_decode_slots_kernel");
+}

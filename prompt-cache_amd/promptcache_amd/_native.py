@@ -152,6 +152,12 @@ SIGNATURES = {
                                      _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pc_greedy_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pc_sample_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pc_rope_append_slots": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pc_attn_decode_slots_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
+    "pc_attn_decode_slots": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
+                                       _vp, _vp]),
+    "pc_sample_advance_slots": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
+                                          _vp, _vp]),
     "pc_quant_act_i8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_rmsnorm_quant_i8": (C.c_int, [_vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_outlier_corr": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -717,6 +723,39 @@ def greedy_advance(logits, vocab: int, ids, pos, past, ring, counter, stream: Op
     rc = load().pc_greedy_advance(logits.data_ptr(), vocab, ids.data_ptr(), pos.data_ptr(), past.data_ptr(), ring.data_ptr(),
                                   counter.data_ptr(), ring.numel(), current_stream() if stream is None else stream)
     check(rc, "pc_greedy_advance")
+
+
+def rope_append_slots(qkv, ld: int, in_layout: int, q_hi, q_lo, q_ts: int, cs, kv_base, cap, length, live, S: int, layer: int,
+                      H: int, Hkv: int, D: int, stream: Optional[int] = None) -> None:
+    """RoPE + K / V append for every live slot (pc_rope_append_slots); the slot state tensors are device arrays over S slots."""
+    rc = load().pc_rope_append_slots(qkv.data_ptr(), ld, in_layout, q_hi.data_ptr(), q_lo.data_ptr(), q_ts, cs.data_ptr(),
+                                     kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(), live.data_ptr(), S, layer, H, Hkv, D,
+                                     current_stream() if stream is None else stream)
+    check(rc, "pc_rope_append_slots")
+
+
+def attn_decode_slots_workspace_bytes(S: int, H: int, D: int, nsplit: int) -> int:
+    return int(load().pc_attn_decode_slots_workspace_bytes(S, H, D, nsplit))
+
+
+def attn_decode_slots(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int, layer: int, H: int, Hkv: int, D: int,
+                      softmax_scale: float, nsplit: int, workspace, out_frag, stream: Optional[int] = None) -> None:
+    """One-row attention of every live slot over its own arena (pc_attn_decode_slots) -> fragment planes (hi, lo)."""
+    rc = load().pc_attn_decode_slots(q_hi.data_ptr(), q_lo.data_ptr(), q_ts, kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(),
+                                     live.data_ptr(), S, layer, H, Hkv, D, softmax_scale, nsplit, workspace.data_ptr(),
+                                     workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
+                                     current_stream() if stream is None else stream)
+    check(rc, "pc_attn_decode_slots")
+
+
+def sample_advance_slots(logits, ldl: int, vocab: int, params, seeds, history, ids, pos, length, cap, live, budget, stop_ids, ring,
+                         counters, ring_cap: int, S: int, processed_out=None, stream: Optional[int] = None) -> None:
+    """Tail of a captured batched decode step (pc_sample_advance_slots): chain + draw + state advance for every live slot."""
+    rc = load().pc_sample_advance_slots(logits.data_ptr(), ldl, vocab, params.data_ptr(), seeds.data_ptr(), history.data_ptr(),
+                                        ids.data_ptr(), pos.data_ptr(), length.data_ptr(), cap.data_ptr(), live.data_ptr(),
+                                        budget.data_ptr(), stop_ids.data_ptr(), ring.data_ptr(), counters.data_ptr(), ring_cap, S,
+                                        _ptr(processed_out), current_stream() if stream is None else stream)
+    check(rc, "pc_sample_advance_slots")
 
 
 def sample_params_bytes(temperature: float, repetition_penalty: float, top_p: float, top_k: int, seed: int) -> bytes:

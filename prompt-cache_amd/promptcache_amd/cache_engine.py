@@ -738,9 +738,14 @@ class SchemaCache:
 
 
 class CacheEngine:
+    MAX_SLOTS = 16          # sequences one batched decode step takes (LlamaHIP.SlotLoop)
+
     def __init__(self, max_ctx_length: int, lm: LanguageModel, target_device=None, module_memory: Optional[str] = None,
-                 module_kv: Optional[str] = None):
-        """``module_memory``: where add_schema leaves the module KV -- ``"device"`` (HBM, default) or ``"host"`` (pinned
+                 module_kv: Optional[str] = None, slots: int = 1):
+        """``slots``: how many prompts can be staged at the same time, each in a staged buffer of its own (``process(...,
+        slot=k)``; what ``GenerationEngine.generate_batch`` decodes together).  Slot 0 is ``self.prompt_cache``; the buffers
+        of the other slots are allocated when they are first used.
+        ``module_memory``: where add_schema leaves the module KV -- ``"device"`` (HBM, default) or ``"host"`` (pinned
         host memory, gathered over PCIe: the reference's default placement, :283-296; for libraries beyond HBM).
         Individual segments move with ``TokenSequenceCache.upload`` / ``free``.  Env default: PC_MODULE_MEMORY.
         ``module_kv``: the format add_schema leaves the module KV in, in either tier -- ``"fp16"`` (default) or ``"int8"``
@@ -748,6 +753,10 @@ class CacheEngine:
         dequantised into the fp16 staged arena by one ``pc_kv_gather_q8`` launch, so the model sees fp16 K/V of the
         format's accuracy).  Env default: PC_MODULE_KV."""
         _native.load()
+        if not isinstance(slots, int) or isinstance(slots, bool) or not 1 <= slots <= self.MAX_SLOTS:
+            raise ValueError(f"slots must be an integer in [1, {self.MAX_SLOTS}], not {slots!r}")
+        self.slots = slots
+        self.max_ctx_length = max_ctx_length
         self.module_memory = module_memory or os.environ.get("PC_MODULE_MEMORY", "device")
         if self.module_memory not in ("device", "host"):
             raise ValueError(f"module_memory must be 'device' or 'host', not {self.module_memory!r}")
@@ -763,6 +772,28 @@ class CacheEngine:
         # PC_DEFER_GATHER=0: PromptCache.update copies at once, as rounds 1-3 did
         self.prompt_cache.defer_gather = bool(getattr(getattr(lm, "hf_model", None), "supports_fused_gather", False)) and \
             os.environ.get("PC_DEFER_GATHER", "1") != "0"
+        self._slot_caches: List[Optional[PromptCache]] = [None] * slots      # [0] stays None: slot 0 is self.prompt_cache
+
+    def slot_cache(self, slot: int) -> PromptCache:
+        """The staged buffer of ``slot`` (allocated on first use; slot 0: ``self.prompt_cache``)."""
+        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.slots:
+            raise ValueError(f"slot must be an integer in [0, {self.slots}), not {slot!r}")
+        if slot == 0:
+            return self.prompt_cache
+        pc = self._slot_caches[slot]
+        if pc is None:
+            num_layers, num_head, head_dim = self.lm.get_cache_shape()
+            pc = PromptCache(max_ctx_length=self.max_ctx_length, num_layers=num_layers, num_head=num_head, head_dim=head_dim,
+                             target_device=self.target_device)
+            pc.defer_gather = self.prompt_cache.defer_gather
+            self._slot_caches[slot] = pc
+        return pc
+
+    def _reset_slots(self) -> None:
+        self.prompt_cache.reset()
+        for pc in self._slot_caches:
+            if pc is not None:
+                pc.reset()
 
     def add_schema(self, schema: Union[str, Schema], batch_size: int = 1, max_tokens: Optional[int] = None,
                    no_cache: bool = False):
@@ -829,7 +860,7 @@ class CacheEngine:
         if name not in self.schemas:
             raise ValueError(f"There is no such schema named {name} in the cache")
         del self.schemas[name]
-        self.prompt_cache.reset()
+        self._reset_slots()
         # The module stores go back to torch's caching allocator.  The reference also calls
         # torch.cuda.empty_cache() here (:376-378); on ROCm that hands multi-GB blocks back to the driver and the
         # next add_schema pays hipMalloc for them again (measured: 0.27 s -> 0.87 s per persona encode).
@@ -837,12 +868,13 @@ class CacheEngine:
 
     def remove_all_schemas(self):
         self.schemas = {}
-        self.prompt_cache.reset()
+        self._reset_slots()
         gc.collect()
 
-    def process(self, prompt: Prompt, no_cache: bool = False, return_full_position_ids: bool = False
+    def process(self, prompt: Prompt, no_cache: bool = False, return_full_position_ids: bool = False, slot: int = 0
                 ) -> Tuple[List[int], List[int], float, Optional[KVCache]]:
-        """Prompt -> (new token ids, their position ids, gather time in ms, staged KV | None).
+        """Prompt -> (new token ids, their position ids, gather time in ms, staged KV | None).  ``slot``: which staged buffer
+        of a ``slots=`` engine takes the prompt (the other slots' buffers are not touched).
 
         Request assembly follows the reference step by step (:411-474): explicit-stack DFS over
         (module reference, schema module) pairs, arguments fill the first positions of their
@@ -850,7 +882,8 @@ class CacheEngine:
         # cache_time: the reference brackets request assembly + PromptCache.update with device events (:391-394, :507-509).
         # When the staging is left to the first forward, or nothing is staged at all (no_cache: pure host assembly), there
         # is no device work in here to bracket: host wall-clock then.
-        host_timed = self.prompt_cache.defer_gather or no_cache
+        pc = self.slot_cache(slot)
+        host_timed = pc.defer_gather or no_cache
         t_host = time.perf_counter()
         if not host_timed:
             start = torch.cuda.Event(enable_timing=True)
@@ -911,10 +944,10 @@ class CacheEngine:
                 raise ValueError(f"segment {s!r} of schema {schema.name} has no cached KV")
             sc.inc_usage_counter()
             seq_caches.append(sc)
-        self.prompt_cache.update(seq_caches)
-        cache = self.prompt_cache.cache
+        pc.update(seq_caches)
+        cache = pc.cache
         if host_timed:
-            if self.prompt_cache.arena.pending is None:      # update() launched the copy after all (host-tier segments)
+            if pc.arena.pending is None:      # update() launched the copy after all (host-tier segments)
                 torch.cuda.synchronize()
             cache_time = (time.perf_counter() - t_host) * 1e3
         else:
@@ -929,5 +962,5 @@ class CacheEngine:
             # DFS order of `used`: an ALiBi model reads position_ids[:S] as the positions of arena rows [0, S).  (The
             # reference returns the DFS order at :517-519 while staging the sorted order -- the two diverge as soon as
             # the usage counters do; not reproduced.)
-            position_ids = [p for c in self.prompt_cache.staged for p in c.token_sequence.position_ids()] + position_ids
+            position_ids = [p for c in pc.staged for p in c.token_sequence.position_ids()] + position_ids
         return input_ids, position_ids, cache_time, cache

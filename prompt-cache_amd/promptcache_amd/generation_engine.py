@@ -219,3 +219,128 @@ class GenerationEngine:
                 loop.close(len(new_ids) - 1)                 # steps of the loop that produced a token (the first came from the prefill)
             del past, loop
             gc.collect()
+
+    # -- several prompts at once ------------------------------------------------------------------
+    MAX_BATCH = 16
+
+    def batch_plan(self, n_requests: int, params: GenerationParameters) -> Tuple[bool, str]:
+        """``(batched, reason)``: whether ``generate_batch`` decodes ``n_requests`` sequences together in one device loop
+        (``model/llama_hip.py`` SlotLoop) or runs them one after another through ``generate``, and why.  Host logic only."""
+        hf = getattr(self.lm, "hf_model", None)
+        plain_greedy = params.greedy and params.repetition_penalty <= 1.0
+        if n_requests < 1:
+            return False, "no requests"
+        if n_requests > self.MAX_BATCH:
+            return False, f"more than {self.MAX_BATCH} requests"
+        if getattr(self.lm, "use_full_position_ids", False):
+            return False, "the model takes full position ids (per-key positions are re-based on the host every step)"
+        if not hasattr(hf, "slot_loop") or not hf.slot_loop_available():
+            return False, "the model has no batched decode loop (architecture, int8 weights or PC_DECODE_TAIL=1)"
+        if plain_greedy and not self.device_greedy_loop:
+            return False, "PC_DEVICE_GREEDY=0"
+        if not plain_greedy and not self.device_sample_loop:
+            return False, "PC_DEVICE_SAMPLE=0"
+        if len(params.stop_token_ids) > 8:
+            return False, "more than 8 stop token ids"
+        if params.max_new_tokens < 2:
+            return False, "nothing to decode after the first token"
+        return True, "one device loop over all sequences"
+
+    @torch.inference_mode()
+    def generate_batch(self, requests, params: GenerationParameters, stream_interval: int = 2
+                       ) -> Generator[Tuple[int, Output], None, None]:
+        """Generate for several prompts at once: ``requests = [(token_ids, position_ids, cache), ...]``, each as
+        ``CacheEngine.process(prompt, slot=k)`` returned it (every cache in a staged buffer of its own).  Yields ``(index,
+        Output)`` pairs; per sequence the ``Output`` stream, the stop-token and stop-string handling, ``max_new_tokens`` and the
+        position rule are ``generate``'s.  The prefills run one after another through the path ``generate`` takes and the first
+        token of each sequence is drawn as ``generate`` draws it; then ONE device loop decodes all sequences together, the
+        host one replay ahead.  Sequence k of a sampled batch uses seed ``seed + k`` of the one seed taken from torch's default
+        generator.  Where no batched loop is available (``batch_plan``) the sequences run one after another through
+        ``generate``."""
+        requests = [(list(t), list(p), c) for t, p, c in requests]
+        batched, _ = self.batch_plan(len(requests), params)
+        hf = getattr(self.lm, "hf_model", None)
+        if batched:
+            # every cache must be a staged batch-1 arena, no two the same
+            arenas = [getattr(c, "arena", None) for _, _, c in requests]
+            batched = all(a is not None and a.B == 1 for a in arenas) and len(set(map(id, arenas))) == len(arenas)
+        if not batched:
+            full = bool(getattr(self.lm, "use_full_position_ids", False))
+            for k, (token_ids, position_ids, cache) in enumerate(requests):
+                for out in self.generate(token_ids, position_ids, params, cache, stream_interval, use_full_position_ids=full):
+                    yield k, out
+            return
+
+        processors = params.get_logits_processor()
+        plain_greedy = params.greedy and params.repetition_penalty <= 1.0
+        seed = 0 if plain_greedy else int(torch.randint(0, 2 ** 62, (1,)))
+        last_step = params.max_new_tokens - 1
+        n = len(requests)
+        output_ids = [list(t) for t, _, _ in requests]
+        new_ids: List[List[int]] = [[] for _ in range(n)]
+        total_ms, ttft_ms = [0.0] * n, [0.0] * n
+        done = [False] * n
+        pasts: list = [None] * n
+        first_free = [max(p) + 1 for _, p, _ in requests]
+        loop, members = None, []
+
+        def emit(k: int, step: int, token: int):
+            """generate's bookkeeping for one token of sequence k -> the Output to yield, if any."""
+            output_ids[k].append(token)
+            new_ids[k].append(token)
+            fin = token in params.stop_token_ids
+            out = None
+            if step % stream_interval == 0 or step == last_step or fin:
+                text, new_text, hit, partial = self._render(output_ids[k], new_ids[k], params.stop_str)
+                fin = fin or hit
+                if not partial:
+                    out = Output(text, new_text, total_ms[k], ttft_ms[k])
+            done[k] = fin or step == last_step
+            return out
+
+        try:
+            for k, (token_ids, position_ids, cache) in enumerate(requests):
+                logits, pasts[k], ms = self._forward(token_ids, position_ids, cache)
+                ttft_ms[k] = total_ms[k] = ms
+                if self.verbose:
+                    print(f"Prefill latency: {ms:.2f} ms")
+                if plain_greedy:
+                    token = self._pick(processors(None, logits[:, -1, :])[0], True)
+                else:
+                    token = hf.sample_token(logits[0, -1], params, seed + k, output_ids[k])
+                out = emit(k, 0, token)
+                if out is not None:
+                    yield k, out
+            members = [k for k in range(n) if not done[k]]
+            if members:
+                loop = hf.slot_loop([pasts[k] for k in members], [new_ids[k][-1] for k in members],
+                                    [first_free[k] + 1 for k in members], last_step, None if plain_greedy else params,
+                                    [seed + k for k in members], [output_ids[k] for k in members], params.stop_token_ids)
+                if loop is None:
+                    raise RuntimeError("generate_batch: the model refused a batched decode loop over these caches")
+                loop.enqueue()
+            for step in range(1, params.max_new_tokens):
+                if all(done):
+                    break
+                if loop.n <= step and loop.n < last_step:
+                    loop.enqueue()                                 # the replay AFTER the one whose tokens are read below
+                ms = loop.elapsed_ms(step - 1)
+                for j, k in enumerate(members):
+                    if done[k]:
+                        continue
+                    token = loop.token(j, step - 1)
+                    if token is None:                              # (the device switched the slot off: its arena is full)
+                        done[k] = True
+                        continue
+                    total_ms[k] += ms
+                    out = emit(k, step, token)
+                    if done[k] and token not in params.stop_token_ids and step != last_step:
+                        loop.kill(j)                               # a stop string: the device cannot know
+                    if out is not None:
+                        yield k, out
+        finally:
+            # also when the consumer abandons the generator at a yield: every arena's length goes back to what was consumed
+            if loop is not None:
+                loop.close([len(new_ids[k]) - 1 for k in members])
+            del pasts, loop
+            gc.collect()

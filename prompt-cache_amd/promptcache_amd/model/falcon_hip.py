@@ -27,6 +27,7 @@ from .llama_hip import LlamaHIP
 
 
 class FalconHIP(LlamaHIP):
+    supports_slot_loop = False      # (batched decode over slots runs on the Llama layer loop only)
     _shared_prefix_loop = False     # (its many-row loop keeps a copy of the trunk per batch row)
     supports_fused_gather = True    # (the weight-streaming loop hands pc_attn the row table: the first forward stages, as in LlamaHIP)
 

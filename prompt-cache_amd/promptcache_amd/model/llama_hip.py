@@ -257,6 +257,147 @@ class SampleLoop(GreedyLoop):
         return self.m._loop_graph(arena, past_len, sample=True)
 
 
+class SlotLoop:
+    """Batched decode: up to 16 sequences, each in a batch-1 arena of its own, advanced together by one captured step.
+
+    GreedyLoop's protocol over SLOTS.  Every replay runs the layer stack over ``S`` rows (one per slot), RoPE + append and the
+    attention per slot over the slot's own arena (``pc_rope_append_slots`` / ``pc_attn_decode_slots``), and one advance launch
+    (``pc_sample_advance_slots``) that draws every slot's token and rewrites the device words the next replay reads: token,
+    position, length, live flag, step counter, history bitmap.  A slot stops on the device (stop id, step budget, full arena)
+    and costs nothing afterwards but its GEMM row; the host mirrors those rules, so ``token(k, i)`` is None from the step after
+    sequence k's last one.  ``kill(k)`` switches a sequence off between replays (stop strings).
+
+    ``enqueue()`` -> step index; ``token(k, i)`` waits for step i only; ``logits`` is the ``[S][V]`` fp32 tensor of the last
+    replay (row = slot index ``slot_index[k]``)."""
+
+    RING = 1024
+    MAX_SLOTS = 16
+
+    @torch.inference_mode()
+    def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, params=None, seeds=None, histories=None,
+                 stop_ids=(), slots: Optional[int] = None, slot_index=None):
+        n = len(arenas)
+        idx = list(range(n)) if slot_index is None else [int(i) for i in slot_index]
+        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= max(idx) + 1)
+        assert 1 <= n and len(set(idx)) == n and 0 <= min(idx) and max(idx) < S <= self.MAX_SLOTS, (n, idx, S)
+        assert len(tokens) == n and len(positions) == n and len(stop_ids) <= 8 and max_new >= 1
+        self.m, self.S, self.idx, self.max_new = model, S, idx, max_new
+        grown = []
+        for a in arenas:                              # no address may move under the captured step
+            need = a.length + max_new + 2
+            grown.append(a.grown(max(need, 2 * a.cap)) if need > a.cap else a)
+            model._tail_done(grown[-1], 0, 1, a.length)       # rows are appended without residuals: a residual tail ends here
+        self.arenas = grown
+        self.len0 = [a.length for a in grown]
+        self.nsplit = model._slot_nsplit(S, max(self.len0) + max_new + 1)
+        st = self.st = model._slot_state(S)
+        model._live_loop = self
+        self.sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
+        self.ctr0 = 1 if self.sampled else 0           # (a sampled stream drew its first token at step 0: sample_token)
+        V = model.config.vocab_size
+        hw = (V + 31) // 32
+
+        def col(vals, dtype, fill=0):
+            t = torch.full((S,), fill, dtype=dtype)
+            for k, v in zip(idx, vals):
+                t[k] = v
+            return t
+        st["kv_base"].copy_(col([a.buf.data_ptr() for a in grown], torch.int64), non_blocking=True)
+        st["cap"].copy_(col([a.cap for a in grown], torch.int32), non_blocking=True)
+        st["len"].copy_(col(self.len0, torch.int32), non_blocking=True)
+        st["pos"].copy_(col(positions, torch.int32), non_blocking=True)
+        st["ids"].copy_(col(tokens, torch.int64), non_blocking=True)
+        st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
+        st["budget"].copy_(col([max_new] * n, torch.int32), non_blocking=True)
+        st["ctr"].fill_(self.ctr0)
+        st["stop"].copy_(torch.tensor(list(stop_ids) + [-1] * (8 - len(stop_ids)), dtype=torch.int32), non_blocking=True)
+        seeds = [0] * n if seeds is None else list(seeds)
+        st["seeds"].copy_(col([sd & (2 ** 63 - 1) for sd in seeds], torch.int64), non_blocking=True)
+        if self.sampled:
+            blk = sample_params_block(params, 0)
+            hist = torch.zeros((S, hw), dtype=torch.int32)
+            for k, h in zip(idx, histories):
+                hist[k] = _history_bits(h, V)
+            st["hist"].copy_(hist, non_blocking=True)
+        else:
+            blk = _native.sample_params_bytes(0.0, 1.0, 1.0, -1, 0)        # greedy: the argmax of the raw row
+        st["params"].copy_(torch.frombuffer(bytearray(blk), dtype=torch.uint8))
+        self.stop_ids = set(int(t) for t in stop_ids)
+        self.logits = st["logits"]
+        self.n = 0
+        self.events = []
+        self.host = torch.empty((self.RING, S), dtype=torch.int32, pin_memory=True)
+        self._ring2d = st["ring"].view(S, self.RING)
+        self._alive = [True] * n          # host mirror of the live words, after the newest step whose tokens were looked at
+        self._seen = 0                    # steps whose tokens the mirror has taken in
+        self._last = [-1] * n             # index of the last step that produced a token for sequence k (-1: none yet)
+        self._killed = [None] * n         # step count at which kill(k) took effect
+        torch.cuda.current_stream().synchronize()        # (the pageable sources of the copies above may go now)
+
+    @torch.inference_mode()
+    def enqueue(self) -> int:
+        m, st = self.m, self.st
+        if getattr(m, "_live_loop", None) is not self:
+            raise RuntimeError("SlotLoop: another device loop on this model took over (one device-side generation per model "
+                               "at a time)")
+        g = m._slot_graph(self.S, self.nsplit)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        i = self.n
+        r = (self.ctr0 + i) % self.RING
+        self.host[r].copy_(self._ring2d[:, r], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self.events.append((e0, e1, done))
+        self.n += 1
+        return i
+
+    def _advance_mirror(self, upto: int) -> None:
+        """Take the tokens of steps [seen, upto] into the host mirror of the live words (the rule of pc_sample_advance_slots)."""
+        while self._seen <= upto:
+            i = self._seen
+            self.events[i][2].synchronize()
+            row = self.host[(self.ctr0 + i) % self.RING]
+            for k, s in enumerate(self.idx):
+                if not self._alive[k] or (self._killed[k] is not None and i >= self._killed[k]):
+                    self._alive[k] = False
+                    continue
+                self._last[k] = i
+                tok = int(row[s])
+                if tok in self.stop_ids or i + 1 >= self.max_new or self.len0[k] + i + 2 >= self.arenas[k].cap:
+                    self._alive[k] = False
+            self._seen += 1
+
+    def token(self, k: int, i: int) -> Optional[int]:
+        """Token of sequence ``k`` at step ``i`` (None: the sequence had stopped before that step)."""
+        self._advance_mirror(i)
+        if i > self._last[k]:
+            return None
+        return int(self.host[(self.ctr0 + i) % self.RING][self.idx[k]])
+
+    def kill(self, k: int) -> None:
+        """Switch sequence ``k`` off from the next replay on (ordered behind the replays already enqueued)."""
+        s = self.idx[k]
+        self.st["live"][s: s + 1].fill_(0)
+        if self._killed[k] is None:
+            self._killed[k] = self.n
+
+    def elapsed_ms(self, i: int) -> float:
+        e0, e1, done = self.events[i]
+        done.synchronize()
+        return e0.elapsed_time(e1)
+
+    def close(self, consumed) -> None:
+        """``consumed[k]``: how many of the loop's steps sequence k's consumer used.  Each arena's ``length`` goes to exactly that
+        (rows a look-ahead replay wrote past it are dead), and the loop state is released."""
+        for a, l0, c in zip(self.arenas, self.len0, consumed):
+            a.length = l0 + int(c)
+        if getattr(self.m, "_live_loop", None) is self:
+            self.m._live_loop = None
+
+
 class LlamaHIP:
     """Weights live on one MI355X in fp16; ``wqkv`` and ``wgu`` are the row-concatenated q|k|v and
     gate|up projections so each is one GEMM."""
@@ -1481,6 +1622,125 @@ class LlamaHIP:
         behind ``past``, continuing the random stream of ``seed`` at step 1.  None where ``greedy_loop`` gives None."""
         arena = self._loop_arena(past)
         return None if arena is None else SampleLoop(self, arena, token, position, max_new, params, seed, history_ids)
+
+    # ---- batched decode over slots (SlotLoop) ---------------------------------------------------------------------------
+    supports_slot_loop = True       # (a subclass with layer loops of its own says no)
+
+    def slot_loop_available(self) -> bool:
+        """Whether this model can host a ``SlotLoop``: the fp16 weight-streaming stack with folded norms, default decode
+        precision (no residual tail through decode), head_dim 64 or 128."""
+        return bool(self.supports_slot_loop and self.skinny and self.use_graphs and self.supports_greedy_loop and
+                    not self.int8_weights and not self.llm_int8 and self.fuse_norm and not self.decode_tail and
+                    not self.use_chain and self.D in (64, 128) and self.batch_invariant)
+
+    def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
+                  slots: Optional[int] = None, slot_index=None) -> Optional["SlotLoop"]:
+        """A batched device-side decode loop over the arenas behind ``pasts`` (one ``past_key_values`` per sequence, each a
+        batch-1 arena of its own): sequence k feeds ``tokens[k]`` at position ``positions[k]`` next.  ``params`` None or plain
+        greedy: argmax; otherwise the sampled chain with ``seeds[k]`` (the stream continues at step 1) and ``histories[k]``.
+        ``stop_ids``: up to 8 token ids that end a sequence on the device.  None where no batched loop is available -- the
+        caller then decodes the sequences one after another."""
+        if not self.slot_loop_available() or not 1 <= len(pasts) <= SlotLoop.MAX_SLOTS or len(stop_ids) > 8:
+            return None
+        arenas = []
+        for past in pasts:
+            a = self._loop_arena(past)
+            if a is None or any(a is b for b in arenas):
+                return None
+            a.materialize()                       # (a staging no forward carried out yet)
+            arenas.append(a)
+        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index)
+
+    def _slot_nsplit(self, S: int, max_keys: int) -> int:
+        """Splits of the key axis of pc_attn_decode_slots: enough workgroups to cover the chip at S slots, at least 256 keys
+        per split at the longest length the loop can reach (a power of two, so that few graphs are captured)."""
+        G = self.H // self.Hkv
+        passes = 1 if G == 1 else (G + 3) // 4 if G <= 4 else (G + 7) // 8
+        want = max(1, 1024 // max(1, S * self.Hkv * passes))
+        ns = 1
+        while ns < 32 and ns < want and ns * 2 * 256 <= max_keys:
+            ns *= 2
+        return ns
+
+    def _slot_state(self, S: int) -> dict:
+        """Device words of the S-slot decode step (one set per S: the captured steps hold their addresses)."""
+        sts = self.__dict__.setdefault("_slot_sts", {})
+        st = sts.get(S)
+        if st is None:
+            dev, V = self.device, self.config.vocab_size
+            z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)
+            st = dict(kv_base=z(S, torch.int64), cap=z(S, torch.int32), len=z(S, torch.int32), pos=z(S, torch.int32),
+                      ids=z(S, torch.int64), live=z(S, torch.int32), budget=z(S, torch.int32), ctr=z(S, torch.int32),
+                      stop=torch.full((8,), -1, dtype=torch.int32, device=dev), seeds=z(S, torch.int64),
+                      ring=z(S * SlotLoop.RING, torch.int32),
+                      params=z(ctypes.sizeof(_native.SampleParams), torch.uint8), hist=z((S, (V + 31) // 32), torch.int32),
+                      logits=z((S, V), torch.float32))
+            sts[S] = st
+        return st
+
+    def _slot_graph(self, S: int, nsplit: int):
+        """The captured S-slot decode step.  Everything that changes from step to step or from batch to batch -- arena
+        addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch."""
+        key = ("slots", S, nsplit)
+        g = self._graphs.pop(key, None)
+        if g is not None:
+            self._graphs[key] = g
+            return g
+        if len(self._graphs) >= self.max_graphs:
+            self._graphs.pop(next(iter(self._graphs)))
+        st = self._slot_state(S)
+        # one eager pass first (loads code objects / sizes the allocator) with every slot idle: it appends nothing and
+        # advances nothing, the live words are put back behind it
+        live = st["live"].clone()
+        st["live"].zero_()
+        self._forward_slots(st, S, nsplit)
+        torch.cuda.synchronize()
+        prime_graph_capture(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._forward_slots(st, S, nsplit)
+        st["live"].copy_(live)
+        self._graphs[key] = g
+        return g
+
+    def _forward_slots(self, st: dict, S: int, nsplit: int) -> None:
+        """One decode step over S slots: the <= 16-row projections of ``_layers_norm_fused`` around per-slot RoPE + append
+        and attention; logits to ``st["logits"]``, then the advance launch."""
+        n = _native
+        dev, c = self.device, self.config
+        H, Hkv, D, hid, inter = self.H, self.Hkv, self.D, c.hidden_size, c.intermediate_size
+        W, eps, V = (H + 2 * Hkv) * D, c.rms_norm_eps, c.vocab_size
+        cs = torch.empty((S, D // 2, 2), dtype=torch.float32, device=dev)
+        n.rope_table(st["pos"], self.inv_freq, cs, S, D)
+        h16 = torch.empty((S, hid), dtype=self.dtype, device=dev)
+        n.embed_gather(self.embed, st["ids"], h16, S, hid, V)
+        x = h16.float()
+        qkv = torch.empty((S, W), dtype=torch.float32, device=dev)
+        q16 = torch.zeros((S, H * D), dtype=self.dtype, device=dev)
+        q16l = torch.zeros((S, H * D), dtype=self.dtype, device=dev)
+        ws = torch.empty(max(n.attn_decode_slots_workspace_bytes(S, H, D, nsplit), 8) // 4, dtype=torch.float32, device=dev)
+
+        def planes(k):          # (zeroed: rows of idle slots are never written and must not hold NaN bit patterns)
+            return (torch.zeros((1, k // 32, 64, 8), dtype=self.dtype, device=dev),
+                    torch.zeros((1, k // 32, 64, 8), dtype=self.dtype, device=dev))
+        ah, al = planes(H * D)
+        ch, cl = planes(inter)
+        ks_down = self.ks_down and self.ks_min_rows <= S and inter >= 2 * hid
+        for li, lw in enumerate(self.layers):
+            n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+            n.rope_append_slots(qkv, W, 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D)
+            n.attn_decode_slots(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
+                                self.softmax_scale, nsplit, ws, (ah, al))
+            n.gemm_skinny(lw["wo_f"], ah, al, S, hid, H * D, n.EPI_ADD, y=x, ldy=hid)                  # x += attn @ Wo^T
+            n.gemm_skinny_norm(lw["wgu_f"], x, lw["ln2"], eps, S, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+            if ks_down:
+                sc, ctr = self._ks_buffers(hid)
+                n.gemm_skinny_ks(lw["wdown_f"], ch, cl, S, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr)
+            else:
+                n.gemm_skinny(lw["wdown_f"], ch, cl, S, hid, inter, n.EPI_ADD, y=x, ldy=hid)           # x += act @ Wd^T
+        n.gemm_skinny_norm(self.lm_head_f, x, self.norm, eps, S, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
+        n.sample_advance_slots(st["logits"], V, V, st["params"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
+                               st["cap"], st["live"], st["budget"], st["stop"], st["ring"], st["ctr"], SlotLoop.RING, S)
 
     def _ks_buffers(self, hid: int):
         """Scratch slabs + arrival counters of pc_gemm_skinny_ks (shared by every such launch of the model: they run one

@@ -36,6 +36,7 @@ def alibi_slopes(num_heads: int, alibi_bias_max: int = 8) -> torch.Tensor:
 
 
 class MptHIP(LlamaHIP):
+    supports_slot_loop = False      # (batched decode over slots runs on the Llama layer loop only)
     _shared_prefix_loop = False     # (its many-row loop keeps a copy of the trunk per batch row)
     supports_fused_gather = False   # (its layer loops read staged rows from the arena: PromptCache.update copies at once)
 

@@ -1,0 +1,110 @@
+"""Batched decode against one-after-another decode, same process, same box: 7b shape (random init), bench.py's persona schema,
+greedy.  (a) B calls of generate() one after another through the device greedy loop -- how B prompts are served without
+generate_batch -- and (b) generate_batch over B slots, for B in --batches; decode tokens per second summed over the sequences,
+prefills excluded from both; --repeats interleaved repetitions, medians reported.  Also the byte-model ratio
+B (W + K) / (W + B K) from the weight bytes W a decode step streams and the K/V bytes K a sequence's step reads.  One JSON line.
+
+    python tools/batch_decode_bench.py [--new 64] [--out profiles/r09_batch_decode.json]
+    python tools/batch_decode_bench.py --only-batch 8        # (b) at B = 8 alone: the run to put under rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "prompt-cache_amd")]
+from promptcache_amd import CacheEngine, GenerationEngine, GenerationParameters, Prompt, synth  # noqa: E402
+from promptcache_amd.model import Llama2  # noqa: E402
+
+
+def serial_rate(ge, eng, prompt, params, B):
+    """(a): B generations one after another; decode seconds = first Output to last Output of each, summed."""
+    dt, n = 0.0, 0
+    for _ in range(B):
+        ids, pos, _, cache = eng.process(prompt)
+        t0 = None
+        for _out in ge.generate(ids, pos, params, cache, stream_interval=10 ** 9):
+            if t0 is None:
+                t0 = time.perf_counter()
+        torch.cuda.synchronize()
+        dt += time.perf_counter() - t0
+        n += params.max_new_tokens - 1
+    return n / dt
+
+
+def batch_rate(ge, eng, prompt, params, B):
+    """(b): one generate_batch over B slots; decode seconds = the last first-token Output (all prefills done) to the end."""
+    reqs = [eng.process(prompt, slot=k) for k in range(B)]
+    firsts, t0 = 0, None
+    for _k, _out in ge.generate_batch([(r[0], r[1], r[3]) for r in reqs], params, stream_interval=10 ** 9):
+        firsts += 1
+        if firsts == B:
+            t0 = time.perf_counter()
+    torch.cuda.synchronize()
+    return B * (params.max_new_tokens - 1) / (time.perf_counter() - t0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--new", type=int, default=64, help="greedy tokens per sequence")
+    ap.add_argument("--batches", default="1,2,4,8,16")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--only-batch", type=int, default=0, help="run (b) at this B alone, twice (warm + one), and print its rate")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "batch_decode_bench measures on the GPU"
+    batches = [int(b) for b in args.batches.split(",")]
+    lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0)
+    eng = CacheEngine(4096, lm, slots=max(batches + [args.only_batch]))
+    fmt = lm.get_formatter()
+    sp, pp = synth.persona_like()
+    eng.add_schema(fmt(sp))
+    prompt = Prompt(pp, [fmt])
+    ge = GenerationEngine(lm)
+    params = GenerationParameters(temperature=0.0, max_new_tokens=args.new, stop_token_ids=[], stop_str=[])
+    assert ge.batch_plan(max(batches), params)[0], ge.batch_plan(max(batches), params)[1]
+    if args.only_batch:
+        batch_rate(ge, eng, prompt, params, args.only_batch)
+        print(json.dumps({"B": args.only_batch, "batch_tok_s": round(batch_rate(ge, eng, prompt, params, args.only_batch), 1)}))
+        return
+
+    m, c = lm.hf_model, lm.hf_model.config
+    hid, inter = c.hidden_size, c.intermediate_size
+    W = 2 * (m.L * ((m.H + 2 * m.Hkv) * m.D * hid + m.H * m.D * hid + 3 * inter * hid) + c.vocab_size * hid)      # fp16 bytes per step
+    ids, _, _, cache = eng.process(prompt)
+    staged = len(eng.prompt_cache)
+    keys = staged + len(ids) + args.new // 2                                   # mean keys a step reads
+    K = 2 * m.L * 2 * m.Hkv * m.D * keys
+    result = {"shape": "llama2-7b (random init)", "prompt": f"persona schema, {staged} staged + {len(ids)} new tokens", "new_tokens": args.new,
+              "how": "greedy; decode tok/s summed over sequences, prefills excluded; (a) B x generate one after another, (b) generate_batch; "
+                     f"{args.repeats} interleaved repetitions, median", "weight_bytes": W, "kv_bytes_per_sequence": K, "rows": {}}
+    for B in batches:                                                          # warm: graphs captured, code objects loaded
+        batch_rate(ge, eng, prompt, params, B)
+    serial_rate(ge, eng, prompt, params, 1)
+    a = {B: [] for B in batches}
+    b = {B: [] for B in batches}
+    for _ in range(args.repeats):
+        for B in batches:
+            a[B].append(serial_rate(ge, eng, prompt, params, B))
+            b[B].append(batch_rate(ge, eng, prompt, params, B))
+    for B in batches:
+        ra, rb = statistics.median(a[B]), statistics.median(b[B])
+        model = B * (W + K) / (W + B * K)
+        result["rows"][str(B)] = {"serial_tok_s": round(ra, 1), "batch_tok_s": round(rb, 1), "batch_over_serial": round(rb / ra, 3),
+                                  "byte_model_ratio": round(model, 3), "fraction_of_byte_model": round(rb / ra / model, 3)}
+    if "8" in result["rows"]:
+        result["bar_met_at_B8"] = result["rows"]["8"]["fraction_of_byte_model"] >= 0.5
+    line = json.dumps(result)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
