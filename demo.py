@@ -38,6 +38,8 @@ def main():
                     help="module KV store format (default: PC_MODULE_KV, else fp16); int8 = 0.516 of the fp16 bytes")
     ap.add_argument("--batch", type=int, default=0,
                     help="also decode N copies of the prompt with different questions together (generate_batch; N <= 16)")
+    ap.add_argument("--share-trunk", action="store_true",
+                    help="with --batch: read the module rows the N prompts have in common once per step for all of them")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
@@ -87,7 +89,7 @@ def main():
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2):
+            for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2, share_trunk=a.share_trunk):
                 lasts[k] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

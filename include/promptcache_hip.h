@@ -630,7 +630,18 @@ int pc_sample_advance(const float* logits, int32_t vocab, const pc_sample_params
  * the draw on logits[b * logits_row_stride ..] with the random stream seeds[b], the step counters[b] and the history bitmap
  * history_bits[b * ceil(vocab/32) ..]; then ids[b] = token, pos[b] += 1, len[b] += 1, ring[b * ring_cap + counters[b] %
  * ring_cap] = token, counters[b] += 1, budget[b] -= 1, and live[b] = 0 when the token is one of stop_ids[0..8) (unused
- * entries: -1), budget[b] reached 0 or len[b] + 1 >= cap[b].  processed_out (optional, [S][vocab]) as in pc_sample_advance. */
+ * entries: -1), budget[b] reached 0 or len[b] + 1 >= cap[b].  processed_out (optional, [S][vocab]) as in pc_sample_advance.
+ *
+ * pc_attn_decode_slots_trunk: pc_attn_decode_slots for slots that hold the same bytes in their first rows (prompts over one
+ * schema).  Two more device arrays over the S slots: leader[b] = -1: slot b is on its own (keys [0, len[b]] of its own arena);
+ * leader[b] = g: keys [0, trunk[b]) are read from the arena of slot g (kv_base[g], cap[g]), keys [trunk[b], len[b]] from b's own.
+ * Host contract: leader[g] == g, trunk[b] == trunk[g] for every member, 0 < trunk[b] <= len[b].  A slot for which the contract
+ * does not hold (or whose leader lies outside [0, S), has trunk[g] > cap[g] or a null arena) is treated as leader[b] = -1: its
+ * result is the plain attention over its own arena.  The leader's rows are read whether or not the leader is live.  A trunk launch reads each group's shared rows once for all live members (MFMA tiles of 16
+ * query rows = members x the kv head's query heads; `nsplit_trunk` shares of the trunk), an own launch does pc_attn_decode_slots'
+ * arithmetic over the remaining keys in `nsplit_own` shares, and the merge takes nsplit_trunk + nsplit_own partials per (slot,
+ * head) in key order.  A row's result depends on its own q, its keys, trunk and the two split counts only.  With leader = -1
+ * everywhere the planes are bit-identical to pc_attn_decode_slots at nsplit = nsplit_own. */
 int pc_rope_append_slots(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
                          const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live,
                          int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, void* stream);
@@ -639,6 +650,12 @@ int pc_attn_decode_slots(const void* q_hi, const void* q_lo, int64_t q_token_str
                          const int32_t* len, const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
                          float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
                          void* out_frag_lo, void* stream);
+int64_t pc_attn_decode_slots_trunk_workspace_bytes(int32_t S, int32_t H, int32_t D, int32_t nsplit_own, int32_t nsplit_trunk);
+int pc_attn_decode_slots_trunk(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                               const int32_t* cap, const int32_t* len, const int32_t* live, const int32_t* leader,
+                               const int32_t* trunk, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, float softmax_scale,
+                               int32_t nsplit_own, int32_t nsplit_trunk, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
+                               void* out_frag_lo, void* stream);
 int pc_sample_advance_slots(const float* logits, int64_t logits_row_stride, int32_t vocab, const pc_sample_params* params_dev,
                             const uint64_t* seeds, uint32_t* history_bits, int64_t* ids, int32_t* pos, int32_t* len,
                             const int32_t* cap, int32_t* live, int32_t* budget, const int32_t* stop_ids, int32_t* ring,

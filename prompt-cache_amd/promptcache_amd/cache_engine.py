@@ -26,7 +26,7 @@ import torch
 
 from . import _native, parallel
 from .model import LanguageModel
-from .model.kv_arena import KVArena, StagedKV, StagingPlan
+from .model.kv_arena import KVArena, StagedKV, StagingPlan, common_trunks  # noqa: F401
 from .pml import Module, ModuleRef, Path, Prompt, Schema, TokenSequence, UnionModule  # noqa: F401
 
 KVCache = List[Tuple[torch.Tensor, torch.Tensor]]
@@ -178,6 +178,7 @@ class PromptCache:
         self.staged, self.length = [], 0
         self.arena.tail_base, self.arena.tail_len = -1, 0
         self.arena.pending = None
+        self.arena.layout = []
 
     @torch.inference_mode()
     def update(self, modules: Sequence[TokenSequenceCache]):
@@ -230,6 +231,9 @@ class PromptCache:
         self.staged = list(ordered)
         self.length = offset
         a.length = offset
+        # (common_trunks: what batched decode may share; kept rows stay under the format they were gathered from)
+        run = lambda m: (m.token_sequence, len(m), m.format)
+        a.layout = [a.layout[i] if i < len(a.layout) else run(m) for i, m in enumerate(ordered[:keep])] + [run(m) for m in ordered[keep:]]
         a.tail_base, a.tail_len = -1, 0          # a new staging: the residual tail of the previous generation is void
 
     def __len__(self):

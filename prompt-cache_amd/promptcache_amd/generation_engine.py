@@ -247,8 +247,8 @@ class GenerationEngine:
         return True, "one device loop over all sequences"
 
     @torch.inference_mode()
-    def generate_batch(self, requests, params: GenerationParameters, stream_interval: int = 2
-                       ) -> Generator[Tuple[int, Output], None, None]:
+    def generate_batch(self, requests, params: GenerationParameters, stream_interval: int = 2,
+                       share_trunk: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
         """Generate for several prompts at once: ``requests = [(token_ids, position_ids, cache), ...]``, each as
         ``CacheEngine.process(prompt, slot=k)`` returned it (every cache in a staged buffer of its own).  Yields ``(index,
         Output)`` pairs; per sequence the ``Output`` stream, the stop-token and stop-string handling, ``max_new_tokens`` and the
@@ -256,7 +256,10 @@ class GenerationEngine:
         token of each sequence is drawn as ``generate`` draws it; then ONE device loop decodes all sequences together, the
         host one replay ahead.  Sequence k of a sampled batch uses seed ``seed + k`` of the one seed taken from torch's default
         generator.  Where no batched loop is available (``batch_plan``) the sequences run one after another through
-        ``generate``."""
+        ``generate``.  ``share_trunk``: sequences that staged the same leading modules read those rows once per step for the
+        whole group (``LlamaHIP.slot_loop(share_trunk=True)``); None reads ``PC_SLOT_TRUNK`` (default 0)."""
+        if share_trunk is None:
+            share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         requests = [(list(t), list(p), c) for t, p, c in requests]
         batched, _ = self.batch_plan(len(requests), params)
         hf = getattr(self.lm, "hf_model", None)
@@ -315,7 +318,8 @@ class GenerationEngine:
             if members:
                 loop = hf.slot_loop([pasts[k] for k in members], [new_ids[k][-1] for k in members],
                                     [first_free[k] + 1 for k in members], last_step, None if plain_greedy else params,
-                                    [seed + k for k in members], [output_ids[k] for k in members], params.stop_token_ids)
+                                    [seed + k for k in members], [output_ids[k] for k in members], params.stop_token_ids,
+                                    share_trunk=bool(share_trunk))
                 if loop is None:
                     raise RuntimeError("generate_batch: the model refused a batched decode loop over these caches")
                 loop.enqueue()

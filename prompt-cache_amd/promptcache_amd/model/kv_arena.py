@@ -12,6 +12,7 @@ past in every layer of every call, ``promptcache/model/llama2.py:361-364``).
 """
 from __future__ import annotations
 
+import os
 import weakref
 from collections.abc import Sequence
 from typing import List, Optional, Tuple
@@ -66,6 +67,9 @@ class KVArena:
         self.tail_len = 0
         self.pending: Optional[StagingPlan] = None     # a staging that has not been carried out yet (see StagingPlan)
         self.row_tab: Optional[torch.Tensor] = None    # pc_kv_row[cap]: the plan expanded per staged row (device scratch)
+        # what PromptCache.update staged, front to back: (token_sequence, rows, store format the rows were gathered from) runs
+        # (common_trunks reads it; reset clears it).  Rows that a later update kept keep the run they were staged under.
+        self.layout: List[tuple] = []
 
     def materialize(self) -> None:
         """Carry out a pending staging with one ``pc_kv_gather`` launch (no-op without one)."""
@@ -135,8 +139,54 @@ class KVArena:
             a.with_lo().lo[:, :, :, :, :self.length].copy_(self.lo[:, :, :, :, :self.length])
             a.lo_len = self.lo_len
         a.length = self.length
+        a.layout = list(self.layout)
         a.tail_lo, a.tail_base, a.tail_len = self.tail_lo, self.tail_base, self.tail_len   # indexed by key, not by row capacity
         return a
+
+
+def slot_trunk_min_rows() -> int:
+    """Fewest shared rows worth a trunk launch (``PC_SLOT_TRUNK_MIN``; the default is the "at least 256 keys per split" figure
+    of ``LlamaHIP._slot_nsplit``: below it the trunk launch has less than one split's work)."""
+    return int(os.environ.get("PC_SLOT_TRUNK_MIN", "256"))
+
+
+def common_trunks(layouts, min_rows: Optional[int] = None) -> List[Tuple[Optional[int], int]]:
+    """Which sequences of a batch share their leading staged rows.  ``layouts[k]``: the ``(token_sequence, rows[, format])`` runs
+    arena k holds, front to back (``KVArena.layout``).  Sequences are grouped by their FIRST run -- the identity rule of
+    ``PromptCache.update``'s retention, ``is`` on the token sequence, plus equal row counts and equal store format: rows gathered
+    from an fp16 store and rows dequantised from its int8 image after ``quantize_`` are different bytes -- and a group's trunk is
+    the longest leading chain of runs that ALL its members have in common, ``T`` rows.  -> per sequence ``(leader, T)``, the leader being the lowest
+    index of the group (its own index for the leader itself), or ``(None, 0)`` for a sequence on its own: a group of one, or
+    ``T < min_rows``."""
+    if min_rows is None:
+        min_rows = slot_trunk_min_rows()
+
+    def same(a, b) -> bool:
+        return a[0] is b[0] and tuple(a[1:]) == tuple(b[1:])
+    out: List[Tuple[Optional[int], int]] = [(None, 0)] * len(layouts)
+    groups: List[List[int]] = []
+    for k, lay in enumerate(layouts):
+        if not lay:
+            continue
+        for g in groups:
+            if same(layouts[g[0]][0], lay[0]):
+                g.append(k)
+                break
+        else:
+            groups.append([k])
+    for g in groups:
+        if len(g) < 2:
+            continue
+        lead, T = layouts[g[0]], 0
+        for i, run in enumerate(lead):
+            if all(i < len(layouts[k]) and same(run, layouts[k][i]) for k in g[1:]):
+                T += int(run[1])
+            else:
+                break
+        if T >= max(1, min_rows):
+            for k in g:
+                out[k] = (g[0], T)
+    return out
 
 
 class StagedKV(Sequence):

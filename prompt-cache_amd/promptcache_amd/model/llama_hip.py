@@ -36,7 +36,7 @@ import numpy as np
 
 from .. import _native
 from .config import LlamaShape
-from .kv_arena import KVArena, StagedKV, arena_from_past
+from .kv_arena import KVArena, StagedKV, arena_from_past, common_trunks
 
 _SEG_DTYPE = np.dtype([("src", "<u8"), ("dst_row", "<i4"), ("len", "<i4")])      # pc_kv_seg
 
@@ -275,7 +275,7 @@ class SlotLoop:
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, params=None, seeds=None, histories=None,
-                 stop_ids=(), slots: Optional[int] = None, slot_index=None):
+                 stop_ids=(), slots: Optional[int] = None, slot_index=None, trunks=None):
         n = len(arenas)
         idx = list(range(n)) if slot_index is None else [int(i) for i in slot_index]
         S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= max(idx) + 1)
@@ -289,7 +289,22 @@ class SlotLoop:
             model._tail_done(grown[-1], 0, 1, a.length)       # rows are appended without residuals: a residual tail ends here
         self.arenas = grown
         self.len0 = [a.length for a in grown]
-        self.nsplit = model._slot_nsplit(S, max(self.len0) + max_new + 1)
+        # shared trunks (slot_loop(share_trunk=True)): per sequence (leader index | None, T) -- rows [0, T) of the sequence's arena
+        # are the bytes of the same rows of the leader's, and every step reads them from the leader's arena once for the group
+        self.trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
+        self.nsplit_trunk = 0
+        if any(l is not None for l, _ in self.trunks):
+            for k, (l, T) in enumerate(self.trunks):
+                assert l is None or (self.trunks[l] == (l, T) and 0 < T <= self.len0[k] and T <= self.len0[l]), (k, self.trunks)
+            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1":
+                for k, (l, T) in enumerate(self.trunks):
+                    if l is not None and l != k and not torch.equal(grown[k].buf[:, :, :, :, :T], grown[l].buf[:, :, :, :, :T]):
+                        raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of sequence {k} differ from its trunk leader's "
+                                           f"(sequence {l})")
+            self.nsplit_trunk = model._slot_nsplit(len({l for l, _ in self.trunks if l is not None}), max(T for _, T in self.trunks))
+            self.nsplit = model._slot_nsplit(S, max(l0 - T for l0, (_, T) in zip(self.len0, self.trunks)) + max_new + 1)
+        else:
+            self.nsplit = model._slot_nsplit(S, max(self.len0) + max_new + 1)
         st = self.st = model._slot_state(S)
         model._live_loop = self
         self.sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
@@ -308,6 +323,9 @@ class SlotLoop:
         st["pos"].copy_(col(positions, torch.int32), non_blocking=True)
         st["ids"].copy_(col(tokens, torch.int64), non_blocking=True)
         st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
+        if self.nsplit_trunk:
+            st["leader"].copy_(col([-1 if l is None else idx[l] for l, _ in self.trunks], torch.int32, -1), non_blocking=True)
+            st["trunk"].copy_(col([T for _, T in self.trunks], torch.int32), non_blocking=True)
         st["budget"].copy_(col([max_new] * n, torch.int32), non_blocking=True)
         st["ctr"].fill_(self.ctr0)
         st["stop"].copy_(torch.tensor(list(stop_ids) + [-1] * (8 - len(stop_ids)), dtype=torch.int32), non_blocking=True)
@@ -340,7 +358,7 @@ class SlotLoop:
         if getattr(m, "_live_loop", None) is not self:
             raise RuntimeError("SlotLoop: another device loop on this model took over (one device-side generation per model "
                                "at a time)")
-        g = m._slot_graph(self.S, self.nsplit)
+        g = m._slot_graph(self.S, self.nsplit, self.nsplit_trunk)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         g.replay()
@@ -1634,12 +1652,16 @@ class LlamaHIP:
                     not self.use_chain and self.D in (64, 128) and self.batch_invariant)
 
     def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
-                  slots: Optional[int] = None, slot_index=None) -> Optional["SlotLoop"]:
+                  slots: Optional[int] = None, slot_index=None, share_trunk: bool = False,
+                  min_trunk: Optional[int] = None) -> Optional["SlotLoop"]:
         """A batched device-side decode loop over the arenas behind ``pasts`` (one ``past_key_values`` per sequence, each a
         batch-1 arena of its own): sequence k feeds ``tokens[k]`` at position ``positions[k]`` next.  ``params`` None or plain
         greedy: argmax; otherwise the sampled chain with ``seeds[k]`` (the stream continues at step 1) and ``histories[k]``.
         ``stop_ids``: up to 8 token ids that end a sequence on the device.  None where no batched loop is available -- the
-        caller then decodes the sequences one after another."""
+        caller then decodes the sequences one after another.  ``share_trunk``: sequences whose arenas staged the same leading
+        module rows (``kv_arena.common_trunks`` over ``KVArena.layout``; at least ``min_trunk`` rows, default
+        ``PC_SLOT_TRUNK_MIN`` = 256) read those rows from one arena, once per step for the whole group
+        (``pc_attn_decode_slots_trunk``); a batch without such a group runs the unshared step, bit for bit."""
         if not self.slot_loop_available() or not 1 <= len(pasts) <= SlotLoop.MAX_SLOTS or len(stop_ids) > 8:
             return None
         arenas = []
@@ -1649,7 +1671,8 @@ class LlamaHIP:
                 return None
             a.materialize()                       # (a staging no forward carried out yet)
             arenas.append(a)
-        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index)
+        trunks = common_trunks([a.layout for a in arenas], min_trunk) if share_trunk else None
+        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks)
 
     def _slot_nsplit(self, S: int, max_keys: int) -> int:
         """Splits of the key axis of pc_attn_decode_slots: enough workgroups to cover the chip at S slots, at least 256 keys
@@ -1670,7 +1693,8 @@ class LlamaHIP:
             dev, V = self.device, self.config.vocab_size
             z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)
             st = dict(kv_base=z(S, torch.int64), cap=z(S, torch.int32), len=z(S, torch.int32), pos=z(S, torch.int32),
-                      ids=z(S, torch.int64), live=z(S, torch.int32), budget=z(S, torch.int32), ctr=z(S, torch.int32),
+                      ids=z(S, torch.int64), live=z(S, torch.int32), leader=torch.full((S,), -1, dtype=torch.int32, device=dev),
+                      trunk=z(S, torch.int32), budget=z(S, torch.int32), ctr=z(S, torch.int32),
                       stop=torch.full((8,), -1, dtype=torch.int32, device=dev), seeds=z(S, torch.int64),
                       ring=z(S * SlotLoop.RING, torch.int32),
                       params=z(ctypes.sizeof(_native.SampleParams), torch.uint8), hist=z((S, (V + 31) // 32), torch.int32),
@@ -1678,10 +1702,11 @@ class LlamaHIP:
             sts[S] = st
         return st
 
-    def _slot_graph(self, S: int, nsplit: int):
+    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0):
         """The captured S-slot decode step.  Everything that changes from step to step or from batch to batch -- arena
-        addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch."""
-        key = ("slots", S, nsplit)
+        addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch.
+        ``nsplit_trunk`` > 0: the step with shared trunks; which slots share what is device data as well (leader / trunk)."""
+        key = ("slots", S, nsplit, "trunk", nsplit_trunk) if nsplit_trunk else ("slots", S, nsplit)
         g = self._graphs.pop(key, None)
         if g is not None:
             self._graphs[key] = g
@@ -1693,17 +1718,17 @@ class LlamaHIP:
         # advances nothing, the live words are put back behind it
         live = st["live"].clone()
         st["live"].zero_()
-        self._forward_slots(st, S, nsplit)
+        self._forward_slots(st, S, nsplit, nsplit_trunk)
         torch.cuda.synchronize()
         prime_graph_capture(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._forward_slots(st, S, nsplit)
+            self._forward_slots(st, S, nsplit, nsplit_trunk)
         st["live"].copy_(live)
         self._graphs[key] = g
         return g
 
-    def _forward_slots(self, st: dict, S: int, nsplit: int) -> None:
+    def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0) -> None:
         """One decode step over S slots: the <= 16-row projections of ``_layers_norm_fused`` around per-slot RoPE + append
         and attention; logits to ``st["logits"]``, then the advance launch."""
         n = _native
@@ -1718,7 +1743,9 @@ class LlamaHIP:
         qkv = torch.empty((S, W), dtype=torch.float32, device=dev)
         q16 = torch.zeros((S, H * D), dtype=self.dtype, device=dev)
         q16l = torch.zeros((S, H * D), dtype=self.dtype, device=dev)
-        ws = torch.empty(max(n.attn_decode_slots_workspace_bytes(S, H, D, nsplit), 8) // 4, dtype=torch.float32, device=dev)
+        ws_bytes = (n.attn_decode_slots_trunk_workspace_bytes(S, H, D, nsplit, nsplit_trunk) if nsplit_trunk
+                    else n.attn_decode_slots_workspace_bytes(S, H, D, nsplit))
+        ws = torch.empty(max(ws_bytes, 8) // 4, dtype=torch.float32, device=dev)
 
         def planes(k):          # (zeroed: rows of idle slots are never written and must not hold NaN bit patterns)
             return (torch.zeros((1, k // 32, 64, 8), dtype=self.dtype, device=dev),
@@ -1729,8 +1756,12 @@ class LlamaHIP:
         for li, lw in enumerate(self.layers):
             n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
             n.rope_append_slots(qkv, W, 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D)
-            n.attn_decode_slots(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
-                                self.softmax_scale, nsplit, ws, (ah, al))
+            if nsplit_trunk:
+                n.attn_decode_slots_trunk(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], st["leader"],
+                                          st["trunk"], S, li, H, Hkv, D, self.softmax_scale, nsplit, nsplit_trunk, ws, (ah, al))
+            else:
+                n.attn_decode_slots(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
+                                    self.softmax_scale, nsplit, ws, (ah, al))
             n.gemm_skinny(lw["wo_f"], ah, al, S, hid, H * D, n.EPI_ADD, y=x, ldy=hid)                  # x += attn @ Wo^T
             n.gemm_skinny_norm(lw["wgu_f"], x, lw["ln2"], eps, S, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
             if ks_down:

@@ -6,6 +6,9 @@ B (W + K) / (W + B K) from the weight bytes W a decode step streams and the K/V 
 
     python tools/batch_decode_bench.py [--new 64] [--out profiles/r09_batch_decode.json]
     python tools/batch_decode_bench.py --only-batch 8        # (b) at B = 8 alone: the run to put under rocprofv3 --kernel-trace --stats
+    python tools/batch_decode_bench.py --share-trunk [--out profiles/r10_trunk_decode.json]
+        # (c) as well: generate_batch(share_trunk=True), interleaved with (a) and (b) in the same process, next to the extended
+        # byte model B (W + K) / (W + K_t + B K_o) (K_t: the shared staged rows, read once; K_o: a sequence's own rows)
 """
 import argparse
 import json
@@ -37,11 +40,12 @@ def serial_rate(ge, eng, prompt, params, B):
     return n / dt
 
 
-def batch_rate(ge, eng, prompt, params, B):
-    """(b): one generate_batch over B slots; decode seconds = the last first-token Output (all prefills done) to the end."""
+def batch_rate(ge, eng, prompt, params, B, share=False):
+    """(b): one generate_batch over B slots; decode seconds = the last first-token Output (all prefills done) to the end.
+    (c): the same with ``share_trunk=True``."""
     reqs = [eng.process(prompt, slot=k) for k in range(B)]
     firsts, t0 = 0, None
-    for _k, _out in ge.generate_batch([(r[0], r[1], r[3]) for r in reqs], params, stream_interval=10 ** 9):
+    for _k, _out in ge.generate_batch([(r[0], r[1], r[3]) for r in reqs], params, stream_interval=10 ** 9, share_trunk=share):
         firsts += 1
         if firsts == B:
             t0 = time.perf_counter()
@@ -55,6 +59,7 @@ def main():
     ap.add_argument("--batches", default="1,2,4,8,16")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--only-batch", type=int, default=0, help="run (b) at this B alone, twice (warm + one), and print its rate")
+    ap.add_argument("--share-trunk", action="store_true", help="add leg (c): generate_batch(share_trunk=True)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "batch_decode_bench measures on the GPU"
@@ -69,8 +74,11 @@ def main():
     params = GenerationParameters(temperature=0.0, max_new_tokens=args.new, stop_token_ids=[], stop_str=[])
     assert ge.batch_plan(max(batches), params)[0], ge.batch_plan(max(batches), params)[1]
     if args.only_batch:
-        batch_rate(ge, eng, prompt, params, args.only_batch)
-        print(json.dumps({"B": args.only_batch, "batch_tok_s": round(batch_rate(ge, eng, prompt, params, args.only_batch), 1)}))
+        batch_rate(ge, eng, prompt, params, args.only_batch, args.share_trunk)
+        row = {"B": args.only_batch, "batch_tok_s": round(batch_rate(ge, eng, prompt, params, args.only_batch, args.share_trunk), 1)}
+        if args.share_trunk:
+            row["share_trunk"] = True
+        print(json.dumps(row))
         return
 
     m, c = lm.hf_model, lm.hf_model.config
@@ -83,20 +91,33 @@ def main():
     result = {"shape": "llama2-7b (random init)", "prompt": f"persona schema, {staged} staged + {len(ids)} new tokens", "new_tokens": args.new,
               "how": "greedy; decode tok/s summed over sequences, prefills excluded; (a) B x generate one after another, (b) generate_batch; "
                      f"{args.repeats} interleaved repetitions, median", "weight_bytes": W, "kv_bytes_per_sequence": K, "rows": {}}
+    Kt = 2 * m.L * 2 * m.Hkv * m.D * staged                                    # the rows every slot staged: one trunk
     for B in batches:                                                          # warm: graphs captured, code objects loaded
         batch_rate(ge, eng, prompt, params, B)
+        if args.share_trunk:
+            batch_rate(ge, eng, prompt, params, B, True)
     serial_rate(ge, eng, prompt, params, 1)
     a = {B: [] for B in batches}
     b = {B: [] for B in batches}
+    sh = {B: [] for B in batches}
     for _ in range(args.repeats):
         for B in batches:
             a[B].append(serial_rate(ge, eng, prompt, params, B))
             b[B].append(batch_rate(ge, eng, prompt, params, B))
+            if args.share_trunk:
+                sh[B].append(batch_rate(ge, eng, prompt, params, B, True))
     for B in batches:
         ra, rb = statistics.median(a[B]), statistics.median(b[B])
         model = B * (W + K) / (W + B * K)
         result["rows"][str(B)] = {"serial_tok_s": round(ra, 1), "batch_tok_s": round(rb, 1), "batch_over_serial": round(rb / ra, 3),
                                   "byte_model_ratio": round(model, 3), "fraction_of_byte_model": round(rb / ra / model, 3)}
+        if args.share_trunk:
+            rs = statistics.median(sh[B])
+            model_s = B * (W + K) / (W + Kt + B * (K - Kt)) if B > 1 else 1.0
+            result["rows"][str(B)].update({"shared_tok_s": round(rs, 1), "shared_over_serial": round(rs / ra, 3),
+                                           "shared_over_unshared": round(rs / rb, 3), "trunk_byte_model_ratio": round(model_s, 3)})
+    if args.share_trunk:
+        result["trunk_bytes"] = Kt
     if "8" in result["rows"]:
         result["bar_met_at_B8"] = result["rows"]["8"]["fraction_of_byte_model"] >= 0.5
     line = json.dumps(result)
