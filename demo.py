@@ -40,6 +40,9 @@ def main():
                     help="also decode N copies of the prompt with different questions together (generate_batch; N <= 16)")
     ap.add_argument("--share-trunk", action="store_true",
                     help="with --batch: read the module rows the N prompts have in common once per step for all of them")
+    ap.add_argument("--serve", type=int, default=0,
+                    help="serve N prompts with mixed max_new_tokens through --batch slots (continuous batching: a finished "
+                         "sequence's slot takes the next prompt while the others keep decoding)")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
@@ -96,6 +99,34 @@ def main():
         n_tok = a.batch * a.max_new_tokens               # (fewer where a stop token or stop string ended a sequence early)
         print(f"batch of {a.batch} ({'one device loop' if batched else 'one after another: ' + why}): up to {n_tok} tokens in "
               f"{dt * 1e3:8.2f} ms, prefills included: {n_tok / dt:8.1f} tokens/s aggregate")
+        print("Assistant[0]:", lasts[0].new_text[:120] + " ...")
+    if a.serve:
+        import dataclasses
+        import time
+        cut = prompt_text.rfind("</prompt>")
+        budgets = [max(2, a.max_new_tokens // d) for d in (4, 1, 2, 8)]
+
+        def stream():                                 # (lazy: a prompt is pulled when a slot is free)
+            for r in range(a.serve):
+                pr = Prompt(prompt_text[:cut] + f"<user>{synth.words(4 + r % 5, 5000 + r)}</user>" + prompt_text[cut:], preproc)
+                yield pr, dataclasses.replace(params, max_new_tokens=budgets[r % len(budgets)])
+        batched, why = gen_engine.serve_plan()
+        for _pass in ("warm", "timed"):
+            lasts = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk):
+                lasts[r] = out
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+        if batched:
+            n_tok = sum(len(t) for t in gen_engine.last_serve_tokens.values())
+            st = gen_engine.last_serve_stats
+            print(f"served {a.serve} prompts through {cache_engine.slots} slots: {n_tok} tokens in {dt * 1e3:8.2f} ms, prefills included: "
+                  f"{n_tok / dt:8.1f} tokens/s aggregate, {st['replays']} replays, "
+                  f"{1.0 - st['live_rows'] / max(1, st['replays'] * cache_engine.slots):.2f} of the rows idle")
+        else:
+            print(f"served {a.serve} prompts one after another ({why}) in {dt * 1e3:8.2f} ms")
         print("Assistant[0]:", lasts[0].new_text[:120] + " ...")
 
 

@@ -661,6 +661,51 @@ int pc_sample_advance_slots(const float* logits, int64_t logits_row_stride, int3
                             const int32_t* cap, int32_t* live, int32_t* budget, const int32_t* stop_ids, int32_t* ring,
                             int32_t* counters, int32_t ring_cap, int32_t S, float* processed_out, void* stream);
 
+/* pc_sample_advance_slots_each -- pc_sample_advance_slots with the sampling state PER SLOT (continuous batching: sequences with
+ * different parameters share a step, and a sequence admitted into a running loop keeps the random stream it would have had
+ * alone).  params_dev: pc_sample_params[S], slot b uses block b (a block in greedy mode -- temperature < 1e-5 or top_p < 1e-8 --
+ * takes the argmax, lowest index among equal maxima); stop_ids: int32 [S][8], row b for slot b (unused entries: -1); draws:
+ * int32 [S], the Philox step of slot b's stream (used where pc_sample_advance_slots uses counters[b]; draws[b] += 1 per draw);
+ * counters[b] keeps its ring role only: ring[b * ring_cap + counters[b] % ring_cap] = token, counters[b] += 1.  Everything else
+ * -- idle slots, full arenas, budget, history bitmap, processed_out, argument checks -- is pc_sample_advance_slots' contract.
+ * With S equal blocks, S equal stop rows and draws == counters every output word equals pc_sample_advance_slots' bit for bit. */
+int pc_sample_advance_slots_each(const float* logits, int64_t logits_row_stride, int32_t vocab, const pc_sample_params* params_dev,
+                                 const uint64_t* seeds, uint32_t* history_bits, int64_t* ids, int32_t* pos, int32_t* len,
+                                 const int32_t* cap, int32_t* live, int32_t* budget, const int32_t* stop_ids, int32_t* ring,
+                                 int32_t* counters, int32_t* draws, int32_t ring_cap, int32_t S, float* processed_out, void* stream);
+
+/* pc_slot_arm -- admission of ONE sequence into a running slot loop: one launch writes every state word of slot `slot` (and its
+ * history bitmap row) from a pinned host block, read with system-scope loads (pc_fetch_block's rule); live[slot] = 1 is the last
+ * store.  The launch is ordered on `stream` behind the replays already enqueued: they saw the old words, later ones see the new
+ * sequence.  No word or bitmap row of another slot is touched.  The block is pc_slot_arm_block followed by hist_words uint32 of
+ * history bitmap; nbytes = sizeof(pc_slot_arm_block) + 4 * hist_words rounded up to a multiple of 8.  hist_words is the row length
+ * of state->history_bits (ceil(vocab / 32)).  The host must not rewrite a block before its launch has finished. */
+typedef struct pc_slot_arm_block {
+    int32_t slot;                /* which of the S slots */
+    int32_t cap;                 /* rows per plane of the arena */
+    uint64_t kv_base;            /* address of the arena */
+    int32_t len;                 /* rows the arena holds */
+    int32_t pos;                 /* position id of the token fed next */
+    int64_t id;                  /* that token */
+    int32_t leader;              /* shared trunk: leading slot, -1: on its own */
+    int32_t trunk;               /* shared rows */
+    int32_t budget;              /* steps left */
+    int32_t counter;             /* ring counter (the loop's, so that ring rows line up across slots) */
+    int32_t draws;               /* Philox step of the sequence's own stream */
+    int32_t hist_words;          /* uint32 words of history bitmap behind the struct */
+    uint64_t seed;
+    pc_sample_params params;
+    int32_t stop_ids[8];         /* unused entries: -1 */
+} pc_slot_arm_block;
+
+typedef struct pc_slot_state {   /* the S-slot device arrays of the captured step */
+    uint64_t* kv_base; int32_t* cap; int32_t* len; int32_t* pos; int64_t* ids; int32_t* live; int32_t* leader; int32_t* trunk;
+    int32_t* budget; int32_t* counters; int32_t* draws; uint64_t* seeds; pc_sample_params* params; int32_t* stop_ids;
+    uint32_t* history_bits;
+} pc_slot_state;
+
+int pc_slot_arm(const pc_slot_arm_block* host_block, int32_t nbytes, const pc_slot_state* state, int32_t S, void* stream);
+
 /* Diagnostics used by the GPU test-suite: dumps the MFMA C/D lane map and the LDS transpose-read
  * map the attention kernel relies on (probe_kernel in csrc/pc_misc.hip). */
 /* dev hook (tools/gemm_trace.py): weight-streaming launches issued by this thread stamp per-wave wall-clock times

@@ -444,6 +444,43 @@ __global__ __launch_bounds__(kThreads) void sample_advance_slots_kernel(
     }
 }
 
+// pc_sample_advance_slots_each: sample_advance_slots_kernel with the sampling state per slot -- parameter block b, stop row b and
+// the Philox step draws[b] of slot b's own random stream; ctr[b] only places the token in the ring.  A sequence admitted into a
+// running loop keeps the stream it would have had alone while its ring rows line up with the other slots'.
+__global__ __launch_bounds__(kThreads) void sample_advance_slots_each_kernel(
+    const float* __restrict__ logits, int64_t ldl, int V, const pc_sample_params* __restrict__ prm,
+    const uint64_t* __restrict__ seeds, uint32_t* hist, int64_t* ids, int32_t* pos, int32_t* len, const int32_t* __restrict__ cap,
+    int32_t* live, int32_t* budget, const int32_t* __restrict__ stop_ids, int32_t* ring, int32_t* ctr, int32_t* draws, int ring_cap,
+    float* processed_out) {
+    const int b = blockIdx.x;
+    if (live[b] == 0) return;                          // (uniform over the workgroup)
+    if (len[b] < 0 || len[b] >= cap[b]) {
+        if (threadIdx.x == 0) live[b] = 0;
+        return;
+    }
+    const int hw = (V + 31) >> 5;
+    uint32_t* hb = hist + (int64_t)b * hw;
+    const uint32_t step = (uint32_t)draws[b];
+    const int bi = sample_row(logits + (int64_t)b * ldl, V, prm + b, hb, seeds[b], step, processed_out ? processed_out + (int64_t)b * V : nullptr);
+    if (threadIdx.x == 0) {
+        ids[b] = bi;
+        pos[b] += 1;
+        const int n = len[b] + 1;
+        len[b] = n;
+        const uint32_t c = (uint32_t)ctr[b];
+        ring[(int64_t)b * ring_cap + c % (uint32_t)ring_cap] = bi;
+        ctr[b] = (int32_t)(c + 1u);
+        draws[b] = (int32_t)(step + 1u);
+        hb[bi >> 5] |= 1u << (bi & 31);
+        const int left = budget[b] - 1;
+        budget[b] = left;
+        bool stop = left <= 0 || n + 1 >= cap[b];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) stop |= stop_ids[b * 8 + j] == bi;
+        if (stop) live[b] = 0;
+    }
+}
+
 }  // namespace
 
 PC_EXPORT int pc_sample_advance(const float* logits, int32_t vocab, const pc_sample_params* params_dev, uint32_t* history_bits,
@@ -475,4 +512,22 @@ PC_EXPORT int pc_sample_advance_slots(const float* logits, int64_t logits_row_st
                        vocab, params_dev, seeds, history_bits, ids, pos, len, cap, live, budget, stop_ids, ring, counters, ring_cap,
                        processed_out);
     return pc_check_launch("sample_advance_slots_kernel");
+}
+
+PC_EXPORT int pc_sample_advance_slots_each(const float* logits, int64_t logits_row_stride, int32_t vocab,
+                                           const pc_sample_params* params_dev, const uint64_t* seeds, uint32_t* history_bits,
+                                           int64_t* ids, int32_t* pos, int32_t* len, const int32_t* cap, int32_t* live,
+                                           int32_t* budget, const int32_t* stop_ids, int32_t* ring, int32_t* counters,
+                                           int32_t* draws, int32_t ring_cap, int32_t S, float* processed_out, void* stream) {
+    PC_REQUIRE(logits && params_dev && seeds && history_bits && ids && pos && len && cap && live && budget && stop_ids && ring &&
+                   counters && draws && ring_cap > 0, PC_ERR_ARG, "pc_sample_advance_slots_each: null pointer or bad sizes");
+    PC_REQUIRE(S >= 1 && S <= 16, PC_ERR_ARG, "pc_sample_advance_slots_each: 1 <= S <= 16");
+    PC_REQUIRE(vocab > 0 && vocab < (1 << 24) && logits_row_stride >= vocab, PC_ERR_ARG,
+               "pc_sample_advance_slots_each: vocab must be in [1, 2^24) and the row stride at least vocab");
+    PC_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)params_dev & 7) == 0 && ((uintptr_t)seeds & 7) == 0, PC_ERR_ARG,
+               "pc_sample_advance_slots_each: logits must be 4-byte, params and seeds 8-byte aligned");
+    hipLaunchKernelGGL(sample_advance_slots_each_kernel, dim3(S), dim3(kThreads), 0, (hipStream_t)stream, logits, logits_row_stride,
+                       vocab, params_dev, seeds, history_bits, ids, pos, len, cap, live, budget, stop_ids, ring, counters, draws,
+                       ring_cap, processed_out);
+    return pc_check_launch("sample_advance_slots_each_kernel");
 }

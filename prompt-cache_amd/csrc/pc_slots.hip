@@ -567,6 +567,49 @@ void launch_trunk_d(const TrunkArgs& a, hipStream_t st) {
                        a.leader, a.trunk, a.kv_base, a.S, a.H, a.ns_trunk, nrec, a.of_hi, a.of_lo);
 }
 
+// ---- pc_slot_arm: every state word of ONE slot from a pinned host block, one launch ---------------------------------------
+// Admission into a running loop: the launch sits on the stream between two replays of the captured step, so the replays before
+// it saw the slot's old words (idle) and the replays behind it see the new sequence.  The block is host memory the host rewrites
+// between admissions: system-scope loads (pc_fetch_block's rule), never a device cache.  One workgroup: the header goes through
+// LDS, the history bitmap row (ceil(V / 32) words, 1 000 at V = 32 000) is copied by all threads, live[slot] = 1 is the last store.
+constexpr int kArmWords = (int)(sizeof(pc_slot_arm_block) / 8);
+
+__global__ __launch_bounds__(kThreads) void slot_arm_kernel(const unsigned long long* __restrict__ src, pc_slot_state st, int S, int hw) {
+    typedef __attribute__((address_space(1))) unsigned long long g64;
+    __shared__ __attribute__((aligned(8))) unsigned long long h[kArmWords];
+    const int tid = threadIdx.x;
+    if (tid < kArmWords) h[tid] = __hip_atomic_load((g64*)(src + tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __syncthreads();
+    const pc_slot_arm_block& b = *(const pc_slot_arm_block*)h;
+    const int s = b.slot;
+    if (s < 0 || s >= S || b.hist_words != hw) return;          // (the block changed under the launch: touch nothing)
+    uint32_t* row = st.history_bits + (int64_t)s * hw;
+    for (int i = tid; 2 * i < hw; i += kThreads) {
+        const unsigned long long w = __hip_atomic_load((g64*)(src + kArmWords + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        row[2 * i] = (uint32_t)w;
+        if (2 * i + 1 < hw) row[2 * i + 1] = (uint32_t)(w >> 32);
+    }
+    if (tid == 0) {
+        st.kv_base[s] = b.kv_base;
+        st.cap[s] = b.cap;
+        st.len[s] = b.len;
+        st.pos[s] = b.pos;
+        st.ids[s] = b.id;
+        st.leader[s] = b.leader;
+        st.trunk[s] = b.trunk;
+        st.budget[s] = b.budget;
+        st.counters[s] = b.counter;
+        st.draws[s] = b.draws;
+        st.seeds[s] = b.seed;
+        st.params[s] = b.params;
+    } else if (tid >= 64 && tid < 72) {
+        st.stop_ids[s * 8 + tid - 64] = b.stop_ids[tid - 64];
+    }
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) st.live[s] = 1;
+}
+
 bool slot_shape_ok(int S, int H, int Hkv, int D) {
     return S >= 1 && S <= 16 && H > 0 && Hkv > 0 && H % Hkv == 0 && (D == 64 || D == 128);
 }
@@ -657,4 +700,22 @@ PC_EXPORT int pc_attn_decode_slots_trunk(const void* q_hi, const void* q_lo, int
     if (D == 128) launch_trunk_d<128>(a, (hipStream_t)stream);
     else launch_trunk_d<64>(a, (hipStream_t)stream);
     return pc_check_launch("attn_trunk_slots_kernel");
+}
+
+PC_EXPORT int pc_slot_arm(const pc_slot_arm_block* host_block, int32_t nbytes, const pc_slot_state* state, int32_t S, void* stream) {
+    PC_REQUIRE(host_block && state, PC_ERR_ARG, "pc_slot_arm: null pointer");
+    PC_REQUIRE(state->kv_base && state->cap && state->len && state->pos && state->ids && state->live && state->leader && state->trunk &&
+                   state->budget && state->counters && state->draws && state->seeds && state->params && state->stop_ids &&
+                   state->history_bits, PC_ERR_ARG, "pc_slot_arm: null pointer in the slot state");
+    PC_REQUIRE(S >= 1 && S <= 16, PC_ERR_ARG, "pc_slot_arm: 1 <= S <= 16");
+    PC_REQUIRE(((uintptr_t)host_block & 7) == 0 && ((uintptr_t)state->params & 7) == 0 && ((uintptr_t)state->seeds & 7) == 0 &&
+                   ((uintptr_t)state->kv_base & 7) == 0 && ((uintptr_t)state->ids & 7) == 0, PC_ERR_ARG,
+               "pc_slot_arm: the block and the 64-bit state arrays must be 8-byte aligned");
+    const int32_t slot = host_block->slot, hw = host_block->hist_words;       // (pinned HOST memory: readable here)
+    PC_REQUIRE(slot >= 0 && slot < S, PC_ERR_ARG, "pc_slot_arm: slot outside [0, S)");
+    PC_REQUIRE(hw >= 1 && hw <= (1 << 19) && (int64_t)nbytes == (int64_t)sizeof(pc_slot_arm_block) + (((int64_t)hw * 4 + 7) & ~(int64_t)7),
+               PC_ERR_ARG, "pc_slot_arm: nbytes must be sizeof(pc_slot_arm_block) + 4 * hist_words rounded up to 8");
+    hipLaunchKernelGGL(slot_arm_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const unsigned long long*)host_block, *state, S,
+                       hw);
+    return pc_check_launch("slot_arm_kernel");
 }

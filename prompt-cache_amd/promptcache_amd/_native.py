@@ -51,6 +51,19 @@ class SampleParams(C.Structure):
     _fields_ = [("temperature", _f32), ("repetition_penalty", _f32), ("top_p", _f32), ("top_k", _i32), ("seed", C.c_uint64)]
 
 
+class SlotArmBlock(C.Structure):
+    """``pc_slot_arm_block``: the header of the pinned host block of pc_slot_arm (``hist_words`` uint32 of bitmap follow)."""
+    _fields_ = [("slot", _i32), ("cap", _i32), ("kv_base", C.c_uint64), ("len", _i32), ("pos", _i32), ("id", _i64),
+                ("leader", _i32), ("trunk", _i32), ("budget", _i32), ("counter", _i32), ("draws", _i32), ("hist_words", _i32),
+                ("seed", C.c_uint64), ("params", SampleParams), ("stop_ids", _i32 * 8)]
+
+
+class SlotState(C.Structure):
+    """``pc_slot_state``: the S-slot device arrays pc_slot_arm writes into."""
+    _fields_ = [(f, _vp) for f in ("kv_base", "cap", "len", "pos", "ids", "live", "leader", "trunk", "budget", "counters", "draws",
+                                   "seeds", "params", "stop_ids", "history_bits")]
+
+
 KV_ROW_STAGED = 1
 KV_ROW_TABLE_MAX_SEG = 1024
 
@@ -161,6 +174,9 @@ SIGNATURES = {
                                              _vp, _i64, _vp, _vp, _vp]),
     "pc_sample_advance_slots": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                                           _vp, _vp]),
+    "pc_sample_advance_slots_each": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                               _i32, _vp, _vp]),
+    "pc_slot_arm": (C.c_int, [_vp, _i32, C.POINTER(SlotState), _i32, _vp]),
     "pc_quant_act_i8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_rmsnorm_quant_i8": (C.c_int, [_vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_outlier_corr": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -776,6 +792,34 @@ def sample_advance_slots(logits, ldl: int, vocab: int, params, seeds, history, i
                                         budget.data_ptr(), stop_ids.data_ptr(), ring.data_ptr(), counters.data_ptr(), ring_cap, S,
                                         _ptr(processed_out), current_stream() if stream is None else stream)
     check(rc, "pc_sample_advance_slots")
+
+
+def sample_advance_slots_each(logits, ldl: int, vocab: int, params, seeds, history, ids, pos, length, cap, live, budget, stop_ids,
+                              ring, counters, draws, ring_cap: int, S: int, processed_out=None, stream: Optional[int] = None) -> None:
+    """``sample_advance_slots`` with per-slot sampling state (pc_sample_advance_slots_each): ``params`` holds S ``SampleParams``,
+    ``stop_ids`` is int32 [S][8], ``draws`` int32 [S] the Philox step of each slot's stream."""
+    rc = load().pc_sample_advance_slots_each(logits.data_ptr(), ldl, vocab, params.data_ptr(), seeds.data_ptr(), history.data_ptr(),
+                                             ids.data_ptr(), pos.data_ptr(), length.data_ptr(), cap.data_ptr(), live.data_ptr(),
+                                             budget.data_ptr(), stop_ids.data_ptr(), ring.data_ptr(), counters.data_ptr(),
+                                             draws.data_ptr(), ring_cap, S, _ptr(processed_out),
+                                             current_stream() if stream is None else stream)
+    check(rc, "pc_sample_advance_slots_each")
+
+
+def slot_arm_bytes(hist_words: int) -> int:
+    """Bytes of a pc_slot_arm block with ``hist_words`` words of history bitmap."""
+    return C.sizeof(SlotArmBlock) + ((4 * hist_words + 7) & ~7)
+
+
+def slot_state(kv_base, cap, length, pos, ids, live, leader, trunk, budget, counters, draws, seeds, params, stop_ids, history) -> SlotState:
+    return SlotState(*[t.data_ptr() for t in (kv_base, cap, length, pos, ids, live, leader, trunk, budget, counters, draws, seeds,
+                                               params, stop_ids, history)])
+
+
+def slot_arm(host_pinned, nbytes: int, state: SlotState, S: int, stream: Optional[int] = None) -> None:
+    """Write every state word of one slot from the pinned host block ``host_pinned`` (pc_slot_arm), ordered on the stream."""
+    rc = load().pc_slot_arm(host_pinned.data_ptr(), nbytes, C.byref(state), S, current_stream() if stream is None else stream)
+    check(rc, "pc_slot_arm")
 
 
 def sample_params_bytes(temperature: float, repetition_penalty: float, top_p: float, top_k: int, seed: int) -> bytes:

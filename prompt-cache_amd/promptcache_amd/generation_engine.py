@@ -24,6 +24,7 @@ import torch
 
 from .model import LanguageModel
 from .model.kv_arena import StagedKV
+from .slot_scheduler import SlotScheduler, split_stop_ids, wants_look_ahead
 
 
 @dataclass
@@ -347,4 +348,184 @@ class GenerationEngine:
             if loop is not None:
                 loop.close([len(new_ids[k]) - 1 for k in members])
             del pasts, loop
+            gc.collect()
+
+    # -- a stream of requests: continuous batching ------------------------------------------------
+    def serve_plan(self) -> Tuple[bool, str]:
+        """``(batched, reason)``: whether ``serve`` runs its requests through one device loop that admits new prompts as slots
+        free up (``model/llama_hip.py`` SlotLoop, ``each=True``), or one after another through ``generate``, and why.  Host logic
+        only.  Requests carry their own parameters, so both device loops must be on."""
+        hf = getattr(self.lm, "hf_model", None)
+        if getattr(self.lm, "use_full_position_ids", False):
+            return False, "the model takes full position ids (per-key positions are re-based on the host every step)"
+        if not hasattr(hf, "slot_loop") or not hf.slot_loop_available():
+            return False, "the model has no batched decode loop (architecture, int8 weights or PC_DECODE_TAIL=1)"
+        if not self.device_greedy_loop:
+            return False, "PC_DEVICE_GREEDY=0"
+        if not self.device_sample_loop:
+            return False, "PC_DEVICE_SAMPLE=0"
+        return True, "one device loop, new prompts admitted as slots free up"
+
+    @torch.inference_mode()
+    def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
+              share_trunk: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
+        """Continuous batching over ``cache_engine.slots`` slots.  ``requests``: any iterable -- it may be lazy -- of ``Prompt`` or
+        ``(Prompt, GenerationParameters)``; ``params`` is the default for bare prompts.  Requests are numbered in the order they
+        are pulled; yields ``(index, Output)``.  A request is pulled when a slot is free: ``cache_engine.process(prompt, slot=k)``,
+        the prefill and the first token as ``generate_batch`` does them, then the sequence enters the running device loop
+        (``SlotLoop.admit``) at the next replay, with its own sampling parameters, stop ids and budget.  A sequence that ends --
+        stop id, budget, stop string, full arena -- is retired and its slot refilled.  Per sequence the ``Output`` stream, the
+        stop-string handling and the position rule are ``generate``'s; sampled request number r uses seed ``seed + r`` of the one
+        seed taken from torch's default generator.  A request with more than 8 stop ids keeps the first 8 on the device; the
+        host kills the slot for the rest.  ``share_trunk`` (None: ``PC_SLOT_TRUNK``): the first fill is grouped by
+        ``common_trunks``; a later request joins a group whose trunk its staged layout covers; the slot of a group's leader is
+        not refilled while members live.  The split counts of the attention are fixed from the slot buffers' capacity, so a
+        sequence's tokens do not depend on who joins later.  Where ``serve_plan`` says no, the requests run one after another
+        through ``generate``.  Abandoning the generator rewinds every arena.  ``last_serve_stats`` / ``last_serve_trace`` /
+        ``last_serve_tokens``: replays and live rows, the scheduler's trace and the decoded tokens per request of the newest run."""
+        if share_trunk is None:
+            share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
+
+        def unpack(req):
+            if isinstance(req, (tuple, list)):
+                return req[0], (req[1] if req[1] is not None else params)
+            return req, params
+
+        batched, _ = self.serve_plan()
+        if not batched:
+            full = bool(getattr(self.lm, "use_full_position_ids", False))
+            for r, req in enumerate(requests):
+                prompt, p = unpack(req)
+                ids, pos, _, cache = cache_engine.process(prompt, return_full_position_ids=full)
+                for out in self.generate(ids, pos, p, cache, stream_interval, use_full_position_ids=full):
+                    yield r, out
+            return
+
+        hf = self.lm.hf_model
+        S = cache_engine.slots
+        sched = SlotScheduler(S, requests, share_trunk=bool(share_trunk))
+        stats = self.last_serve_stats = dict(replays=0, rows=0, live_rows=0, requests=0)
+        self.last_serve_trace = sched.trace
+        tokens = self.last_serve_tokens = {}          # request index -> the tokens it decoded
+        seq = {}            # slot -> state of the running sequence
+        loop, seed = None, None
+        pending: list = []  # first fill: sequences waiting for the loop to be built
+
+        def first_token(index, slot, req):
+            """process + prefill + first token of a pulled request -> (state, Output | None)."""
+            nonlocal seed
+            prompt, p = unpack(req)
+            if p is None:
+                raise ValueError("serve: a bare prompt needs the default params")
+            ids, pos, _, cache = cache_engine.process(prompt, slot=slot)
+            plain = p.greedy and p.repetition_penalty <= 1.0
+            if not plain and seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)))
+            logits, past, ms = self._forward(list(ids), list(pos), cache)
+            if self.verbose:
+                print(f"Prefill latency: {ms:.2f} ms")
+            st = dict(index=index, slot=slot, p=p, plain=plain, output_ids=list(ids), new_ids=[], total_ms=ms, ttft_ms=ms,
+                      past=past, first_free=max(pos) + 1, last_step=p.max_new_tokens - 1, done=False, k=None,
+                      seed=0 if plain else seed + index)
+            tokens[index] = st["new_ids"]
+            if plain:
+                token = self._pick(p.get_logits_processor()(None, logits[:, -1, :])[0], True)
+            else:
+                token = hf.sample_token(logits[0, -1], p, st["seed"], st["output_ids"])
+            return st, emit(st, 0, token)
+
+        def emit(st, step, token):
+            p = st["p"]
+            st["output_ids"].append(token)
+            st["new_ids"].append(token)
+            fin = token in p.stop_token_ids
+            out = None
+            if step % stream_interval == 0 or step == st["last_step"] or fin:
+                text, new_text, hit, partial = self._render(st["output_ids"], st["new_ids"], p.stop_str)
+                fin = fin or hit
+                if not partial:
+                    out = Output(text, new_text, st["total_ms"], st["ttft_ms"])
+            st["done"] = fin or step >= st["last_step"]
+            return out
+
+        def loop_args(st):
+            return (st["past"], st["new_ids"][-1], st["first_free"] + 1, st["last_step"], None if st["plain"] else st["p"], st["seed"],
+                    st["output_ids"], split_stop_ids(st["p"].stop_token_ids)[0])
+
+        def admit_free_slots():
+            """Pull requests into free slots; sequences with more to decode enter the loop (or wait for it to be built)."""
+            while True:
+                nxt = sched.next_request()
+                if nxt is None:
+                    return
+                index, slot, req = nxt
+                stats["requests"] += 1
+                st, out = first_token(index, slot, req)
+                if out is not None:
+                    yield index, out
+                if st["done"]:
+                    sched.dropped(slot, index, 0 if loop is None else loop.n)
+                    continue
+                if loop is None:
+                    pending.append(st)
+                    sched.started(slot, index, 0)
+                else:
+                    trunk = sched.join(slot, st["past"].arena.layout) if share_trunk and loop.nsplit_trunk else None
+                    st["k"] = loop.admit(slot, *loop_args(st), trunk=trunk)
+                    sched.started(slot, index, loop.n)
+                seq[slot] = st
+
+        try:
+            yield from admit_free_slots()
+            if pending:
+                args = [loop_args(st) for st in pending]
+                slots_ = [st["slot"] for st in pending]
+                trunks = sched.group_first_fill(slots_, [st["past"].arena.layout for st in pending]) if share_trunk else None
+                loop = hf.slot_loop([a[0] for a in args], [a[1] for a in args], [a[2] for a in args], [a[3] for a in args],
+                                    [a[4] for a in args], [a[5] for a in args], [a[6] for a in args], [a[7] for a in args],
+                                    slots=S, slot_index=slots_, each=True, max_keys=cache_engine.max_ctx_length, trunks=trunks)
+                if loop is None:
+                    raise RuntimeError("serve: the model refused a batched decode loop over these caches")
+                for k, st in enumerate(pending):
+                    st["k"] = k
+                pending.clear()
+            i = 0
+            while seq:
+                while loop.n <= i:
+                    loop.enqueue()
+                if loop.n == i + 1 and wants_look_ahead(
+                        [(loop._start[st["k"]], st["last_step"] - max(0, i - loop._start[st["k"]])) for st in seq.values()], i):
+                    loop.enqueue()                                 # the replay AFTER the one whose tokens are read below
+                ms = loop.elapsed_ms(i)
+                stats["rows"] += S
+                for slot in sorted(seq):
+                    st = seq[slot]
+                    if loop._start[st["k"]] > i:
+                        continue
+                    token = loop.token(st["k"], i)
+                    out = None
+                    if token is None:                              # (the device switched the slot off: its arena is full)
+                        st["done"] = True
+                    else:
+                        stats["live_rows"] += 1
+                        st["total_ms"] += ms
+                        step = i - loop._start[st["k"]] + 1
+                        out = emit(st, step, token)
+                        if st["done"] and token not in split_stop_ids(st["p"].stop_token_ids)[0] and step != st["last_step"]:
+                            loop.kill(st["k"])                     # a stop string or a stop id past the first 8: the device cannot know
+                    if st["done"]:
+                        loop.retire(st["k"], len(st["new_ids"]) - 1)
+                        del seq[slot]
+                        st["past"] = None
+                        sched.finished(slot, i)
+                    if out is not None:
+                        yield st["index"], out
+                yield from admit_free_slots()
+                i += 1
+        finally:
+            # also when the consumer abandons the generator at a yield: every arena's length goes back to what was consumed
+            if loop is not None:
+                stats["replays"] = loop.n
+                loop.close({st["k"]: len(st["new_ids"]) - 1 for st in seq.values() if st["k"] is not None})
+            del seq, loop, pending
             gc.collect()

@@ -275,11 +275,16 @@ class SlotLoop:
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, params=None, seeds=None, histories=None,
-                 stop_ids=(), slots: Optional[int] = None, slot_index=None, trunks=None):
+                 stop_ids=(), slots: Optional[int] = None, slot_index=None, trunks=None, each: bool = False,
+                 max_keys: Optional[int] = None):
         n = len(arenas)
         idx = list(range(n)) if slot_index is None else [int(i) for i in slot_index]
         S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= max(idx) + 1)
         assert 1 <= n and len(set(idx)) == n and 0 <= min(idx) and max(idx) < S <= self.MAX_SLOTS, (n, idx, S)
+        self.each = bool(each)
+        if each:
+            self._init_each(model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, S, idx, trunks, max_keys)
+            return
         assert len(tokens) == n and len(positions) == n and len(stop_ids) <= 8 and max_new >= 1
         self.m, self.S, self.idx, self.max_new = model, S, idx, max_new
         grown = []
@@ -305,6 +310,10 @@ class SlotLoop:
             self.nsplit = model._slot_nsplit(S, max(l0 - T for l0, (_, T) in zip(self.len0, self.trunks)) + max_new + 1)
         else:
             self.nsplit = model._slot_nsplit(S, max(self.len0) + max_new + 1)
+        if max_keys is not None:                          # split counts from the caller's bound, not from this batch
+            self.nsplit = model._slot_nsplit(S, int(max_keys))
+            if self.nsplit_trunk:
+                self.nsplit_trunk = model._slot_nsplit(1, int(max_keys))
         st = self.st = model._slot_state(S)
         model._live_loop = self
         self.sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
@@ -343,14 +352,162 @@ class SlotLoop:
         self.stop_ids = set(int(t) for t in stop_ids)
         self.logits = st["logits"]
         self.n = 0
-        self.events = []
+        self.events = {}                  # step -> (start, end, tokens on the host); steps the ring no longer holds are dropped
         self.host = torch.empty((self.RING, S), dtype=torch.int32, pin_memory=True)
         self._ring2d = st["ring"].view(S, self.RING)
         self._alive = [True] * n          # host mirror of the live words, after the newest step whose tokens were looked at
         self._seen = 0                    # steps whose tokens the mirror has taken in
         self._last = [-1] * n             # index of the last step that produced a token for sequence k (-1: none yet)
         self._killed = [None] * n         # step count at which kill(k) took effect
+        self._start = [0] * n             # the replay at which sequence k entered the loop
+        self._max_new = [max_new] * n
+        self._stops = [self.stop_ids] * n
+        self._active = list(range(n))     # sequences the mirror still follows
+        self._retired = set()
         torch.cuda.current_stream().synchronize()        # (the pageable sources of the copies above may go now)
+
+    # ---- per-slot sampling state and admission (each=True) ---------------------------------------------------------------
+    def _init_each(self, model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, S, idx, trunks, max_keys):
+        """The loop over ``pc_sample_advance_slots_each``: every initial sequence enters through ``admit``'s path, at replay 0.
+        ``max_new`` / ``params`` / ``stop_ids``: one value for all sequences or a list with one per sequence."""
+        n = len(arenas)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+        max_news, paramss = per(max_new), per(params)
+        stops = list(stop_ids) if len(stop_ids) and isinstance(stop_ids[0], (list, tuple)) else [tuple(stop_ids)] * n
+        assert len(tokens) == n and len(positions) == n and len(max_news) == n and len(paramss) == n and len(stops) == n
+        self.m, self.S, self.idx, self.max_new = model, S, [], max(max_news)
+        self.arenas, self.len0, self.trunks = [], [], []
+        trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
+        shared = any(l is not None for l, _ in trunks)
+        for k, (l, T) in enumerate(trunks):
+            assert l is None or (trunks[l] == (l, T) and 0 < T <= arenas[k].length and T <= arenas[l].length), (k, trunks)
+        if max_keys is None:
+            max_keys = max(a.length + mn for a, mn in zip(arenas, max_news)) + 1
+        self.nsplit = model._slot_nsplit(S, int(max_keys))
+        self.nsplit_trunk = model._slot_nsplit(1, int(max_keys)) if shared else 0
+        st = self.st = model._slot_state(S)
+        model._live_loop = self
+        self.sampled, self.ctr0 = True, 0      # (ring-only counters; every stream drew its first token at step 0: draws start at 1)
+        self.stop_ids = set()
+        st["live"].zero_()
+        st["leader"].fill_(-1)
+        st["trunk"].zero_()
+        self.logits = st["logits"]
+        self.n = 0
+        self.events = {}
+        self.host = torch.empty((self.RING, S), dtype=torch.int32, pin_memory=True)
+        self._ring2d = st["ring"].view(S, self.RING)
+        self._alive, self._last, self._killed, self._start, self._max_new, self._stops = [], [], [], [], [], []
+        self._seen, self._active = 0, []
+        self._slot_seq = [None] * S            # the newest sequence of every slot
+        self._retired = set()
+        hw = (model.config.vocab_size + 31) // 32
+        self._arm_bytes = _native.slot_arm_bytes(hw)
+        self._arm_ring = [[torch.zeros(self._arm_bytes, dtype=torch.uint8, pin_memory=True), torch.cuda.Event(), False] for _ in range(4)]
+        self._arm_next = 0
+        self._arm_state = _native.slot_state(st["kv_base"], st["cap"], st["len"], st["pos"], st["ids"], st["live"], st["leader"],
+                                             st["trunk"], st["budget"], st["ctr"], st["draws"], st["seeds"], st["params_each"],
+                                             st["stop_each"], st["hist"])
+        seeds = [0] * n if seeds is None else list(seeds)
+        histories = [()] * n if histories is None else list(histories)
+        for k in range(n):
+            l, T = trunks[k]
+            self._admit(idx[k], arenas[k], tokens[k], positions[k], max_news[k], paramss[k], seeds[k], histories[k], stops[k],
+                        None if l is None else (idx[l], T))
+
+    @torch.inference_mode()
+    def admit(self, slot_index: int, past, token: int, position: int, max_new: int, params, seed: int, history, stop_ids,
+              trunk=None) -> int:
+        """A new sequence into slot ``slot_index`` of a running ``each=True`` loop, from the next replay on: the arena behind ``past``
+        feeds ``token`` at ``position`` for at most ``max_new`` steps, with its own ``params`` (None / plain greedy: argmax), random
+        stream ``seed`` (continuing at step 1), ``history`` ids and up to 8 ``stop_ids``.  ``trunk = (leader slot, T)``: rows [0, T) are
+        read from the arena of that slot.  Only legal when the slot's previous sequence is over on the host mirror (stopped, out of
+        budget or killed) and was retired.  -> the new sequence's index."""
+        if not self.each:
+            raise RuntimeError("SlotLoop.admit needs a loop built with each=True")
+        a = self.m._loop_arena(past)
+        if a is None:
+            raise RuntimeError("SlotLoop.admit: the cache is not a staged batch-1 arena")
+        return self._admit(int(slot_index), a, token, position, max_new, params, seed, history, stop_ids, trunk)
+
+    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, trunk) -> int:
+        m, st = self.m, self.st
+        if getattr(m, "_live_loop", None) is not self:
+            raise RuntimeError("SlotLoop: another device loop on this model took over")
+        if not 0 <= s < self.S or max_new < 1:
+            raise ValueError(f"SlotLoop.admit: slot {s} outside [0, {self.S}) or max_new < 1")
+        prev = self._slot_seq[s]
+        if prev is not None:
+            if self._alive[prev] and self._killed[prev] is None:
+                raise RuntimeError(f"SlotLoop.admit: the sequence in slot {s} is still running")
+            self._alive[prev] = False
+            if prev in self._active:
+                self._active.remove(prev)
+        if any(a is self.arenas[k] for k in self._active):
+            raise RuntimeError("SlotLoop.admit: the arena belongs to a running sequence")
+        a.materialize()
+        need = a.length + max_new + 2
+        if need > a.cap:
+            a = a.grown(max(need, 2 * a.cap))
+        m._tail_done(a, 0, 1, a.length)
+        leader, T = (-1, 0) if trunk is None else (int(trunk[0]), int(trunk[1]))
+        if leader >= 0:
+            lead = self._slot_seq[leader] if leader != s else None
+            la = a if leader == s else (None if lead is None else self.arenas[lead])
+            if not self.nsplit_trunk or la is None or not 0 < T <= a.length or T > la.cap:
+                raise ValueError(f"SlotLoop.admit: no trunk of {T} rows led by slot {leader} in this loop")
+            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1" and la is not a and \
+                    not torch.equal(a.buf[:, :, :, :, :T], la.buf[:, :, :, :, :T]):
+                raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of the sequence for slot {s} differ from its trunk leader's "
+                                   f"(slot {leader})")
+        stop_ids = [int(t) for t in stop_ids]
+        assert len(stop_ids) <= 8, "at most 8 stop ids live on the device (the host kills for the rest)"
+        sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
+        blk_p = sample_params_block(params, 0) if sampled else _native.sample_params_bytes(0.0, 1.0, 1.0, -1, 0)
+        V = m.config.vocab_size
+        hw = (V + 31) // 32
+        # the next pinned block of the ring, once the launch that read it last has finished
+        ent = self._arm_ring[self._arm_next]
+        self._arm_next = (self._arm_next + 1) % len(self._arm_ring)
+        if ent[2]:
+            ent[1].synchronize()
+        arr = ent[0].numpy()
+        b = _native.SlotArmBlock.from_buffer(arr)
+        b.slot, b.cap, b.kv_base, b.len, b.pos, b.id = s, a.cap, a.buf.data_ptr(), a.length, int(position), int(token)
+        b.leader, b.trunk, b.budget, b.counter, b.draws, b.hist_words = leader, T, int(max_new), self.ctr0 + self.n, 1, hw
+        b.seed = int(seed) & (2 ** 63 - 1)
+        b.params = _native.SampleParams.from_buffer_copy(blk_p)
+        for j in range(8):
+            b.stop_ids[j] = stop_ids[j] if j < len(stop_ids) else -1
+        hb = arr[ctypes.sizeof(_native.SlotArmBlock):ctypes.sizeof(_native.SlotArmBlock) + 4 * hw].view(np.int32)
+        if sampled:
+            hb[:] = _history_bits(history, V).numpy()
+        else:
+            hb[:] = 0
+        del b
+        _native.slot_arm(ent[0], self._arm_bytes, self._arm_state, self.S)
+        ent[1].record()
+        ent[2] = True
+        k = len(self.arenas)
+        self.arenas.append(a)
+        self.len0.append(a.length)
+        self.idx.append(s)
+        self.trunks.append((None, 0) if leader < 0 else (leader, T))
+        self._alive.append(True)
+        self._last.append(-1)
+        self._killed.append(None)
+        self._start.append(self.n)
+        self._max_new.append(int(max_new))
+        self._stops.append(set(stop_ids))
+        self._active.append(k)
+        self._slot_seq[s] = k
+        return k
+
+    def retire(self, k: int, consumed: int) -> None:
+        """Sequence ``k`` is over and its consumer used ``consumed`` of its steps: its arena's ``length`` goes to exactly that
+        (``close``'s rule, for one sequence) -- before the buffer is staged again for the slot's next sequence."""
+        self.arenas[k].length = self.len0[k] + int(consumed)
+        self._retired.add(k)
 
     @torch.inference_mode()
     def enqueue(self) -> int:
@@ -358,17 +515,20 @@ class SlotLoop:
         if getattr(m, "_live_loop", None) is not self:
             raise RuntimeError("SlotLoop: another device loop on this model took over (one device-side generation per model "
                                "at a time)")
-        g = m._slot_graph(self.S, self.nsplit, self.nsplit_trunk)
+        g = m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         g.replay()
         e1.record()
         i = self.n
         r = (self.ctr0 + i) % self.RING
+        if i >= self.RING:
+            self._advance_mirror(i - self.RING)          # (row r still holds step i - RING: the mirror takes it in first)
         self.host[r].copy_(self._ring2d[:, r], non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        self.events.append((e0, e1, done))
+        self.events[i] = (e0, e1, done)
+        self.events.pop(i - self.RING, None)             # nobody can ask for a step whose ring row is being reused
         self.n += 1
         return i
 
@@ -378,20 +538,25 @@ class SlotLoop:
             i = self._seen
             self.events[i][2].synchronize()
             row = self.host[(self.ctr0 + i) % self.RING]
-            for k, s in enumerate(self.idx):
+            for k in list(self._active):
+                if i < self._start[k]:
+                    continue
                 if not self._alive[k] or (self._killed[k] is not None and i >= self._killed[k]):
                     self._alive[k] = False
+                    self._active.remove(k)
                     continue
                 self._last[k] = i
-                tok = int(row[s])
-                if tok in self.stop_ids or i + 1 >= self.max_new or self.len0[k] + i + 2 >= self.arenas[k].cap:
+                tok, j = int(row[self.idx[k]]), i - self._start[k]
+                if tok in self._stops[k] or j + 1 >= self._max_new[k] or self.len0[k] + j + 2 >= self.arenas[k].cap:
                     self._alive[k] = False
+                    self._active.remove(k)
             self._seen += 1
 
     def token(self, k: int, i: int) -> Optional[int]:
-        """Token of sequence ``k`` at step ``i`` (None: the sequence had stopped before that step)."""
+        """Token of sequence ``k`` at step ``i`` of the loop (the global replay index).  None: the sequence had stopped before
+        that step, or had not been admitted yet."""
         self._advance_mirror(i)
-        if i > self._last[k]:
+        if i > self._last[k] or i < self._start[k]:
             return None
         return int(self.host[(self.ctr0 + i) % self.RING][self.idx[k]])
 
@@ -410,8 +575,12 @@ class SlotLoop:
     def close(self, consumed) -> None:
         """``consumed[k]``: how many of the loop's steps sequence k's consumer used.  Each arena's ``length`` goes to exactly that
         (rows a look-ahead replay wrote past it are dead), and the loop state is released."""
-        for a, l0, c in zip(self.arenas, self.len0, consumed):
-            a.length = l0 + int(c)
+        if isinstance(consumed, dict):                   # an each=True loop: the sequences that were not retired one by one
+            for k, c in consumed.items():
+                self.arenas[k].length = self.len0[k] + int(c)
+        else:
+            for a, l0, c in zip(self.arenas, self.len0, consumed):
+                a.length = l0 + int(c)
         if getattr(self.m, "_live_loop", None) is self:
             self.m._live_loop = None
 
@@ -1653,7 +1822,8 @@ class LlamaHIP:
 
     def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
                   slots: Optional[int] = None, slot_index=None, share_trunk: bool = False,
-                  min_trunk: Optional[int] = None) -> Optional["SlotLoop"]:
+                  min_trunk: Optional[int] = None, each: bool = False, max_keys: Optional[int] = None,
+                  trunks=None) -> Optional["SlotLoop"]:
         """A batched device-side decode loop over the arenas behind ``pasts`` (one ``past_key_values`` per sequence, each a
         batch-1 arena of its own): sequence k feeds ``tokens[k]`` at position ``positions[k]`` next.  ``params`` None or plain
         greedy: argmax; otherwise the sampled chain with ``seeds[k]`` (the stream continues at step 1) and ``histories[k]``.
@@ -1661,8 +1831,16 @@ class LlamaHIP:
         caller then decodes the sequences one after another.  ``share_trunk``: sequences whose arenas staged the same leading
         module rows (``kv_arena.common_trunks`` over ``KVArena.layout``; at least ``min_trunk`` rows, default
         ``PC_SLOT_TRUNK_MIN`` = 256) read those rows from one arena, once per step for the whole group
-        (``pc_attn_decode_slots_trunk``); a batch without such a group runs the unshared step, bit for bit."""
-        if not self.slot_loop_available() or not 1 <= len(pasts) <= SlotLoop.MAX_SLOTS or len(stop_ids) > 8:
+        (``pc_attn_decode_slots_trunk``); a batch without such a group runs the unshared step, bit for bit (``trunks``: the
+        grouping, where the caller has worked it out already).
+        ``each``: the step ends in ``pc_sample_advance_slots_each`` -- ``params``, ``max_new`` and ``stop_ids`` may then be lists
+        with one entry per sequence, and ``SlotLoop.admit`` puts new sequences into slots whose sequence is over.
+        ``max_keys``: the upper bound of keys the split counts of the attention are taken from (default: from this batch).  A
+        serving loop passes the capacity of the slot buffers, once: a sequence's bits must not depend on who joins later, and the
+        attention's summation order depends on the split counts."""
+        per_seq_stops = each and len(stop_ids) and isinstance(stop_ids[0], (list, tuple))
+        if not self.slot_loop_available() or not 1 <= len(pasts) <= SlotLoop.MAX_SLOTS or \
+                (max(map(len, stop_ids)) if per_seq_stops else len(stop_ids)) > 8:
             return None
         arenas = []
         for past in pasts:
@@ -1671,8 +1849,10 @@ class LlamaHIP:
                 return None
             a.materialize()                       # (a staging no forward carried out yet)
             arenas.append(a)
-        trunks = common_trunks([a.layout for a in arenas], min_trunk) if share_trunk else None
-        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks)
+        if trunks is None and share_trunk:
+            trunks = common_trunks([a.layout for a in arenas], min_trunk)
+        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks,
+                        each, max_keys)
 
     def _slot_nsplit(self, S: int, max_keys: int) -> int:
         """Splits of the key axis of pc_attn_decode_slots: enough workgroups to cover the chip at S slots, at least 256 keys
@@ -1698,15 +1878,20 @@ class LlamaHIP:
                       stop=torch.full((8,), -1, dtype=torch.int32, device=dev), seeds=z(S, torch.int64),
                       ring=z(S * SlotLoop.RING, torch.int32),
                       params=z(ctypes.sizeof(_native.SampleParams), torch.uint8), hist=z((S, (V + 31) // 32), torch.int32),
-                      logits=z((S, V), torch.float32))
+                      logits=z((S, V), torch.float32),
+                      # per-slot sampling state of the each=True step (pc_sample_advance_slots_each)
+                      params_each=z(S * ctypes.sizeof(_native.SampleParams), torch.uint8),
+                      stop_each=torch.full((S, 8), -1, dtype=torch.int32, device=dev), draws=z(S, torch.int32))
             sts[S] = st
         return st
 
-    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0):
+    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False):
         """The captured S-slot decode step.  Everything that changes from step to step or from batch to batch -- arena
         addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch.
         ``nsplit_trunk`` > 0: the step with shared trunks; which slots share what is device data as well (leader / trunk)."""
         key = ("slots", S, nsplit, "trunk", nsplit_trunk) if nsplit_trunk else ("slots", S, nsplit)
+        if each:
+            key += ("each",)
         g = self._graphs.pop(key, None)
         if g is not None:
             self._graphs[key] = g
@@ -1718,17 +1903,17 @@ class LlamaHIP:
         # advances nothing, the live words are put back behind it
         live = st["live"].clone()
         st["live"].zero_()
-        self._forward_slots(st, S, nsplit, nsplit_trunk)
+        self._forward_slots(st, S, nsplit, nsplit_trunk, each)
         torch.cuda.synchronize()
         prime_graph_capture(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._forward_slots(st, S, nsplit, nsplit_trunk)
+            self._forward_slots(st, S, nsplit, nsplit_trunk, each)
         st["live"].copy_(live)
         self._graphs[key] = g
         return g
 
-    def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0) -> None:
+    def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False) -> None:
         """One decode step over S slots: the <= 16-row projections of ``_layers_norm_fused`` around per-slot RoPE + append
         and attention; logits to ``st["logits"]``, then the advance launch."""
         n = _native
@@ -1770,8 +1955,13 @@ class LlamaHIP:
             else:
                 n.gemm_skinny(lw["wdown_f"], ch, cl, S, hid, inter, n.EPI_ADD, y=x, ldy=hid)           # x += act @ Wd^T
         n.gemm_skinny_norm(self.lm_head_f, x, self.norm, eps, S, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
-        n.sample_advance_slots(st["logits"], V, V, st["params"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
-                               st["cap"], st["live"], st["budget"], st["stop"], st["ring"], st["ctr"], SlotLoop.RING, S)
+        if each:
+            n.sample_advance_slots_each(st["logits"], V, V, st["params_each"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
+                                        st["cap"], st["live"], st["budget"], st["stop_each"], st["ring"], st["ctr"], st["draws"],
+                                        SlotLoop.RING, S)
+        else:
+            n.sample_advance_slots(st["logits"], V, V, st["params"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
+                                   st["cap"], st["live"], st["budget"], st["stop"], st["ring"], st["ctr"], SlotLoop.RING, S)
 
     def _ks_buffers(self, hid: int):
         """Scratch slabs + arrival counters of pc_gemm_skinny_ks (shared by every such launch of the model: they run one
