@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--serve", type=int, default=0,
                     help="serve N prompts with mixed max_new_tokens through --batch slots (continuous batching: a finished "
                          "sequence's slot takes the next prompt while the others keep decoding)")
+    ap.add_argument("--lookup", type=int, default=None,
+                    help="prompt-lookup speculative decoding for the greedy single-prompt generation: draft up to K tokens (1..15; "
+                         "try 7) from the context per step and verify them in one K+1-row forward (default: PC_LOOKUP, else off)")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
@@ -54,7 +57,7 @@ def main():
         lm = cls(shape, random_init=True)
     preproc = [lm.get_formatter()]
     cache_engine = CacheEngine(a.max_ctx, lm, module_kv=a.module_kv, slots=max(1, a.batch))
-    gen_engine = GenerationEngine(lm)
+    gen_engine = GenerationEngine(lm, lookup=a.lookup)
     if a.schema:
         cache_engine.add_schema(read_file(a.schema, preproc), max_tokens=a.max_tokens)
         prompt_text = open(a.prompt_file).read()

@@ -605,6 +605,32 @@ int pc_sample_advance(const float* logits, int32_t vocab, const pc_sample_params
                       int32_t* pos, int32_t* past_len, int32_t* ring, int32_t* counter, int32_t ring_cap, float* processed_out,
                       void* stream);
 
+/* ---- prompt-lookup speculative decoding (csrc/pc_lookup.hip) ---------------------------------------------------------------------
+ * Greedy decoding with up to k + 1 tokens per forward: the two ends of a captured step whose middle is the ordinary forward of
+ * rows = k + 1 <= 16 tokens read from ids / pos / past_len.  All state lives in DEVICE words, so a replay needs no host input:
+ *   hist int32[hist_cap], hist_len int32[1]   every token of the sequence so far (corpus, prompt, output); hist[hist_len - 1]
+ *                                             is the token the step feeds and equals ids[0]
+ *   ids int64[k + 1], pos int32[k + 1]        the forward's inputs: row 0 the fed token, rows 1..k the drafts
+ *   ndraft int32[1]                           how many of rows 1..k are real drafts (the rest are pads)
+ *
+ * pc_lookup_draft: with h = hist, L = hist_len: for n = min(nmax, L - 1) down to 1, the candidates are the j in [0, L - n - 1]
+ * with h[j..j+n) == h[L-n..L); the LARGEST j of the first n that has one is taken.  m = min(k, L - (j + n)); ids[1 + i] =
+ * h[j + n + i] for i < m and ids[0] for m <= i < k (pad rows embed a valid token); pos[i] = pos[0] + i; ndraft = m, or 0 without
+ * a candidate.  1 <= k <= 15, 1 <= nmax <= 8, hist_cap < 2^24.  One workgroup; nothing else is written.
+ *
+ * pc_lookup_verify: logits fp32 [rows][vocab] with row stride ldl (elements; 4-byte alignment suffices).  a[i] = argmax of row
+ * i, the lowest index among equal maxima (pc_greedy_advance's rule), left in row_argmax int32[rows] (scratch).  acc = the
+ * largest c <= ndraft with a[i] == ids[1 + i] for all i < c; emit = min(acc + 1, budget[0]).  The record
+ * ring[(counter % ring_cap) * (rows + 1) ..] gets {emit, a[0..emit)} and counter += 1; when emit > 0: hist[L..L+emit) =
+ * a[0..emit), hist_len += emit, ids[0] = a[emit - 1], pos[0] += emit, past_len[0] += emit, budget[0] -= emit.  With budget[0] = 0
+ * the record is {0} and nothing else changes, so replays past the end of a generation are harmless.  At rows = 1 (ndraft = 0)
+ * the token and the ids / pos / past_len / counter words are pc_greedy_advance's.  Two launches: rows workgroups, then one wave. */
+int pc_lookup_draft(const int32_t* hist, const int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* ndraft,
+                    int32_t k, int32_t nmax, void* stream);
+int pc_lookup_verify(const float* logits, int64_t ldl, int32_t vocab, int32_t rows, int32_t* row_argmax, int32_t* hist,
+                     int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* past_len, const int32_t* ndraft,
+                     int32_t* budget, int32_t* ring, int32_t* counter, int32_t ring_cap, void* stream);
+
 /* ---- batched decode over slots (csrc/pc_slots.hip, csrc/pc_sample.hip) ---------------------------------------------------------
  * A slot is one running sequence in a batch-1 KV arena of its own ([n_layers][2][Hkv][cap][head_dim] fp16, pc_kv_gather's dst).
  * Its state is one element of each of these DEVICE arrays over S <= 16 slots, so that one captured step serves every replay:

@@ -165,6 +165,8 @@ SIGNATURES = {
                                      _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pc_greedy_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pc_sample_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pc_lookup_draft": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "pc_lookup_verify": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pc_rope_append_slots": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pc_attn_decode_slots_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
     "pc_attn_decode_slots": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
@@ -742,6 +744,26 @@ def greedy_advance(logits, vocab: int, ids, pos, past, ring, counter, stream: Op
     rc = load().pc_greedy_advance(logits.data_ptr(), vocab, ids.data_ptr(), pos.data_ptr(), past.data_ptr(), ring.data_ptr(),
                                   counter.data_ptr(), ring.numel(), current_stream() if stream is None else stream)
     check(rc, "pc_greedy_advance")
+
+
+def lookup_draft(hist, hist_len, ids, pos, ndraft, k: int, nmax: int = 3, stream: Optional[int] = None) -> None:
+    """Head of a prompt-lookup step (pc_lookup_draft): drafts ids[1..k] / pos[1..k] from the most recent earlier occurrence of
+    the history's suffix.  ``ids`` int64 / ``pos`` int32 hold at least k + 1 words."""
+    assert ids.numel() >= k + 1 and pos.numel() >= k + 1
+    rc = load().pc_lookup_draft(hist.data_ptr(), hist_len.data_ptr(), hist.numel(), ids.data_ptr(), pos.data_ptr(), ndraft.data_ptr(),
+                                k, nmax, current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_draft")
+
+
+def lookup_verify(logits, ldl: int, vocab: int, rows: int, row_argmax, hist, hist_len, ids, pos, past, ndraft, budget, ring, counter,
+                  ring_cap: int, stream: Optional[int] = None) -> None:
+    """Tail of a prompt-lookup step (pc_lookup_verify): per-row argmax, longest agreeing draft prefix + one token, state advance;
+    ``ring`` int32 [ring_cap][rows + 1] takes the record {count, tokens...}."""
+    assert ring.numel() >= ring_cap * (rows + 1) and row_argmax.numel() >= rows and ids.numel() >= rows
+    rc = load().pc_lookup_verify(logits.data_ptr(), ldl, vocab, rows, row_argmax.data_ptr(), hist.data_ptr(), hist_len.data_ptr(),
+                                 hist.numel(), ids.data_ptr(), pos.data_ptr(), past.data_ptr(), ndraft.data_ptr(), budget.data_ptr(),
+                                 ring.data_ptr(), counter.data_ptr(), ring_cap, current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_verify")
 
 
 def rope_append_slots(qkv, ld: int, in_layout: int, q_hi, q_lo, q_ts: int, cs, kv_base, cap, length, live, S: int, layer: int,

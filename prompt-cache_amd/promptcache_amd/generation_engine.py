@@ -94,9 +94,12 @@ class GenerationEngine:
     # (model/llama_hip.py SampleLoop; PC_DEVICE_SAMPLE=0: step through lm() and torch's sampler)
     device_sample_loop = os.environ.get("PC_DEVICE_SAMPLE", "1") != "0"
 
-    def __init__(self, lm: LanguageModel, verbose: bool = False):
+    def __init__(self, lm: LanguageModel, verbose: bool = False, lookup: Optional[int] = None):
+        """``lookup`` = k > 0 (None: ``PC_LOOKUP``, default 0 = off): plain-greedy generations draft up to k tokens per step by
+        prompt lookup and verify them in one k+1-row forward (model/llama_hip.py LookupLoop) where the model offers it."""
         self.lm = lm
         self.verbose = verbose
+        self.lookup = int(os.environ.get("PC_LOOKUP", "0")) if lookup is None else int(lookup)
 
     # -- pieces of the loop ---------------------------------------------------------------------
     def _forward(self, ids: List[int], positions: List[int], past) -> Tuple[torch.Tensor, object, float]:
@@ -126,6 +129,20 @@ class GenerationEngine:
                 return text, new_text, False, True
         return text, new_text, False, False
 
+    @staticmethod
+    def _lookup_corpus(cache, token_ids: List[int]) -> List[int]:
+        """What a lookup generation may copy from: the ids of the staged rows in arena row order (the ``KVArena.layout`` runs
+        carry their token sequences; a run whose ids cannot be recovered contributes nothing), then the prompt's new ids."""
+        ids: List[int] = []
+        for run in getattr(getattr(cache, "arena", None), "layout", None) or []:
+            try:
+                t = [int(x) for x in run[0].token_ids()]
+            except Exception:
+                continue
+            if len(t) == run[1]:
+                ids += t
+        return ids + [int(x) for x in token_ids]
+
     # -- the generator ----------------------------------------------------------------------------
     @torch.inference_mode()
     def generate(self, token_ids: List[int], position_ids: List[int], params: GenerationParameters,
@@ -154,14 +171,34 @@ class GenerationEngine:
         want_loop = plain_greedy and not use_full_position_ids and hasattr(hf, "greedy_loop") and self.device_greedy_loop
         want_sample = not plain_greedy and not use_full_position_ids and hasattr(hf, "sample_loop") and self.device_sample_loop
         seed = int(torch.randint(0, 2 ** 62, (1,))) if want_sample else 0
+        # ... and with ``lookup`` = k > 0 a plain-greedy generation runs the lookup loop instead: a step yields 1..k+1 tokens.  The
+        # host reads step after step, one replay ahead while the step in flight cannot exhaust the budget (a replay behind the
+        # last token would stream the weights for nothing); tokens of a step behind a stop are dropped.
+        want_lookup = want_loop and self.lookup > 0 and hasattr(hf, "lookup_loop")
+        lstep, got, queued = 0, 0, []
+        loop_total = params.max_new_tokens - 1
 
         try:
             for step in range(params.max_new_tokens):
                 if loop is not None:
-                    if loop.n <= step and loop.n < params.max_new_tokens - 1:
-                        loop.enqueue()                             # the replay AFTER the one whose token is read below
-                    token = loop.token(step - 1)
-                    total_ms += loop.elapsed_ms(step - 1)
+                    if getattr(loop, "multi", False):
+                        if not queued:
+                            if loop.n <= lstep:
+                                loop.enqueue()
+                            if loop.n == lstep + 1 and got + loop.k + 1 < loop_total:
+                                loop.enqueue()                         # the replay AFTER the one whose tokens are read below
+                            queued = loop.tokens(lstep)
+                            total_ms += loop.elapsed_ms(lstep)
+                            got += len(queued)
+                            lstep += 1
+                            if not queued:                             # (the device budget ran out: nothing more will come)
+                                break
+                        token = queued.pop(0)
+                    else:
+                        if loop.n <= step and loop.n < params.max_new_tokens - 1:
+                            loop.enqueue()                             # the replay AFTER the one whose token is read below
+                        token = loop.token(step - 1)
+                        total_ms += loop.elapsed_ms(step - 1)
                     output_ids.append(token)
                     new_ids.append(token)
                     done = token in params.stop_token_ids
@@ -207,7 +244,10 @@ class GenerationEngine:
                     break
                 if step == 0 and (want_loop or want_sample) and params.max_new_tokens > 1:
                     # the first decoded token sits at position first_free + 1 (the reference's loop index starts at 1, :132)
-                    if want_loop:
+                    if want_lookup:
+                        loop = hf.lookup_loop(past, token, first_free + 1, loop_total, min(self.lookup, 15),
+                                              self._lookup_corpus(cache, token_ids))
+                    elif want_loop:
                         loop = hf.greedy_loop(past, token, first_free + 1, params.max_new_tokens)
                     else:
                         loop = hf.sample_loop(past, token, first_free + 1, params.max_new_tokens, params, seed, output_ids)

@@ -257,6 +257,118 @@ class SampleLoop(GreedyLoop):
         return self.m._loop_graph(arena, past_len, sample=True)
 
 
+class LookupLoop:
+    """Greedy decode with prompt-lookup drafts, on the device: up to ``k + 1`` tokens per weight stream.
+
+    One step = ``pc_lookup_draft`` (copy the ``k`` tokens that followed the most recent earlier occurrence of the history's last
+    few tokens) -> the ordinary ``k + 1``-row forward over the ids / positions / past length in the loop's device words ->
+    ``pc_lookup_verify`` (per-row argmax; the longest draft prefix the model agrees with, plus its own next token, goes to the
+    ring and advances the words by that many rows).  The step is ONE captured graph that serves the whole loop; the host only
+    enqueues replays and reads ``{count, tokens}`` records through pinned memory.  How many tokens a replay yields is known on
+    the device only, so the loop is safe by construction instead of by host bookkeeping: the arena holds
+    ``len0 + max_new + k + 2`` rows, the device ``budget`` word keeps the past length at or below ``len0 + max_new``, a step
+    writes rows ``[past, past + k]`` only, and a replay with no budget left changes nothing but its (empty) record.
+
+    ``enqueue()`` -> step index; ``tokens(i)`` -> the 0..k+1 tokens of step i (waits for that step only);
+    ``close(consumed_tokens)``.  ``PC_DEVICE_LOOKUP=0`` runs the same three stages eagerly with a host read per step."""
+
+    RING = 1024
+    ROWS_MAX = 16
+    multi = True                     # a step yields a list of tokens (GenerationEngine)
+    device_loop = os.environ.get("PC_DEVICE_LOOKUP", "1") != "0"
+
+    @torch.inference_mode()
+    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3):
+        if not 1 <= k < self.ROWS_MAX:
+            raise ValueError(f"LookupLoop: k = {k} outside 1..{self.ROWS_MAX - 1}")
+        self.m, self.k, self.nmax = model, int(k), int(nmax)
+        arena.materialize()
+        len0 = arena.length
+        need = len0 + max_new + k + 2
+        if need > arena.cap:
+            arena = arena.grown(max(need, 2 * arena.cap))
+        self.arena = arena
+        self.len0, self.max_new = len0, int(max_new)
+        # the attention's split counts (and its kernel) for the WHOLE loop, from an upper bound of the keys a step can see
+        # (64-row buckets so that generations of similar length share a graph): the tokens of a generation do not depend on how
+        # far ahead the host enqueues, and the stepped mode runs the very same launches
+        self.kv_ceiling = min((len0 + max_new + k + 1 + 63) // 64 * 64, arena.cap)
+        hist0 = [int(t) for t in corpus_ids] + [int(token)]
+        st = self.st = model._lookup_state(len(hist0) + max_new)
+        model._live_loop = self
+        st["past"][0:1].fill_(len0)
+        st["hist_len"].fill_(len(hist0))
+        st["budget"].fill_(max_new)
+        st["pos"].fill_(position)
+        st["ids"].fill_(int(token))
+        st["ndraft"].zero_()
+        st["ctr"].zero_()
+        st["hist"][:len(hist0)].copy_(torch.tensor(hist0, dtype=torch.int32))
+        self.n = 0
+        self.events = []
+        self.host = torch.zeros((self.RING, k + 2), dtype=torch.int32, pin_memory=True)
+        self.ring = st["ring"][:self.RING * (k + 2)].view(self.RING, k + 2)
+
+    def _step(self):
+        """The three stages of one step on the current stream (captured, or launched eagerly by the stepped mode)."""
+        m, st, k, n = self.m, self.st, self.k, _native
+        V = m.config.vocab_size
+        n.lookup_draft(st["hist"], st["hist_len"], st["ids"], st["pos"], st["ndraft"], k, self.nmax)
+        out = m._forward_skinny(st["ids"][:k + 1], st["pos"][:k + 1], st["past"], self.arena, 1, k + 1, self.kv_ceiling - (k + 1),
+                                False, None)
+        n.lookup_verify(out, V, V, k + 1, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["past"], st["ndraft"],
+                        st["budget"], st["ring"], st["ctr"], self.RING)
+        return out
+
+    @torch.inference_mode()
+    def enqueue(self) -> int:
+        m, a = self.m, self.arena
+        if getattr(m, "_live_loop", None) is not self:
+            raise RuntimeError("LookupLoop: another device loop on this model took over (one device-side generation per model "
+                               "at a time)")
+        m._lo_mode = 0                     # appended rows carry no residual planes, as in default decode
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if self.device_loop:
+            ent = m._lookup_graph(self)
+            e0.record()
+            ent[0].replay()
+        else:
+            e0.record()
+            self.logits = self._step()     # (the stepped mode keeps the step's logits for whoever wants to look)
+        e1.record()
+        i = self.n
+        r = i % self.RING
+        self.host[r].copy_(self.ring[r], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self.events.append((e0, e1, done))
+        if not self.device_loop:
+            done.synchronize()             # the host read per step
+        m._tail_done(a, 0, 1, self.len0)
+        self.n += 1
+        return i
+
+    def tokens(self, i: int):
+        self.events[i][2].synchronize()
+        rec = self.host[i % self.RING]
+        c = int(rec[0])
+        return [int(t) for t in rec[1:1 + c]]
+
+    def close(self, consumed_tokens: int) -> None:
+        """The generation used ``consumed_tokens`` of the tokens the enqueued steps produced: the arena's length becomes the
+        real sequence (rows behind it -- rejected drafts, steps past a stop -- are rewritten before anything reads them), and
+        the loop state is released."""
+        self.arena.length = self.len0 + consumed_tokens
+        self.arena.tail_base, self.arena.tail_len = -1, 0
+        if getattr(self.m, "_live_loop", None) is self:
+            self.m._live_loop = None
+
+    def elapsed_ms(self, i: int) -> float:
+        e0, e1, done = self.events[i]
+        done.synchronize()
+        return e0.elapsed_time(e1)
+
+
 class SlotLoop:
     """Batched decode: up to 16 sequences, each in a batch-1 arena of its own, advanced together by one captured step.
 
@@ -680,6 +792,7 @@ class LlamaHIP:
         self.supports_ragged_past = True    # the many-row path takes past_lens (see __call__)
         self._shared = None        # set per call: (trunk arena, per-row prefix lengths int32 [B], their maximum)
         self.supports_greedy_loop = True    # decode steps can run as a device-side loop (GreedyLoop)
+        self._live_loop = None              # the device loop that owns the loop state words right now (one per model)
         self.llm_int8 = False
         self._last_qt = None
         self.batch_invariant = True         # a row's result does not depend on the other rows of the forward (see llm_int8)
@@ -1809,6 +1922,76 @@ class LlamaHIP:
         behind ``past``, continuing the random stream of ``seed`` at step 1.  None where ``greedy_loop`` gives None."""
         arena = self._loop_arena(past)
         return None if arena is None else SampleLoop(self, arena, token, position, max_new, params, seed, history_ids)
+
+    # ---- prompt-lookup speculative decoding (LookupLoop) ----------------------------------------------------------------
+    def lookup_available(self) -> bool:
+        """Whether this model runs ``LookupLoop``: the Llama layer loop over fp16 weight images, default decode precision (no
+        residual tail through decode).  Everything else (Falcon, MPT, int8 weights, PC_DECODE_TAIL=1) keeps ``GreedyLoop``."""
+        return bool(self.skinny and self.use_graphs and self.supports_greedy_loop and not self.int8_weights and
+                    not self.llm_int8 and not self.decode_tail and not self.use_chain and
+                    type(self)._forward_skinny is LlamaHIP._forward_skinny)
+
+    @torch.inference_mode()
+    def _lookup_state(self, hist_need: int) -> dict:
+        """Device words of the lookup loop (one set per model: the newest loop owns it, as with ``_loop_state``).  The history
+        buffer grows in powers of two; a captured step holds its address, so the graph key carries it (and the entry keeps the
+        buffer alive)."""
+        st = getattr(self, "_lookup_st", None)
+        dev = self.device
+        if st is None:
+            R = LookupLoop.ROWS_MAX
+            st = self._lookup_st = dict(
+                ids=torch.zeros(R, dtype=torch.int64, device=dev), pos=torch.zeros(R, dtype=torch.int32, device=dev),
+                past=torch.zeros(2, dtype=torch.int32, device=dev), ndraft=torch.zeros(1, dtype=torch.int32, device=dev),
+                budget=torch.zeros(1, dtype=torch.int32, device=dev), hist_len=torch.zeros(1, dtype=torch.int32, device=dev),
+                ctr=torch.zeros(1, dtype=torch.int32, device=dev), amax=torch.zeros(R, dtype=torch.int32, device=dev),
+                ring=torch.zeros(LookupLoop.RING * (R + 1), dtype=torch.int32, device=dev), hist=None)
+            # first launches of the two kernels outside any capture (code-object load), on words that hold zeros:
+            # budget 0 -> an empty record in ring[0], nothing else changes
+            warm = torch.zeros(1, dtype=torch.int32, device=dev)
+            _native.lookup_draft(warm, st["hist_len"], st["ids"], st["pos"], st["ndraft"], 1, 1)
+            _native.lookup_verify(torch.zeros(16, dtype=torch.float32, device=dev), 16, 16, 1, st["amax"], warm, st["hist_len"],
+                                  st["ids"], st["pos"], st["past"], st["ndraft"], st["budget"], st["ring"], st["ctr"], LookupLoop.RING)
+        if st["hist"] is None or st["hist"].numel() < hist_need:
+            cap = 8192
+            while cap < hist_need:
+                cap *= 2
+            st["hist"] = torch.zeros(cap, dtype=torch.int32, device=dev)
+        return st
+
+    def _lookup_graph(self, loop: "LookupLoop"):
+        """The captured graph of ONE lookup step of ``loop`` (draft + ``k + 1``-row forward + verify), one per key."""
+        arena, st, k = loop.arena, loop.st, loop.k
+        key = ("loop", "lookup", k, arena.buf.data_ptr(), arena.cap, self._nsplit_key(1, k + 1, loop.kv_ceiling), loop.kv_ceiling,
+               loop.nmax, st["hist"].data_ptr(), st["hist"].numel(), self.fuse_norm)
+        ent = self._graphs.pop(key, None)
+        if ent is not None:
+            self._graphs[key] = ent
+            return ent
+        if len(self._graphs) >= self.max_graphs:
+            self._graphs.pop(next(iter(self._graphs)))
+        # one eager pass of the forward first (loads code objects / sizes the allocator): it writes K / V rows [past, past + k],
+        # which the first replay writes again, reads whatever valid ids the draft rows hold, and does not touch the loop state
+        self._forward_skinny(st["ids"][:k + 1], st["pos"][:k + 1], st["past"], arena, 1, k + 1, loop.kv_ceiling - (k + 1), False, None)
+        torch.cuda.synchronize()
+        prime_graph_capture(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = loop._step()
+        ent = (g, out, st["hist"])
+        self._graphs[key] = ent
+        return ent
+
+    def lookup_loop(self, past, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3):
+        """A device-side greedy decode loop with prompt-lookup drafts (``LookupLoop``: up to ``k + 1`` tokens per step, ``k`` in
+        1..15) over the arena behind ``past``.  ``corpus_ids``: the ids the drafts may copy from besides the output itself --
+        the context in key order; the history starts as ``corpus_ids ++ [token]``.  ``max_new``: the most tokens the loop
+        emits.  None where ``greedy_loop`` gives None; a plain ``GreedyLoop`` where the model has no lookup step
+        (``lookup_available``)."""
+        if not self.lookup_available():
+            return self.greedy_loop(past, token, position, max_new)
+        arena = self._loop_arena(past)
+        return None if arena is None else LookupLoop(self, arena, token, position, max_new, k, corpus_ids, nmax)
 
     # ---- batched decode over slots (SlotLoop) ---------------------------------------------------------------------------
     supports_slot_loop = True       # (a subclass with layer loops of its own says no)

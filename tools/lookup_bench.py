@@ -1,0 +1,121 @@
+"""Prompt-lookup speculative decoding against the plain greedy loop at the 7b shape (random init, the persona prompt): tok/s of
+``GreedyLoop`` and of ``LookupLoop`` at k in {3, 7, 15} with a full-acceptance corpus (the context tail followed by the answer
+itself: every draft is right) and with an empty one (the worst case: every step pays k + 1 rows for one token, unless the output
+repeats itself), and the per-step time of the k + 1-row step against the one-row step.  Same process, interleaved repetitions,
+medians.  Prints one JSON line.
+
+    python tools/lookup_bench.py [--new 64] [--repeats 5] [--out profiles/lookup_bench.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "prompt-cache_amd")]
+from promptcache_amd import CacheEngine, Prompt, synth  # noqa: E402
+from promptcache_amd.model import Llama2  # noqa: E402
+
+KS = (3, 7, 15)
+
+
+def prefill(lm, eng, prompt):
+    ids, pos, _, cache = eng.process(prompt)
+    out = lm(input_ids=torch.tensor([ids]), position_ids=torch.tensor([pos]), past_key_values=cache, use_cache=True)
+    return ids, out.past_key_values, int(out.logits[0, -1].argmax()), max(pos) + 2
+
+
+def run_greedy(lm, eng, prompt, n_new):
+    """-> (tokens, seconds from the first enqueue to the last token on the host, per-step ms)."""
+    _, past, first, p0 = prefill(lm, eng, prompt)
+    loop = lm.hf_model.greedy_loop(past, first, p0, n_new)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loop.enqueue()
+    toks = []
+    for i in range(n_new):
+        if loop.n <= i + 1 and loop.n < n_new:
+            loop.enqueue()
+        toks.append(loop.token(i))
+    dt = time.perf_counter() - t0
+    ms = [loop.elapsed_ms(i) for i in range(n_new)]
+    loop.close(n_new)
+    return first, toks, dt, ms
+
+
+def run_lookup(lm, eng, prompt, n_new, k, corpus):
+    _, past, first, p0 = prefill(lm, eng, prompt)
+    loop = lm.hf_model.lookup_loop(past, first, p0, n_new, k, corpus)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    toks, i = [], 0
+    while len(toks) < n_new:
+        if loop.n <= i:
+            loop.enqueue()
+        if loop.n == i + 1 and len(toks) + k + 1 < n_new:
+            loop.enqueue()                       # one replay ahead while the step in flight cannot exhaust the budget
+        toks += loop.tokens(i)
+        i += 1
+    dt = time.perf_counter() - t0
+    ms = [loop.elapsed_ms(j) for j in range(i)]
+    loop.close(n_new)
+    return toks, dt, ms, i
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--new", type=int, default=64, help="tokens per generation (behind the first)")
+    ap.add_argument("--repeats", type=int, default=5, help="interleaved repetitions per leg (medians)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "lookup_bench measures on the GPU"
+    lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0)
+    assert lm.hf_model.lookup_available()
+    eng = CacheEngine(4096, lm)
+    fmt = lm.get_formatter()
+    sp, pp = synth.persona_like()
+    eng.add_schema(fmt(sp))
+    prompt = Prompt(pp, [fmt])
+    N = args.new
+    ctx_ids, _, _, _ = prefill(lm, eng, prompt)
+    first, T, _, _ = run_greedy(lm, eng, prompt, N)                  # warm + the answer the full-acceptance corpus copies
+    full = list(ctx_ids)[-8:] + [first] + T
+    legs = [("greedy", None, None)] + [(f"lookup_k{k}_{name}", k, c) for k in KS for name, c in (("full", full), ("empty", []))]
+    for name, k, c in legs[1:]:
+        run_lookup(lm, eng, prompt, N, k, c)                         # warm: graphs captured
+    rate = {name: [] for name, _, _ in legs}
+    step_ms = {name: [] for name, _, _ in legs}
+    steps, same = {}, {}
+    for _ in range(args.repeats):
+        for name, k, c in legs:
+            if k is None:
+                _, toks, dt, ms = run_greedy(lm, eng, prompt, N)
+                steps[name] = N
+            else:
+                toks, dt, ms, n_steps = run_lookup(lm, eng, prompt, N, k, c)
+                steps[name] = n_steps
+            same[name] = toks[:N] == T
+            rate[name].append(N / dt)
+            step_ms[name].append(statistics.median(ms))
+    result = {"shape": "llama2-7b (random init)", "prompt": "persona-structured schema, the decode leg's prompt", "new_tokens": N,
+              "how": "same process, legs interleaved, %d repetitions, medians; wall clock from the first enqueue to the last token "
+                     "on the host; step_ms: HIP events around one replay" % args.repeats,
+              "tokens_per_s": {n: round(statistics.median(v), 1) for n, v in rate.items()},
+              "tokens_per_s_min_max": {n: [round(min(v), 1), round(max(v), 1)] for n, v in rate.items()},
+              "step_ms": {n: round(statistics.median(v), 4) for n, v in step_ms.items()},
+              "steps": steps, "tokens_equal_greedy": same}
+    g = result["tokens_per_s"]["greedy"]
+    result["speedup_over_greedy"] = {n: round(v / g, 3) for n, v in result["tokens_per_s"].items() if n != "greedy"}
+    line = json.dumps(result)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
