@@ -45,7 +45,8 @@ def main():
                          "sequence's slot takes the next prompt while the others keep decoding)")
     ap.add_argument("--lookup", type=int, default=None,
                     help="prompt-lookup speculative decoding for the greedy single-prompt generation: draft up to K tokens (1..15; "
-                         "try 7) from the context per step and verify them in one K+1-row forward (default: PC_LOOKUP, else off)")
+                         "try 7) from the context per step and verify them in one K+1-row forward (default: PC_LOOKUP, else off); "
+                         "with --batch also for the batched loop (generate_batch(lookup=K): N * (K + 1) <= 64 rows per step)")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
@@ -95,7 +96,8 @@ def main():
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2, share_trunk=a.share_trunk):
+            for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2, share_trunk=a.share_trunk,
+                                                     lookup=a.lookup):
                 lasts[k] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

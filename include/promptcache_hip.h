@@ -700,6 +700,58 @@ int pc_sample_advance_slots_each(const float* logits, int64_t logits_row_stride,
                                  const int32_t* cap, int32_t* live, int32_t* budget, const int32_t* stop_ids, int32_t* ring,
                                  int32_t* counters, int32_t* draws, int32_t ring_cap, int32_t S, float* processed_out, void* stream);
 
+/* ---- prompt-lookup speculative decoding over slots (csrc/pc_lookup_slots.hip, csrc/pc_lookup.hip) ---------------------------------
+ * The batched step with up to k + 1 tokens per sequence and weight stream: every slot feeds its token and k drafts, so row
+ * r = b * (k + 1) + i of every activation is draft row i of slot b, R = S * (k + 1) <= 64 rows in all (1 <= k <= 15; the two
+ * middle entries also take k = 0).  A slot keeps kv_base / cap / len / live of the section above and gains, each an array over S:
+ *   hist int32[S][hist_cap], hist_len int32[S]   pc_lookup_draft's history, one row per slot
+ *   ids int64[S][k + 1], pos int32[S][k + 1]     the forward's inputs: row 0 the fed token, rows 1..k the drafts
+ *   ndraft int32[S], budget int32[S]             real drafts of this step; tokens the slot may still emit
+ *   stop_ids int32[S][8]                         token ids that end the slot's sequence (unused entries: -1)
+ *   ring int32[S][ring_cap][k + 2], ctr int32[S] one record {count, tokens...} per replay and slot
+ * A slot RUNS when live[b] != 0 and 0 <= len[b] and len[b] + k + 1 <= cap[b].  For a slot that does not run nothing is read and
+ * nothing is written by the first three entries; pc_lookup_verify_slots leaves it an EMPTY record (ring[b][ctr[b] % ring_cap] =
+ * {0}, ctr[b] += 1: record c of every slot belongs to replay c) and sets live[b] = 0 -- the too-full slot is switched off.
+ *
+ * pc_lookup_draft_slots: pc_lookup_draft's rule, one workgroup per running slot on hist[b], hist_len[b], ids[b], pos[b],
+ * ndraft[b].  With S = 1 every word written equals pc_lookup_draft's.
+ *
+ * pc_rope_append_slots_rows: pc_rope_append_slots for k + 1 rows per slot: row r of qkv (fp32 [R][ld], in_layout as there) is
+ * rotated with row r of cs [R][head_dim/2][2]; q goes to row r of the split-precision pair q_hi / q_lo [R][q_token_stride], K / V
+ * (rounded to fp16 once) to row len[b] + i of layer `layer` of the slot's arena.  The arithmetic is pc_rope_append_ex's; at k = 0
+ * the bytes equal pc_rope_append_slots'.
+ *
+ * pc_attn_verify_slots: for every running slot b, draft row i and query head: softmax(q k^T * softmax_scale) v over keys
+ * [0, len[b] + i] of the slot's arena -- the rows pc_rope_append_slots_rows just wrote included, row i does not see the draft
+ * rows behind it.  mfma_f32_16x16x32_f16 tiles of 16 (draft row x query head of one kv head) columns with q and p as hi / lo pairs,
+ * fp32 online softmax, K / V as stored.  The key axis [0, len[b] + k + 1) is cut into `nsplit` (1..32, from the host) shares
+ * read from the device; a share in which a row sees no key contributes (m = -1e30, l = 0).  Partials go to `workspace`
+ * (pc_attn_verify_slots_workspace_bytes) and are merged in key order by a second launch into the fragment planes out_frag_hi /
+ * out_frag_lo [ceil(R/16)][H*head_dim/32][64][8] (row = r) that pc_gemm's o_proj consumes.  head_dim 64 or 128.  A row's result
+ * depends on its own q, its own keys, k and nsplit only -- not on the other slots, the slot index or the live count.  Rows of
+ * slots that do not run are left as they are.
+ *
+ * pc_lookup_verify_slots: a[r] = argmax of row r of logits fp32 [R][vocab] (row stride ldl; pc_lookup_verify's rule) into
+ * row_argmax int32[R], then per running slot pc_lookup_verify's rule on the slot's words with len[b] in the place of past_len and
+ * two additions: emit is cut behind the first a[i], i < emit, that is one of stop_ids[b][0..8) -- that token is emitted and
+ * live[b] = 0 --, and live[b] = 0 when budget[b] reached 0 or the new len[b] + k + 1 > cap[b].  With S = 1 and no stop ids
+ * every word equals pc_lookup_verify's.  Ordinary vector stores only. */
+int pc_lookup_draft_slots(const int32_t* hist, const int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* ndraft,
+                          const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t k, int32_t nmax,
+                          void* stream);
+int pc_rope_append_slots_rows(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
+                              const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live,
+                              int32_t S, int32_t k, int32_t layer, int32_t H, int32_t Hkv, int32_t D, void* stream);
+int64_t pc_attn_verify_slots_workspace_bytes(int32_t S, int32_t k, int32_t H, int32_t D, int32_t nsplit);
+int pc_attn_verify_slots(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base, const int32_t* cap,
+                         const int32_t* len, const int32_t* live, int32_t S, int32_t k, int32_t layer, int32_t H, int32_t Hkv,
+                         int32_t D, float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
+                         void* out_frag_lo, void* stream);
+int pc_lookup_verify_slots(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k, int32_t* row_argmax, int32_t* hist,
+                           int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* len, const int32_t* cap,
+                           int32_t* live, const int32_t* ndraft, int32_t* budget, const int32_t* stop_ids, int32_t* ring,
+                           int32_t* counters, int32_t ring_cap, void* stream);
+
 /* pc_slot_arm -- admission of ONE sequence into a running slot loop: one launch writes every state word of slot `slot` (and its
  * history bitmap row) from a pinned host block, read with system-scope loads (pc_fetch_block's rule); live[slot] = 1 is the last
  * store.  The launch is ordered on `stream` behind the replays already enqueued: they saw the old words, later ones see the new

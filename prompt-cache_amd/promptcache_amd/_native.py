@@ -167,6 +167,14 @@ SIGNATURES = {
     "pc_sample_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pc_lookup_draft": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "pc_lookup_verify": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "pc_lookup_draft_slots": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "pc_rope_append_slots_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                            _vp]),
+    "pc_attn_verify_slots_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
+    "pc_attn_verify_slots": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
+                                       _vp, _vp]),
+    "pc_lookup_verify_slots": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _i32, _vp]),
     "pc_rope_append_slots": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pc_attn_decode_slots_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
     "pc_attn_decode_slots": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
@@ -804,6 +812,56 @@ def attn_decode_slots_trunk(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, l
                                            workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(),
                                            out_frag[1].data_ptr(), current_stream() if stream is None else stream)
     check(rc, "pc_attn_decode_slots_trunk")
+
+
+def lookup_draft_slots(hist, hist_len, ids, pos, ndraft, cap, length, live, S: int, k: int, nmax: int = 3,
+                       stream: Optional[int] = None) -> None:
+    """pc_lookup_draft per running slot (pc_lookup_draft_slots): ``hist`` int32 [S][hist_cap], ``ids`` int64 / ``pos`` int32
+    [S][k + 1]."""
+    assert hist.dim() == 2 and hist.shape[0] == S and hist.is_contiguous() and ids.numel() >= S * (k + 1) and pos.numel() >= S * (k + 1)
+    rc = load().pc_lookup_draft_slots(hist.data_ptr(), hist_len.data_ptr(), hist.shape[1], ids.data_ptr(), pos.data_ptr(),
+                                      ndraft.data_ptr(), cap.data_ptr(), length.data_ptr(), live.data_ptr(), S, k, nmax,
+                                      current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_draft_slots")
+
+
+def rope_append_slots_rows(qkv, ld: int, in_layout: int, q_hi, q_lo, q_ts: int, cs, kv_base, cap, length, live, S: int, k: int,
+                           layer: int, H: int, Hkv: int, D: int, stream: Optional[int] = None) -> None:
+    """RoPE + K / V append of ``k + 1`` rows per running slot (pc_rope_append_slots_rows); row ``b * (k + 1) + i`` = draft row i of
+    slot b."""
+    rc = load().pc_rope_append_slots_rows(qkv.data_ptr(), ld, in_layout, q_hi.data_ptr(), q_lo.data_ptr(), q_ts, cs.data_ptr(),
+                                          kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(), live.data_ptr(), S, k, layer, H, Hkv,
+                                          D, current_stream() if stream is None else stream)
+    check(rc, "pc_rope_append_slots_rows")
+
+
+def attn_verify_slots_workspace_bytes(S: int, k: int, H: int, D: int, nsplit: int) -> int:
+    return int(load().pc_attn_verify_slots_workspace_bytes(S, k, H, D, nsplit))
+
+
+def attn_verify_slots(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int, k: int, layer: int, H: int, Hkv: int, D: int,
+                      softmax_scale: float, nsplit: int, workspace, out_frag, stream: Optional[int] = None) -> None:
+    """Causal attention of the ``k + 1`` draft rows of every running slot over its own arena (pc_attn_verify_slots) -> fragment
+    planes (hi, lo) with ``ceil(S * (k + 1) / 16)`` row tiles."""
+    rc = load().pc_attn_verify_slots(q_hi.data_ptr(), q_lo.data_ptr(), q_ts, kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(),
+                                     live.data_ptr(), S, k, layer, H, Hkv, D, softmax_scale, nsplit, workspace.data_ptr(),
+                                     workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
+                                     current_stream() if stream is None else stream)
+    check(rc, "pc_attn_verify_slots")
+
+
+def lookup_verify_slots(logits, ldl: int, vocab: int, S: int, k: int, row_argmax, hist, hist_len, ids, pos, length, cap, live, ndraft,
+                        budget, stop_ids, ring, counters, ring_cap: int, stream: Optional[int] = None) -> None:
+    """Tail of a batched prompt-lookup step (pc_lookup_verify_slots): per-row argmax over ``S * (k + 1)`` rows, then per slot the
+    accepted prefix + one token, stop ids, budget and arena room; ``ring`` int32 [S][ring_cap][k + 2], ``stop_ids`` int32 [S][8]."""
+    R = S * (k + 1)
+    assert ring.numel() >= S * ring_cap * (k + 2) and row_argmax.numel() >= R and ids.numel() >= R and stop_ids.numel() >= 8 * S
+    assert hist.dim() == 2 and hist.shape[0] == S and hist.is_contiguous()
+    rc = load().pc_lookup_verify_slots(logits.data_ptr(), ldl, vocab, S, k, row_argmax.data_ptr(), hist.data_ptr(), hist_len.data_ptr(),
+                                       hist.shape[1], ids.data_ptr(), pos.data_ptr(), length.data_ptr(), cap.data_ptr(), live.data_ptr(),
+                                       ndraft.data_ptr(), budget.data_ptr(), stop_ids.data_ptr(), ring.data_ptr(), counters.data_ptr(),
+                                       ring_cap, current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_verify_slots")
 
 
 def sample_advance_slots(logits, ldl: int, vocab: int, params, seeds, history, ids, pos, length, cap, live, budget, stop_ids, ring,

@@ -289,7 +289,8 @@ class GenerationEngine:
 
     @torch.inference_mode()
     def generate_batch(self, requests, params: GenerationParameters, stream_interval: int = 2,
-                       share_trunk: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
+                       share_trunk: Optional[bool] = None, lookup: Optional[int] = None
+                       ) -> Generator[Tuple[int, Output], None, None]:
         """Generate for several prompts at once: ``requests = [(token_ids, position_ids, cache), ...]``, each as
         ``CacheEngine.process(prompt, slot=k)`` returned it (every cache in a staged buffer of its own).  Yields ``(index,
         Output)`` pairs; per sequence the ``Output`` stream, the stop-token and stop-string handling, ``max_new_tokens`` and the
@@ -298,9 +299,20 @@ class GenerationEngine:
         host one replay ahead.  Sequence k of a sampled batch uses seed ``seed + k`` of the one seed taken from torch's default
         generator.  Where no batched loop is available (``batch_plan``) the sequences run one after another through
         ``generate``.  ``share_trunk``: sequences that staged the same leading modules read those rows once per step for the
-        whole group (``LlamaHIP.slot_loop(share_trunk=True)``); None reads ``PC_SLOT_TRUNK`` (default 0)."""
+        whole group (``LlamaHIP.slot_loop(share_trunk=True)``); None reads ``PC_SLOT_TRUNK`` (default 0).
+        ``lookup`` = k > 0 (None: ``PC_SLOT_LOOKUP``, default 0 = off; the engine's own ``lookup`` is NOT consulted): a
+        plain-greedy batch drafts up to k tokens per sequence and step by prompt lookup and verifies them in one
+        ``S * (k + 1)``-row step (``LlamaHIP.lookup_slot_loop``); the tokens are greedy decoding's.  Sampled or
+        penalised params, a model without that step and ``S * (k + 1) > 64`` run the loop above instead.  k above 15 is
+        taken as 15 (a step's draft rows fill one 16-row tile at most).  Up to 8 stop ids end a sequence on the device and a
+        stop string is seen by the host, which switches the slot off between replays; with more than 8 stop ids
+        ``batch_plan`` runs the sequences one after another, with or without ``lookup``.  Together with
+        ``share_trunk`` it raises ValueError (there is no trunk kernel for the verify step)."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
+        lookup = int(os.environ.get("PC_SLOT_LOOKUP", "0")) if lookup is None else int(lookup)
+        if lookup > 0 and share_trunk:
+            raise ValueError("generate_batch: lookup > 0 and share_trunk=True cannot be combined (no shared-trunk verify step)")
         requests = [(list(t), list(p), c) for t, p, c in requests]
         batched, _ = self.batch_plan(len(requests), params)
         hf = getattr(self.lm, "hf_model", None)
@@ -356,6 +368,39 @@ class GenerationEngine:
                 if out is not None:
                     yield k, out
             members = [k for k in range(n) if not done[k]]
+            if members and lookup > 0 and plain_greedy and hasattr(hf, "lookup_slot_loop"):
+                loop = hf.lookup_slot_loop([pasts[k] for k in members], [new_ids[k][-1] for k in members],
+                                           [first_free[k] + 1 for k in members], last_step, min(lookup, 15),
+                                           [self._lookup_corpus(requests[k][2], requests[k][0]) for k in members],
+                                           stop_ids=params.stop_token_ids)
+            if loop is not None:
+                # a step yields 0..k+1 tokens per sequence: the host reads step after step, one replay ahead while the step in
+                # flight cannot exhaust every budget; tokens of a step behind a stop are dropped
+                lstep = 0
+                loop.enqueue()
+                while not all(done[k] for k in members):
+                    room = max(last_step - (len(new_ids[k]) - 1) for k in members if not done[k])
+                    if loop.n <= lstep or (loop.n == lstep + 1 and room > loop.k + 1):
+                        loop.enqueue()
+                    ms = loop.elapsed_ms(lstep)
+                    for j, k in enumerate(members):
+                        if done[k]:
+                            continue
+                        toks = loop.tokens(j, lstep)
+                        if not toks:                               # (the device switched the slot off: nothing more will come)
+                            done[k] = True
+                            continue
+                        total_ms[k] += ms
+                        for token in toks:
+                            out = emit(k, len(new_ids[k]), token)
+                            if out is not None:
+                                yield k, out
+                            if done[k]:
+                                if token not in params.stop_token_ids and len(new_ids[k]) - 1 != last_step:
+                                    loop.kill(j)                   # a stop string: the device cannot know
+                                break
+                    lstep += 1
+                return
             if members:
                 loop = hf.slot_loop([pasts[k] for k in members], [new_ids[k][-1] for k in members],
                                     [first_free[k] + 1 for k in members], last_step, None if plain_greedy else params,

@@ -697,6 +697,126 @@ class SlotLoop:
             self.m._live_loop = None
 
 
+class LookupSlotLoop:
+    """Batched decode with prompt-lookup drafts: ``SlotLoop``'s slots x ``LookupLoop``'s ``k + 1`` rows.
+
+    Every replay of the ONE captured step runs ``pc_lookup_draft_slots`` -> the layer stack over ``R = S * (k + 1)`` rows (row
+    ``b * (k + 1) + i`` = draft row i of slot b) with ``pc_rope_append_slots_rows`` / ``pc_attn_verify_slots`` per slot ->
+    ``pc_lookup_verify_slots``, which leaves one ``{count, tokens...}`` record per slot and advances the slot's words by what it
+    accepted.  A slot stops on the device (stop id, budget) and leaves empty records afterwards.  Safe by construction, per slot,
+    as ``LookupLoop`` is: every arena holds ``len0 + max_new + k + 2`` rows, ``budget`` keeps ``len`` at or below
+    ``len0 + max_new``, a step writes rows ``[len, len + k]`` only.
+
+    ``enqueue()`` -> step index; ``tokens(j, i)`` -> the 0..k+1 tokens of sequence j at step i (waits for that step only);
+    ``kill(j)``; ``close(consumed)`` with the TOKENS each sequence's consumer used; ``logits`` is the ``[R][V]`` fp32 tensor of
+    the last replay."""
+
+    RING = 1024
+    MAX_ROWS = 64
+
+    @torch.inference_mode()
+    def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
+                 slots: Optional[int] = None, max_keys: Optional[int] = None):
+        n = len(arenas)
+        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= n)
+        assert 1 <= n <= S <= SlotLoop.MAX_SLOTS and 1 <= k <= 15 and S * (k + 1) <= self.MAX_ROWS, (n, S, k)
+        assert len(tokens) == n and len(positions) == n and len(corpora) == n and len(stop_ids) <= 8 and max_new >= 1
+        self.m, self.S, self.k, self.nmax, self.max_new = model, S, int(k), int(nmax), int(max_new)
+        grown = []
+        for a in arenas:                              # no address may move under the captured step
+            need = a.length + max_new + k + 2
+            grown.append(a.grown(max(need, 2 * a.cap)) if need > a.cap else a)
+            model._tail_done(grown[-1], 0, 1, a.length)
+        self.arenas = grown
+        self.len0 = [a.length for a in grown]
+        if max_keys is None:
+            max_keys = (max(self.len0) + max_new + k + 1 + 63) // 64 * 64
+        self.max_keys = int(max_keys)
+        self.nsplit = model._slot_nsplit(S, self.max_keys)
+        hists = [[int(t) for t in c] + [int(tok)] for c, tok in zip(corpora, tokens)]
+        st = self.st = model._lookup_slot_state(S, k, max(map(len, hists)) + max_new)
+        model._live_loop = self
+        R1 = k + 1
+
+        def col(vals, dtype, fill=0):
+            t = torch.full((S,), fill, dtype=dtype)
+            t[:n] = torch.tensor(list(vals), dtype=dtype)
+            return t
+        st["kv_base"].copy_(col([a.buf.data_ptr() for a in grown], torch.int64), non_blocking=True)
+        st["cap"].copy_(col([a.cap for a in grown], torch.int32), non_blocking=True)
+        st["len"].copy_(col(self.len0, torch.int32), non_blocking=True)
+        st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
+        st["budget"].copy_(col([max_new] * n, torch.int32), non_blocking=True)
+        st["hist_len"].copy_(col(map(len, hists), torch.int32), non_blocking=True)
+        st["ndraft"].zero_()
+        st["ctr"].zero_()
+        ids = torch.zeros((S, R1), dtype=torch.int64)
+        pos = torch.zeros((S, R1), dtype=torch.int32)
+        hist = torch.zeros((S, max(map(len, hists))), dtype=torch.int32)
+        for j, h in enumerate(hists):
+            ids[j], pos[j] = int(tokens[j]), int(positions[j])
+            hist[j, :len(h)] = torch.tensor(h, dtype=torch.int32)
+        st["ids"].copy_(ids, non_blocking=True)
+        st["pos"].copy_(pos, non_blocking=True)
+        st["hist"][:, :hist.shape[1]].copy_(hist, non_blocking=True)
+        stop = torch.full((S, 8), -1, dtype=torch.int32)
+        stop[:, :len(stop_ids)] = torch.tensor([int(t) for t in stop_ids], dtype=torch.int32)
+        st["stop"].copy_(stop, non_blocking=True)
+        self.logits = st["logits"]
+        self.n = 0
+        self.events = {}
+        self.host = torch.zeros((self.RING, S, k + 2), dtype=torch.int32, pin_memory=True)
+        self._ring3d = st["ring"].view(S, self.RING, k + 2)
+        torch.cuda.current_stream().synchronize()        # (the pageable sources of the copies above may go now)
+
+    @torch.inference_mode()
+    def enqueue(self) -> int:
+        m = self.m
+        if getattr(m, "_live_loop", None) is not self:
+            raise RuntimeError("LookupSlotLoop: another device loop on this model took over (one device-side generation per model "
+                               "at a time)")
+        m._lo_mode = 0                     # appended rows carry no residual planes, as in default decode
+        g = m._lookup_slot_graph(self)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        i = self.n
+        r = i % self.RING
+        self.host[r].copy_(self._ring3d[:, r], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self.events[i] = (e0, e1, done)
+        self.events.pop(i - self.RING, None)
+        self.n += 1
+        return i
+
+    def tokens(self, j: int, i: int):
+        """The tokens sequence ``j`` emitted at step ``i`` (empty: the sequence was over, or had no budget left)."""
+        self.events[i][2].synchronize()
+        rec = self.host[i % self.RING][j]
+        c = int(rec[0])
+        return [int(t) for t in rec[1:1 + c]]
+
+    def kill(self, j: int) -> None:
+        """Switch sequence ``j`` off from the next replay on (ordered behind the replays already enqueued)."""
+        self.st["live"][j: j + 1].fill_(0)
+
+    def elapsed_ms(self, i: int) -> float:
+        e0, e1, done = self.events[i]
+        done.synchronize()
+        return e0.elapsed_time(e1)
+
+    def close(self, consumed) -> None:
+        """``consumed[j]``: how many of its TOKENS sequence j's consumer used.  Each arena's ``length`` goes to exactly that (rows
+        behind it -- rejected drafts, look-ahead replays -- are rewritten before anything reads them); the loop state is released."""
+        for a, l0, c in zip(self.arenas, self.len0, consumed):
+            a.length = l0 + int(c)
+            a.tail_base, a.tail_len = -1, 0
+        if getattr(self.m, "_live_loop", None) is self:
+            self.m._live_loop = None
+
+
 class LlamaHIP:
     """Weights live on one MI355X in fp16; ``wqkv`` and ``wgu`` are the row-concatenated q|k|v and
     gate|up projections so each is one GEMM."""
@@ -2145,6 +2265,140 @@ class LlamaHIP:
         else:
             n.sample_advance_slots(st["logits"], V, V, st["params"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
                                    st["cap"], st["live"], st["budget"], st["stop"], st["ring"], st["ctr"], SlotLoop.RING, S)
+
+    # ---- prompt-lookup drafts in the slot loop (LookupSlotLoop) ----------------------------------------------------------
+    def lookup_slot_loop(self, pasts, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
+                         slots: Optional[int] = None, max_keys: Optional[int] = None) -> Optional["LookupSlotLoop"]:
+        """``slot_loop`` with prompt-lookup drafts: up to ``k + 1`` greedy tokens per sequence and step (``LookupSlotLoop``).
+        ``corpora[j]``: the ids sequence j's drafts may copy from besides its own output (``lookup_loop``'s ``corpus_ids``).  None
+        where ``slot_loop`` gives None, where the model has no lookup step (``lookup_available``) and where ``S * (k + 1)``
+        exceeds the 64 rows of the weight-streaming projections -- the caller then runs ``slot_loop``."""
+        n = len(pasts)
+        if not (self.slot_loop_available() and self.lookup_available()) or not 1 <= n <= SlotLoop.MAX_SLOTS or len(stop_ids) > 8:
+            return None
+        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= n)
+        if not 1 <= k <= 15 or not n <= S <= SlotLoop.MAX_SLOTS or S * (k + 1) > LookupSlotLoop.MAX_ROWS:
+            return None
+        arenas = []
+        for past in pasts:
+            a = self._loop_arena(past)
+            if a is None or any(a is b for b in arenas):
+                return None
+            a.materialize()
+            arenas.append(a)
+        return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys)
+
+    @torch.inference_mode()
+    def _lookup_slot_state(self, S: int, k: int, hist_need: int) -> dict:
+        """Device words of the (S, k) lookup step (one set per (S, k): the captured steps hold their addresses).  The history
+        buffer grows in powers of two; the graph key carries its address."""
+        sts = self.__dict__.setdefault("_lookup_slot_sts", {})
+        st = sts.get((S, k))
+        dev, V = self.device, self.config.vocab_size
+        if st is None:
+            R = S * (k + 1)
+            z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)
+            st = sts[(S, k)] = dict(
+                kv_base=z(S, torch.int64), cap=z(S, torch.int32), len=z(S, torch.int32), live=z(S, torch.int32),
+                ids=z((S, k + 1), torch.int64), pos=z((S, k + 1), torch.int32), ndraft=z(S, torch.int32), budget=z(S, torch.int32),
+                hist_len=z(S, torch.int32), ctr=z(S, torch.int32), amax=z(R, torch.int32),
+                stop=torch.full((S, 8), -1, dtype=torch.int32, device=dev), ring=z(S * LookupSlotLoop.RING * (k + 2), torch.int32),
+                logits=z((R, V), torch.float32), hist=None)
+        if st["hist"] is None or st["hist"].shape[1] < hist_need:
+            cap = 8192
+            while cap < hist_need:
+                cap *= 2
+            st["hist"] = torch.zeros((S, cap), dtype=torch.int32, device=dev)
+        return st
+
+    def _lookup_slot_graph(self, loop: "LookupSlotLoop"):
+        """The captured (S, k) lookup step.  Arena addresses, lengths and histories are device data: one graph per key."""
+        st, S, k = loop.st, loop.S, loop.k
+        key = ("slots", "lookup", S, k, loop.nsplit, loop.nmax, st["hist"].data_ptr(), st["hist"].shape[1])
+        ent = self._graphs.pop(key, None)
+        if ent is not None:
+            self._graphs[key] = ent
+            return ent[0]
+        if len(self._graphs) >= self.max_graphs:
+            self._graphs.pop(next(iter(self._graphs)))
+        # one eager pass first (loads code objects / sizes the allocator) with every slot idle: it appends nothing and advances
+        # nothing but the record counters, which are put back behind it with the live words
+        live, ctr = st["live"].clone(), st["ctr"].clone()
+        st["live"].zero_()
+        self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax)
+        torch.cuda.synchronize()
+        prime_graph_capture(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax)
+        st["live"].copy_(live)
+        st["ctr"].copy_(ctr)
+        self._graphs[key] = (g, st["hist"])
+        return g
+
+    def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3) -> None:
+        """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
+        k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
+        projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop."""
+        n = _native
+        dev, c = self.device, self.config
+        H, Hkv, D, hid, inter = self.H, self.Hkv, self.D, c.hidden_size, c.intermediate_size
+        W, eps, V = (H + 2 * Hkv) * D, c.rms_norm_eps, c.vocab_size
+        R = S * (k + 1)
+        mt = (R + 15) // 16
+        slot = (st["kv_base"], st["cap"], st["len"], st["live"])
+        n.lookup_draft_slots(st["hist"], st["hist_len"], st["ids"], st["pos"], st["ndraft"], st["cap"], st["len"], st["live"], S, k, nmax)
+        cs = torch.empty((R, D // 2, 2), dtype=torch.float32, device=dev)
+        n.rope_table(st["pos"], self.inv_freq, cs, R, D)
+        h16 = torch.empty((R, hid), dtype=self.dtype, device=dev)
+        n.embed_gather(self.embed, st["ids"], h16, R, hid, V)
+        x = h16.float()
+        qkv = torch.empty((R, W), dtype=torch.float32, device=dev)
+        q16 = torch.zeros((R, H * D), dtype=self.dtype, device=dev)
+        q16l = torch.zeros((R, H * D), dtype=self.dtype, device=dev)
+        ws = torch.empty(max(n.attn_verify_slots_workspace_bytes(S, k, H, D, nsplit), 16) // 4, dtype=torch.float32, device=dev)
+
+        def planes(kk, zero=False):   # (zeroed where rows of idle slots are never written: they must not hold NaN bit patterns)
+            mk = torch.zeros if zero else torch.empty
+            return (mk((mt, kk // 32, 64, 8), dtype=self.dtype, device=dev), mk((mt, kk // 32, 64, 8), dtype=self.dtype, device=dev))
+        ah, al = planes(H * D, True)
+        ch, cl = planes(inter, True)
+
+        def attend(li):
+            n.rope_append_slots_rows(qkv, W, 1, q16, q16l, H * D, cs, *slot, S, k, li, H, Hkv, D)
+            n.attn_verify_slots(q16, q16l, H * D, *slot, S, k, li, H, Hkv, D, self.softmax_scale, nsplit, ws, (ah, al))
+
+        if R <= 16:
+            ks_down = self.ks_down and self.ks_min_rows <= R and inter >= 2 * hid
+            for li, lw in enumerate(self.layers):
+                n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+                attend(li)
+                n.gemm_skinny(lw["wo_f"], ah, al, R, hid, H * D, n.EPI_ADD, y=x, ldy=hid)
+                n.gemm_skinny_norm(lw["wgu_f"], x, lw["ln2"], eps, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+                if ks_down:
+                    sc, ctr = self._ks_buffers(hid)
+                    n.gemm_skinny_ks(lw["wdown_f"], ch, cl, R, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr)
+                else:
+                    n.gemm_skinny(lw["wdown_f"], ch, cl, R, hid, inter, n.EPI_ADD, y=x, ldy=hid)
+            n.gemm_skinny_norm(self.lm_head_f, x, self.norm, eps, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
+        else:
+            xh, xl = planes(hid)
+            KQ = self.rows_kslices(R, hid)
+            slabs = torch.empty((KQ, R, hid), dtype=torch.float32, device=dev)
+            pending = 0
+            for li, lw in enumerate(self.layers):
+                n.rmsnorm_frag(x, lw["ln1"], xh, xl, R, hid, eps, slabs, pending)
+                n.gemm_skinny(lw["wqkv_f"], xh, xl, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+                attend(li)
+                n.gemm_skinny(lw["wo_f"], ah, al, R, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                n.rmsnorm_frag(x, lw["ln2"], xh, xl, R, hid, eps, slabs, KQ)
+                n.gemm_skinny(lw["wgu_f"], xh, xl, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+                n.gemm_skinny(lw["wdown_f"], ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                pending = KQ
+            n.rmsnorm_frag(x, self.norm, xh, xl, R, hid, eps, slabs, pending)
+            n.gemm_skinny(self.lm_head_f, xh, xl, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
+        n.lookup_verify_slots(st["logits"], V, V, S, k, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"],
+                              st["cap"], st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
 
     def _ks_buffers(self, hid: int):
         """Scratch slabs + arrival counters of pc_gemm_skinny_ks (shared by every such launch of the model: they run one
