@@ -39,7 +39,8 @@ def main():
     ap.add_argument("--batch", type=int, default=0,
                     help="also decode N copies of the prompt with different questions together (generate_batch; N <= 16)")
     ap.add_argument("--share-trunk", action="store_true",
-                    help="with --batch: read the module rows the N prompts have in common once per step for all of them")
+                    help="with --batch: read the module rows the N prompts have in common once per step for all of them "
+                         "(with --lookup K as well: once for all K + 1 draft rows of all of them)")
     ap.add_argument("--serve", type=int, default=0,
                     help="serve N prompts with mixed max_new_tokens through --batch slots (continuous batching: a finished "
                          "sequence's slot takes the next prompt while the others keep decoding)")

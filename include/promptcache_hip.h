@@ -731,6 +731,20 @@ int pc_sample_advance_slots_each(const float* logits, int64_t logits_row_stride,
  * depends on its own q, its own keys, k and nsplit only -- not on the other slots, the slot index or the live count.  Rows of
  * slots that do not run are left as they are.
  *
+ * pc_attn_verify_slots_trunk: pc_attn_verify_slots for slots that hold the same bytes in their first rows, with the leader /
+ * trunk words and the host contract of pc_attn_decode_slots_trunk (leader[g] == g, trunk[b] == trunk[g], 0 < trunk[b] <= len[b];
+ * a slot for which it does not hold is treated as leader[b] = -1).  For a running slot b with T shared rows, draft row i takes
+ * keys [0, T) from the arena of its leader and keys [T, len[b] + i] from its own; with T = 0 keys [0, len[b] + i] of its own.  The
+ * leader's rows are read whether or not the leader is live or runs (no step rewrites rows below len >= T).  Three launches: a
+ * trunk launch reads each group's shared rows once for all draft rows of all running members (tiles of 16 columns, column
+ * (m * (k + 1) + i) * G + g = member m, draft row i, query head g of the kv head; no mask, every trunk key is visible to every
+ * draft row; `nsplit_trunk` shares of the trunk), an own launch does pc_attn_verify_slots' arithmetic over keys [T, len[b] + k + 1)
+ * in `nsplit_own` shares with the mask of the draft rows unchanged, and the merge takes nsplit_trunk + nsplit_own partials per
+ * (row, head) in key order from `workspace` (pc_attn_verify_slots_trunk_workspace_bytes); a row of a slot on its own has no
+ * trunk partials.  A row's result depends on its own q, its keys, k, T and the two split counts only -- not on the size of its
+ * group, its place in a tile or the slot index.  With leader = -1 everywhere the planes are bit-identical to
+ * pc_attn_verify_slots at nsplit = nsplit_own.  For slots that do not run nothing is read and nothing is written.
+ *
  * pc_lookup_verify_slots: a[r] = argmax of row r of logits fp32 [R][vocab] (row stride ldl; pc_lookup_verify's rule) into
  * row_argmax int32[R], then per running slot pc_lookup_verify's rule on the slot's words with len[b] in the place of past_len and
  * two additions: emit is cut behind the first a[i], i < emit, that is one of stop_ids[b][0..8) -- that token is emitted and
@@ -747,6 +761,13 @@ int pc_attn_verify_slots(const void* q_hi, const void* q_lo, int64_t q_token_str
                          const int32_t* len, const int32_t* live, int32_t S, int32_t k, int32_t layer, int32_t H, int32_t Hkv,
                          int32_t D, float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
                          void* out_frag_lo, void* stream);
+int64_t pc_attn_verify_slots_trunk_workspace_bytes(int32_t S, int32_t k, int32_t H, int32_t D, int32_t nsplit_own,
+                                                   int32_t nsplit_trunk);
+int pc_attn_verify_slots_trunk(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                               const int32_t* cap, const int32_t* len, const int32_t* live, const int32_t* leader,
+                               const int32_t* trunk, int32_t S, int32_t k, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                               float softmax_scale, int32_t nsplit_own, int32_t nsplit_trunk, void* workspace,
+                               int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, void* stream);
 int pc_lookup_verify_slots(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k, int32_t* row_argmax, int32_t* hist,
                            int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* len, const int32_t* cap,
                            int32_t* live, const int32_t* ndraft, int32_t* budget, const int32_t* stop_ids, int32_t* ring,

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "pc_attn_common.h"
+#include "pc_lookup_common.h"
 
 namespace {
 
@@ -103,19 +104,7 @@ __global__ __launch_bounds__(kThreads) void rope_append_slots_kernel(
 // grid (split, kv head x pass, slot).  A pass takes GQ query heads of the kv head's group; D / 8 lanes hold one key row, a wave
 // 64 / (D / 8) keys at a time, four keys per lane group in flight.  Every lane group keeps an online softmax of its own
 // keys; the groups of a wave are merged through lane exchanges, the four waves through LDS, always in the same order.
-// Shared rows of slot b (pc_attn_decode_slots_trunk): trunk[b] where the host contract holds for b -- a leader g inside the S
-// slots that leads itself, a trunk that fits the leader's arena and the slot's own length and is the leader's -- and 0 otherwise:
-// the slot is then on its own.  The trunk launch, the own launch and the merge all ask here, so a violated contract gives the
-// slot's plain attention over its own arena, never a read of records nobody wrote.
-__device__ __forceinline__ int slot_trunk_rows(int b, int S, const uint64_t* __restrict__ kv_base, const int32_t* __restrict__ cap,
-                                               const int32_t* __restrict__ len, const int32_t* __restrict__ leader,
-                                               const int32_t* __restrict__ trunk) {
-    const int g = leader[b];
-    if (g < 0 || g >= S) return 0;
-    const int T = trunk[g];
-    return (leader[g] == g && T > 0 && T <= cap[g] && kv_base[g] != 0 && trunk[b] == T && T <= len[b]) ? T : 0;
-}
-
+// Shared rows of a slot (pc_attn_decode_slots_trunk): slot_trunk_rows, pc_lookup_common.h.
 // TRUNK (pc_attn_decode_slots_trunk): a slot with shared rows (slot_trunk_rows) takes keys [trunk[b], len[b]] only -- the keys in front of them
 // are the trunk launch's -- and its partials are records rec0 .. rec0 + nsplit - 1 of the nrec records per (slot, head).  With
 // none the arithmetic is the plain instantiation's.

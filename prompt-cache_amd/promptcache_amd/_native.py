@@ -173,6 +173,9 @@ SIGNATURES = {
     "pc_attn_verify_slots_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "pc_attn_verify_slots": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
                                        _vp, _vp]),
+    "pc_attn_verify_slots_trunk_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "pc_attn_verify_slots_trunk": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32,
+                                             _i32, _vp, _i64, _vp, _vp, _vp]),
     "pc_lookup_verify_slots": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _i32, _vp]),
     "pc_rope_append_slots": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
@@ -848,6 +851,23 @@ def attn_verify_slots(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int,
                                      workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
                                      current_stream() if stream is None else stream)
     check(rc, "pc_attn_verify_slots")
+
+
+def attn_verify_slots_trunk_workspace_bytes(S: int, k: int, H: int, D: int, nsplit_own: int, nsplit_trunk: int) -> int:
+    return int(load().pc_attn_verify_slots_trunk_workspace_bytes(S, k, H, D, nsplit_own, nsplit_trunk))
+
+
+def attn_verify_slots_trunk(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, leader, trunk, S: int, k: int, layer: int, H: int,
+                            Hkv: int, D: int, softmax_scale: float, nsplit_own: int, nsplit_trunk: int, workspace, out_frag,
+                            stream: Optional[int] = None) -> None:
+    """pc_attn_verify_slots with shared trunks: keys [0, trunk[b]) of a slot with leader[b] = g are read from slot g's arena, once
+    for all draft rows of all members of the group (pc_attn_verify_slots_trunk) -> fragment planes (hi, lo)."""
+    rc = load().pc_attn_verify_slots_trunk(q_hi.data_ptr(), q_lo.data_ptr(), q_ts, kv_base.data_ptr(), cap.data_ptr(),
+                                           length.data_ptr(), live.data_ptr(), leader.data_ptr(), trunk.data_ptr(), S, k, layer, H,
+                                           Hkv, D, softmax_scale, nsplit_own, nsplit_trunk, workspace.data_ptr(),
+                                           workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(),
+                                           out_frag[1].data_ptr(), current_stream() if stream is None else stream)
+    check(rc, "pc_attn_verify_slots_trunk")
 
 
 def lookup_verify_slots(logits, ldl: int, vocab: int, S: int, k: int, row_argmax, hist, hist_len, ids, pos, length, cap, live, ndraft,

@@ -307,15 +307,24 @@ class GenerationEngine:
         taken as 15 (a step's draft rows fill one 16-row tile at most).  Up to 8 stop ids end a sequence on the device and a
         stop string is seen by the host, which switches the slot off between replays; with more than 8 stop ids
         ``batch_plan`` runs the sequences one after another, with or without ``lookup``.  Together with
-        ``share_trunk`` it raises ValueError (there is no trunk kernel for the verify step)."""
+        ``share_trunk`` the lookup step reads a group's shared rows once for all draft rows of the group
+        (``LlamaHIP.lookup_slot_loop(share_trunk=True)``) where the model has that step
+        (``lookup_trunk_available``) and ``batch_plan`` decodes the batch in a device loop; a refused lookup loop falls back to
+        ``slot_loop(share_trunk=True)``.  Anywhere else the combination raises ValueError, as it did before that step existed,
+        before anything is asked of the model."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         lookup = int(os.environ.get("PC_SLOT_LOOKUP", "0")) if lookup is None else int(lookup)
-        if lookup > 0 and share_trunk:
-            raise ValueError("generate_batch: lookup > 0 and share_trunk=True cannot be combined (no shared-trunk verify step)")
         requests = [(list(t), list(p), c) for t, p, c in requests]
-        batched, _ = self.batch_plan(len(requests), params)
         hf = getattr(self.lm, "hf_model", None)
+        batched, why = self.batch_plan(len(requests), params)
+        if lookup > 0 and share_trunk:
+            offered = getattr(hf, "lookup_trunk_available", None)
+            if offered is None or not offered():
+                raise ValueError("generate_batch: lookup > 0 and share_trunk=True cannot be combined (no shared-trunk verify step)")
+            if not batched:
+                raise ValueError("generate_batch: lookup > 0 and share_trunk=True cannot be combined (no shared-trunk verify step "
+                                 f"runs for this batch: {why})")
         if batched:
             # every cache must be a staged batch-1 arena, no two the same
             arenas = [getattr(c, "arena", None) for _, _, c in requests]
@@ -372,7 +381,7 @@ class GenerationEngine:
                 loop = hf.lookup_slot_loop([pasts[k] for k in members], [new_ids[k][-1] for k in members],
                                            [first_free[k] + 1 for k in members], last_step, min(lookup, 15),
                                            [self._lookup_corpus(requests[k][2], requests[k][0]) for k in members],
-                                           stop_ids=params.stop_token_ids)
+                                           stop_ids=params.stop_token_ids, share_trunk=bool(share_trunk))
             if loop is not None:
                 # a step yields 0..k+1 tokens per sequence: the host reads step after step, one replay ahead while the step in
                 # flight cannot exhaust every budget; tokens of a step behind a stop are dropped

@@ -709,14 +709,16 @@ class LookupSlotLoop:
 
     ``enqueue()`` -> step index; ``tokens(j, i)`` -> the 0..k+1 tokens of sequence j at step i (waits for that step only);
     ``kill(j)``; ``close(consumed)`` with the TOKENS each sequence's consumer used; ``logits`` is the ``[R][V]`` fp32 tensor of
-    the last replay."""
+    the last replay.  ``trunks`` (``lookup_slot_loop(share_trunk=True)``): ``SlotLoop``'s grouping -- the step then
+    reads a group's shared rows from the leader's arena, once for all draft rows of all members
+    (``pc_attn_verify_slots_trunk``); ``nsplit_trunk`` > 0 says so."""
 
     RING = 1024
     MAX_ROWS = 64
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
-                 slots: Optional[int] = None, max_keys: Optional[int] = None):
+                 slots: Optional[int] = None, max_keys: Optional[int] = None, trunks=None):
         n = len(arenas)
         S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= n)
         assert 1 <= n <= S <= SlotLoop.MAX_SLOTS and 1 <= k <= 15 and S * (k + 1) <= self.MAX_ROWS, (n, S, k)
@@ -729,9 +731,29 @@ class LookupSlotLoop:
             model._tail_done(grown[-1], 0, 1, a.length)
         self.arenas = grown
         self.len0 = [a.length for a in grown]
-        if max_keys is None:
-            max_keys = (max(self.len0) + max_new + k + 1 + 63) // 64 * 64
-        self.max_keys = int(max_keys)
+        # shared trunks, as in SlotLoop: per sequence (leader index | None, T), checked on the arenas the loop uses
+        self.trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
+        self.nsplit_trunk = 0
+        shared = any(l is not None for l, _ in self.trunks)
+        if shared:
+            for j, (l, T) in enumerate(self.trunks):
+                assert l is None or (self.trunks[l] == (l, T) and 0 < T <= self.len0[j] and T <= self.len0[l]), (j, self.trunks)
+            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1":
+                for j, (l, T) in enumerate(self.trunks):
+                    if l is not None and l != j and not torch.equal(grown[j].buf[:, :, :, :, :T], grown[l].buf[:, :, :, :, :T]):
+                        raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of sequence {j} differ from its trunk leader's "
+                                           f"(sequence {l})")
+        # max_keys: the bound the split counts are taken from -- of all keys of a sequence, or, in a loop with shared trunks
+        # and no bound from the caller, of a sequence's OWN keys behind its trunk (the trunk has a split count of its own)
+        if max_keys is not None:                          # split counts from the caller's bound, not from this batch
+            self.max_keys = int(max_keys)
+            if shared:
+                self.nsplit_trunk = model._slot_nsplit(1, self.max_keys)
+        elif shared:
+            self.nsplit_trunk = model._slot_nsplit(len({l for l, _ in self.trunks if l is not None}), max(T for _, T in self.trunks))
+            self.max_keys = (max(l0 - T for l0, (_, T) in zip(self.len0, self.trunks)) + max_new + k + 1 + 63) // 64 * 64
+        else:
+            self.max_keys = (max(self.len0) + max_new + k + 1 + 63) // 64 * 64
         self.nsplit = model._slot_nsplit(S, self.max_keys)
         hists = [[int(t) for t in c] + [int(tok)] for c, tok in zip(corpora, tokens)]
         st = self.st = model._lookup_slot_state(S, k, max(map(len, hists)) + max_new)
@@ -746,6 +768,8 @@ class LookupSlotLoop:
         st["cap"].copy_(col([a.cap for a in grown], torch.int32), non_blocking=True)
         st["len"].copy_(col(self.len0, torch.int32), non_blocking=True)
         st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
+        st["leader"].copy_(col([-1 if l is None else l for l, _ in self.trunks], torch.int32, -1), non_blocking=True)
+        st["trunk"].copy_(col([T for _, T in self.trunks], torch.int32), non_blocking=True)
         st["budget"].copy_(col([max_new] * n, torch.int32), non_blocking=True)
         st["hist_len"].copy_(col(map(len, hists), torch.int32), non_blocking=True)
         st["ndraft"].zero_()
@@ -2268,11 +2292,15 @@ class LlamaHIP:
 
     # ---- prompt-lookup drafts in the slot loop (LookupSlotLoop) ----------------------------------------------------------
     def lookup_slot_loop(self, pasts, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
-                         slots: Optional[int] = None, max_keys: Optional[int] = None) -> Optional["LookupSlotLoop"]:
+                         slots: Optional[int] = None, max_keys: Optional[int] = None, share_trunk: bool = False,
+                         min_trunk: Optional[int] = None, trunks=None) -> Optional["LookupSlotLoop"]:
         """``slot_loop`` with prompt-lookup drafts: up to ``k + 1`` greedy tokens per sequence and step (``LookupSlotLoop``).
         ``corpora[j]``: the ids sequence j's drafts may copy from besides its own output (``lookup_loop``'s ``corpus_ids``).  None
         where ``slot_loop`` gives None, where the model has no lookup step (``lookup_available``) and where ``S * (k + 1)``
-        exceeds the 64 rows of the weight-streaming projections -- the caller then runs ``slot_loop``."""
+        exceeds the 64 rows of the weight-streaming projections -- the caller then runs ``slot_loop``.  ``share_trunk`` /
+        ``min_trunk`` / ``trunks``: ``slot_loop``'s -- sequences that staged the same leading module rows read them from one
+        arena, once per step for all draft rows of the group (``pc_attn_verify_slots_trunk``); a batch without such a group runs
+        the unshared step, bit for bit."""
         n = len(pasts)
         if not (self.slot_loop_available() and self.lookup_available()) or not 1 <= n <= SlotLoop.MAX_SLOTS or len(stop_ids) > 8:
             return None
@@ -2286,7 +2314,13 @@ class LlamaHIP:
                 return None
             a.materialize()
             arenas.append(a)
-        return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys)
+        if trunks is None and share_trunk:
+            trunks = common_trunks([a.layout for a in arenas], min_trunk)
+        return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks)
+
+    def lookup_trunk_available(self) -> bool:
+        """Whether ``lookup_slot_loop`` can share trunks: the lookup step and the slot step are both there."""
+        return bool(self.lookup_available() and self.slot_loop_available())
 
     @torch.inference_mode()
     def _lookup_slot_state(self, S: int, k: int, hist_need: int) -> dict:
@@ -2300,6 +2334,7 @@ class LlamaHIP:
             z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)
             st = sts[(S, k)] = dict(
                 kv_base=z(S, torch.int64), cap=z(S, torch.int32), len=z(S, torch.int32), live=z(S, torch.int32),
+                leader=torch.full((S,), -1, dtype=torch.int32, device=dev), trunk=z(S, torch.int32),
                 ids=z((S, k + 1), torch.int64), pos=z((S, k + 1), torch.int32), ndraft=z(S, torch.int32), budget=z(S, torch.int32),
                 hist_len=z(S, torch.int32), ctr=z(S, torch.int32), amax=z(R, torch.int32),
                 stop=torch.full((S, 8), -1, dtype=torch.int32, device=dev), ring=z(S * LookupSlotLoop.RING * (k + 2), torch.int32),
@@ -2314,7 +2349,8 @@ class LlamaHIP:
     def _lookup_slot_graph(self, loop: "LookupSlotLoop"):
         """The captured (S, k) lookup step.  Arena addresses, lengths and histories are device data: one graph per key."""
         st, S, k = loop.st, loop.S, loop.k
-        key = ("slots", "lookup", S, k, loop.nsplit, loop.nmax, st["hist"].data_ptr(), st["hist"].shape[1])
+        key = ("slots", "lookup", S, k, loop.nsplit) + (("trunk", loop.nsplit_trunk) if loop.nsplit_trunk else ()) + \
+            (loop.nmax, st["hist"].data_ptr(), st["hist"].shape[1])
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2325,21 +2361,22 @@ class LlamaHIP:
         # nothing but the record counters, which are put back behind it with the live words
         live, ctr = st["live"].clone(), st["ctr"].clone()
         st["live"].zero_()
-        self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax)
+        self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk)
         torch.cuda.synchronize()
         prime_graph_capture(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax)
+            self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk)
         st["live"].copy_(live)
         st["ctr"].copy_(ctr)
         self._graphs[key] = (g, st["hist"])
         return g
 
-    def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3) -> None:
+    def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3, nsplit_trunk: int = 0) -> None:
         """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
         k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
-        projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop."""
+        projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop.
+        ``nsplit_trunk`` > 0: the attention with shared trunks (leader / trunk words of the state)."""
         n = _native
         dev, c = self.device, self.config
         H, Hkv, D, hid, inter = self.H, self.Hkv, self.D, c.hidden_size, c.intermediate_size
@@ -2356,7 +2393,9 @@ class LlamaHIP:
         qkv = torch.empty((R, W), dtype=torch.float32, device=dev)
         q16 = torch.zeros((R, H * D), dtype=self.dtype, device=dev)
         q16l = torch.zeros((R, H * D), dtype=self.dtype, device=dev)
-        ws = torch.empty(max(n.attn_verify_slots_workspace_bytes(S, k, H, D, nsplit), 16) // 4, dtype=torch.float32, device=dev)
+        ws_bytes = (n.attn_verify_slots_trunk_workspace_bytes(S, k, H, D, nsplit, nsplit_trunk) if nsplit_trunk
+                    else n.attn_verify_slots_workspace_bytes(S, k, H, D, nsplit))
+        ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev)
 
         def planes(kk, zero=False):   # (zeroed where rows of idle slots are never written: they must not hold NaN bit patterns)
             mk = torch.zeros if zero else torch.empty
@@ -2366,7 +2405,11 @@ class LlamaHIP:
 
         def attend(li):
             n.rope_append_slots_rows(qkv, W, 1, q16, q16l, H * D, cs, *slot, S, k, li, H, Hkv, D)
-            n.attn_verify_slots(q16, q16l, H * D, *slot, S, k, li, H, Hkv, D, self.softmax_scale, nsplit, ws, (ah, al))
+            if nsplit_trunk:
+                n.attn_verify_slots_trunk(q16, q16l, H * D, *slot, st["leader"], st["trunk"], S, k, li, H, Hkv, D, self.softmax_scale,
+                                          nsplit, nsplit_trunk, ws, (ah, al))
+            else:
+                n.attn_verify_slots(q16, q16l, H * D, *slot, S, k, li, H, Hkv, D, self.softmax_scale, nsplit, ws, (ah, al))
 
         if R <= 16:
             ks_down = self.ks_down and self.ks_min_rows <= R and inter >= 2 * hid
