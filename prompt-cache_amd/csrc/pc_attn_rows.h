@@ -1,0 +1,256 @@
+// Shared by the slot attention units (pc_slots.hip, pc_lookup_slots.hip): the MFMA tile loop over a wave's key slice with the
+// four-wave merge behind it, the merge of a row's split records, and the host side the four attention entries have in common.
+// The kernels built from this header are compiled in pc_lookup_slots.hip alone; pc_slots.hip reaches them through the launchers
+// declared here.
+#pragma once
+#include <hip/hip_fp16.h>
+#include <math.h>
+
+#include "pc_attn_common.h"
+#include "pc_lookup_common.h"
+
+namespace pcr {
+
+using pca::f4;
+using pca::h8;
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+// One description for pc_attn_decode_slots[_trunk] (k = 0) and pc_attn_verify_slots[_trunk]: row b * (k + 1) + i of the q pair is
+// draft row i of slot b, a (row, head) has ns_trunk + ns_own records -- the trunk launch's first -- and the plain entries have
+// no leader / trunk words and ns_trunk = 0.
+struct SlotAttnArgs {
+    const _Float16 *q_hi, *q_lo; int64_t q_ts;
+    const uint64_t* kv_base; const int32_t *cap, *len, *live, *leader, *trunk;
+    int S, k, layer, H, Hkv; float scale_log2; int ns_own, ns_trunk; float *part_o, *part_ml; _Float16 *of_hi, *of_lo;
+};
+
+// The argument checks of the four entries, messages prefixed with the entry's `name`, and the split of the workspace into
+// a.part_o / a.part_ml.  rows: an entry with k + 1 rows per slot, which needs q_token_stride >= H * D.
+int slot_attn_prepare(const char* name, bool rows, bool trunk, int ws_align, SlotAttnArgs& a, int D, float softmax_scale,
+                      void* workspace, int64_t workspace_bytes);
+// attn_verify_trunk_slots_kernel<D, RT>: the shared rows of every group, once for all rows of all members
+void launch_attn_trunk_slots(const SlotAttnArgs& a, int D, int RT, hipStream_t st);
+// attn_merge_slots_kernel<D, TRUNK>
+void launch_attn_merge_slots(const SlotAttnArgs& a, int D, bool trunk, hipStream_t st);
+// rope_append_slots_rows_kernel, grid (k + 1, S)
+void launch_rope_append_slots_rows(const float* qkv, int64_t ld, int layout, _Float16* q_hi, _Float16* q_lo, int64_t q_ts,
+                                   const float2* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len,
+                                   const int32_t* live, int S, int k, int layer, int H, int Hkv, int D, hipStream_t st);
+
+// ---- device side -------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void load8(const float* p, float (&x)[8]) {
+    const f4 a = *(const f4*)p, b = *(const f4*)(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x[e] = a[e]; x[e + 4] = b[e]; }
+}
+
+// LDS of a kernel that calls attn_rows_tiles: four wave-private V tiles, reused for the four waves' partials
+template <int D, int RT>
+constexpr int rows_lds_bytes() {
+    constexpr int tiles = 4 * pca::kTK * D * 2, merge = RT * (4 * (D / 16) * 64 * 4 + 4 * 16 * 2) * 4;
+    return tiles > merge ? tiles : merge;
+}
+
+// RT tiles of 16 query columns against the keys [k0, k1) of THIS WAVE, then the four waves' partials merged into one
+// (O, m, l) record per column.  The formulation is attn_small_kernel's (pc_attn.hip): S^T = K . Q^T and O^T += V^T . P^T on
+// mfma_f32_16x16x32_f16, Q and P as hi / lo pairs, fp32 online softmax; K fragments go from global memory into the A operand, V
+// through a wave-private LDS tile and back transposed, no barrier until the merge.
+// Lane (n, g) of a wave holds column n of every tile: its q row starts at q + qoff[rt], pad[rt] marks a column past the last one
+// (zero operand, nothing written), it sees keys below lim[rt] (MASK only; without MASK every key of the slice) and its record
+// is rec[rt].  A column that sees no key of the slice keeps (m = -1e30, l = 0).  A column of an MFMA tile depends on that
+// column's B operand only and every reduction runs in a fixed order: what a column gets does not depend on the other columns.
+// smem: rows_lds_bytes<D, RT>() bytes, 16-byte aligned.  All 256 threads of the workgroup must call.
+template <int D, int RT, bool MASK>
+__device__ __forceinline__ void attn_rows_tiles(const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo,
+                                                const int64_t (&qoff)[RT], const bool (&pad)[RT], const int (&lim)[RT],
+                                                const int64_t (&rec)[RT], const _Float16* kbase, const _Float16* vbase, int k0, int k1,
+                                                float scale_log2, char* smem, float* __restrict__ part_o,
+                                                float* __restrict__ part_ml) {
+    using pca::kTK;
+    constexpr int KS = D / 32, DB = D / 16, CPR = D / 8;
+    constexpr int LPW = kTK * CPR / 64;              // 16-byte V chunks per lane per tile
+    constexpr int kTileHalfs = kTK * D;
+    const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    h8 qf[RT][KS], qfl[RT][KS];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int64_t off = qoff[rt] + g * 8;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const h8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            const h8 a = *(const h8*)(q_hi + off + ks * 32), r = *(const h8*)(q_lo + off + ks * 32);
+            qf[rt][ks] = pad[rt] ? z : a;
+            qfl[rt][ks] = pad[rt] ? z : r;
+        }
+    }
+    f4 o[RT][DB];
+    float m_run[RT], l_run[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+        for (int db = 0; db < DB; ++db) { f4 z = {0.f, 0.f, 0.f, 0.f}; o[rt][db] = z; }
+        m_run[rt] = pca::kNegBig; l_run[rt] = 0.f;
+    }
+    _Float16* Vw = (_Float16*)smem + wave * kTileHalfs;            // this wave's V tile
+    char* Vwb = smem + wave * kTileHalfs * 2;
+
+    for (int key0 = k0; key0 < k1; key0 += kTK) {
+        // every load of the tile first, all unconditional (keys past k1 re-read the last valid row and are masked below)
+        pca::u32x4 kr[4][KS];
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            const int key = key0 + kb * 16 + n < k1 ? key0 + kb * 16 + n : k1 - 1;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) kr[kb][ks] = *(const pca::u32x4*)(kbase + (int64_t)key * D + ks * 32 + g * 8);
+        }
+        // V rows by LDS-DMA, rotated by 32 B per row on the source side (attn_small_kernel)
+#pragma unroll
+        for (int i = 0; i < LPW; ++i) {
+            const int c = lane + i * 64, row = c / CPR, pos = c - row * CPR;
+            const int col = (pos - 2 * (row & 7)) & (CPR - 1);
+            const int rr = key0 + row < k1 ? key0 + row : k1 - 1;
+            pca::glds16(vbase + (int64_t)rr * D + col * 8, Vwb + i * 1024);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        h8 pb[RT][2], pbl[RT][2];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const int vis = MASK && lim[rt] < k1 ? lim[rt] : k1;  // keys of this slice the column sees
+            float sv[4][4];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) {
+                f4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const h8 a = __builtin_bit_cast(h8, kr[kb][ks]);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qf[rt][ks], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qfl[rt][ks], acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = key0 + kb * 16 + g * 4 + r;
+                    const float s = key < vis ? acc[r] * scale_log2 : -INFINITY;
+                    sv[kb][r] = s;
+                    mx = fmaxf(mx, s);
+                }
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float m_new = fmaxf(m_run[rt], mx);             // (stays -1e30, finite, while the column has seen no key)
+            const float alpha = pca::fast_exp2(m_run[rt] - m_new);
+            float rs = 0.f;
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float e = pca::fast_exp2(sv[kb][r] - m_new);
+                    rs += e;
+                    const _Float16 eh = (_Float16)e;
+                    pb[rt][kb >> 1][(kb & 1) * 4 + r] = eh;
+                    pbl[rt][kb >> 1][(kb & 1) * 4 + r] = (_Float16)(e - (float)eh);
+                }
+            rs += __shfl_xor(rs, 16);
+            rs += __shfl_xor(rs, 32);
+            l_run[rt] = l_run[rt] * alpha + rs;
+#pragma unroll
+            for (int db = 0; db < DB; ++db) { o[rt][db][0] *= alpha; o[rt][db][1] *= alpha; o[rt][db][2] *= alpha; o[rt][db][3] *= alpha; }
+            m_run[rt] = m_new;
+        }
+        // the V tile has landed (this wave's own DMA: vmcnt covers it), back transposed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int vrow = t * 32 + g * 4 + (n >> 2);
+                const _Float16* vp = Vw + vrow * D + ((db * 16 + (n & 3) * 4 + 16 * (vrow & 7)) & (D - 1));
+                const pca::h4 lo = pca::lds_tr_read(vp);
+                const pca::h4 hi = pca::lds_tr_read(vp + 16 * D);
+                const h8 a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    o[rt][db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, pb[rt][t], o[rt][db], 0, 0, 0);
+                    o[rt][db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, pbl[rt][t], o[rt][db], 0, 0, 0);
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();             // (the next tile's DMA overwrites what these reads took)
+    }
+
+    // the four waves' partials through LDS, in wave order: one (O, m, l) record per column
+    __syncthreads();
+    float* mo = (float*)smem;                            // [RT][4][DB][64][4]
+    float* mml = mo + RT * 4 * DB * 64 * 4;              // [RT][4][16][2]
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+        for (int db = 0; db < DB; ++db) *(f4*)(mo + (((rt * 4 + wave) * DB + db) * 64 + lane) * 4) = o[rt][db];
+        if (g == 0) { mml[((rt * 4 + wave) * 16 + n) * 2] = m_run[rt]; mml[((rt * 4 + wave) * 16 + n) * 2 + 1] = l_run[rt]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        float mw[4], lw[4], mstar = pca::kNegBig;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            mw[w] = mml[((rt * 4 + w) * 16 + n) * 2]; lw[w] = mml[((rt * 4 + w) * 16 + n) * 2 + 1];
+            mstar = fmaxf(mstar, mw[w]);
+        }
+        float wt[4], lsum = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { wt[w] = pca::fast_exp2(mw[w] - mstar); lsum += wt[w] * lw[w]; }
+        if (!pad[rt]) {
+            constexpr int DPW = (DB + 3) / 4;                // head-dim blocks merged by one wave
+#pragma unroll
+            for (int j = 0; j < DPW; ++j) {
+                const int db = wave * DPW + j;
+                if (db < DB) {
+                    f4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        const f4 x = *(const f4*)(mo + (((rt * 4 + w) * DB + db) * 64 + lane) * 4);
+                        acc[0] += wt[w] * x[0]; acc[1] += wt[w] * x[1]; acc[2] += wt[w] * x[2]; acc[3] += wt[w] * x[3];
+                    }
+                    *(f4*)(part_o + rec[rt] * D + db * 16 + g * 4) = acc;
+                }
+            }
+            if (wave == 0 && g == 0) { part_ml[rec[rt] * 2] = mstar; part_ml[rec[rt] * 2 + 1] = lsum; }
+        }
+    }
+}
+
+// Merge of the records of a (row, head) in index (= key) order, one workgroup per (head, row), one thread per head dim; k + 1
+// rows per slot, nrec records per (row, head).  TRUNK: the first nsplit_t records are the trunk launch's, and a row of a slot on
+// its own (slot_trunk_rows 0) has none: its merge starts at record nsplit_t.  den > 0: every row sees its own key.
+template <int D, bool TRUNK>
+__global__ __launch_bounds__(D) void attn_merge_slots_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                             const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
+                                                             const int32_t* __restrict__ live, const int32_t* __restrict__ leader,
+                                                             const int32_t* __restrict__ trunk,
+                                                             const uint64_t* __restrict__ kv_base, int S, int k, int H, int nsplit_t,
+                                                             int nrec, _Float16* __restrict__ of_hi, _Float16* __restrict__ of_lo) {
+    const int h = blockIdx.x, r = blockIdx.y, d = threadIdx.x;
+    const int b = r / (k + 1);
+    if (!lookup_slot_runs(cap, len, live, b, k)) return;
+    const int64_t base = ((int64_t)r * H + h) * nrec;
+    int s0 = 0;
+    if constexpr (TRUNK) s0 = slot_trunk_rows(b, S, kv_base, cap, len, leader, trunk) > 0 ? 0 : nsplit_t;
+    float ms = pca::kNegBig;
+    for (int s = s0; s < nrec; ++s) ms = fmaxf(ms, part_ml[(base + s) * 2]);
+    float num = 0.0f, den = 0.0f;
+    for (int s = s0; s < nrec; ++s) {
+        const float wt = exp2f(part_ml[(base + s) * 2] - ms);
+        den = fmaf(wt, part_ml[(base + s) * 2 + 1], den);
+        num = fmaf(wt, part_o[(base + s) * D + d], num);
+    }
+    _Float16 hi, lo;
+    pc_split(num / den, hi, lo);
+    const int64_t off = pca::frag_off(r, h * D + d, H * D / 32);
+    of_hi[off] = hi;
+    of_lo[off] = lo;
+}
+
+}  // namespace pcr

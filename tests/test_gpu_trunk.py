@@ -182,6 +182,29 @@ def test_group_invariance_bit_for_bit(H, Hkv, D, ns_own, ns_trunk):
     assert torch.equal(res[0][1].view(torch.int16), res[1][1].view(torch.int16)), "lo planes differ"
 
 
+def test_a_member_in_the_second_pass_of_the_trunk_launch():
+    """Five members x 8 query heads of one kv head are 40 tile columns: the trunk launch takes two passes (32 columns each), their
+    number follows from S, and the last member lies in the second.  It gets what the references give, and bit for bit what the
+    same sequence gets as the only member of a group of one in a four-slot batch."""
+    n = base.native()
+    H, Hkv, D, ns_own, ns_trunk, T = 8, 1, 64, 1, 2, 65
+    rng = np.random.default_rng(40)
+    keys = [66, 70, 100, 129, 130]
+    c = Case(rng, [(k, 0, T, 1) for k in keys], H, Hkv, D)
+    out = c.run(n, ns_own, ns_trunk)
+    c.check(n, out, "second pass")
+    crowd = [n.from_act_frags(p, 5)[4].clone() for p in out]
+    spec = [(None, None, 0, 0)] * 4
+    spec[2] = (keys[4], 2, T, 1)
+    solo = Case(rng, spec, H, Hkv, D)
+    solo.arenas[2][:, :, :, :T] = c.arenas[0][:, :, :, :T]                 # the leader's trunk rows ...
+    solo.arenas[2][:, :, :, T:keys[4]] = c.arenas[4][:, :, :, T:keys[4]]   # ... and the member's own
+    solo.qh[2], solo.ql[2] = c.qh[4], c.ql[4]
+    alone = [n.from_act_frags(p, 4)[2] for p in solo.run(n, ns_own, ns_trunk)]
+    assert torch.equal(crowd[0].view(torch.int16), alone[0].view(torch.int16)), "hi planes differ"
+    assert torch.equal(crowd[1].view(torch.int16), alone[1].view(torch.int16)), "lo planes differ"
+
+
 @pytest.mark.parametrize("H,Hkv,D,ns_own", [(32, 32, 128, 4), (16, 2, 128, 8), (8, 1, 64, 2), (8, 8, 64, 1)])
 def test_no_trunk_is_pc_attn_decode_slots_bit_for_bit(H, Hkv, D, ns_own):
     n = base.native()
