@@ -48,6 +48,9 @@ def main():
                     help="prompt-lookup speculative decoding for the greedy single-prompt generation: draft up to K tokens (1..15; "
                          "try 7) from the context per step and verify them in one K+1-row forward (default: PC_LOOKUP, else off); "
                          "with --batch also for the batched loop (generate_batch(lookup=K): N * (K + 1) <= 64 rows per step)")
+    ap.add_argument("--lookup-sampled", action="store_true", default=None,
+                    help="with --lookup K: sampled generations (and greedy ones with a repetition penalty) draft and verify too, "
+                         "the sampler drawing every row (SampleLookupLoop; default: PC_LOOKUP_SAMPLE=1, else off)")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
@@ -59,7 +62,7 @@ def main():
         lm = cls(shape, random_init=True)
     preproc = [lm.get_formatter()]
     cache_engine = CacheEngine(a.max_ctx, lm, module_kv=a.module_kv, slots=max(1, a.batch))
-    gen_engine = GenerationEngine(lm, lookup=a.lookup)
+    gen_engine = GenerationEngine(lm, lookup=a.lookup, lookup_sampled=a.lookup_sampled)
     if a.schema:
         cache_engine.add_schema(read_file(a.schema, preproc), max_tokens=a.max_tokens)
         prompt_text = open(a.prompt_file).read()

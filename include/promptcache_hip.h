@@ -631,6 +631,27 @@ int pc_lookup_verify(const float* logits, int64_t ldl, int32_t vocab, int32_t ro
                      int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* past_len, const int32_t* ndraft,
                      int32_t* budget, int32_t* ring, int32_t* counter, int32_t ring_cap, void* stream);
 
+/* pc_lookup_verify_sample -- pc_lookup_verify for SAMPLED generations (csrc/pc_sample.hip): a prompt-lookup draft is a point
+ * mass, so verifying it needs no rejection-sampling residual -- only pc_sample_advance's draw on every row, with a random stream
+ * per TOKEN.  d = draws[0], nd = ndraft[0].  For every row i <= nd, t[i] = pc_sample_advance's draw on logits row i (same chain,
+ * thresholds, Gumbel-max and greedy rule, from the parameter block) with the random stream (params->seed, step d + i) under the
+ * penalty history history_bits + {ids[1], ..., ids[i]}: the draw the one-token loop makes for that position when drafts 1..i
+ * were emitted.  Rows i > nd are pads: never accepted, not drawn; their row_token / processed_out rows are unspecified.  acc =
+ * the largest c <= nd with t[i] == ids[1 + i] for all i < c; emit = min(acc + 1, budget[0]).  The record
+ * ring[(counter % ring_cap) * (rows + 1) ..] gets {emit, t[0..emit)} and counter += 1; when emit > 0, pc_lookup_verify's state
+ * updates on hist / hist_len / ids[0] / pos[0] / past_len[0] / budget[0] (the hist_cap clamp included), draws[0] += emit and the
+ * bits of t[0..emit) are set in history_bits.  With budget[0] = 0 the record is {0} and nothing else changes.  The draws of
+ * rejected rows are not consumed: step d + emit is drawn again by the next replay, for the token that then stands there, so
+ * token number n of a generation is always drawn at step n -- on identical logits the tokens are pc_sample_advance's, one for
+ * one.  row_bits uint32 [rows][ceil(vocab / 32)] and row_token int32 [rows] are scratch (row_bits must not alias history_bits);
+ * processed_out (optional, fp32 [rows][vocab]): the processed rows, as in pc_sample_advance.  1 <= rows <= 16, vocab < 2^24,
+ * ldl >= vocab; logits need only be 4-byte aligned.  Two launches: rows workgroups, then one wave.  At rows = 1 the token and the
+ * ids / pos / past_len / history words are pc_sample_advance's at counter = draws. */
+int pc_lookup_verify_sample(const float* logits, int64_t ldl, int32_t vocab, int32_t rows, const pc_sample_params* params_dev,
+                            uint32_t* history_bits, uint32_t* row_bits, int32_t* draws, int32_t* row_token, int32_t* hist,
+                            int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* past_len, const int32_t* ndraft,
+                            int32_t* budget, int32_t* ring, int32_t* counter, int32_t ring_cap, float* processed_out, void* stream);
+
 /* ---- batched decode over slots (csrc/pc_slots.hip, csrc/pc_sample.hip) ---------------------------------------------------------
  * A slot is one running sequence in a batch-1 KV arena of its own ([n_layers][2][Hkv][cap][head_dim] fp16, pc_kv_gather's dst).
  * Its state is one element of each of these DEVICE arrays over S <= 16 slots, so that one captured step serves every replay:

@@ -130,45 +130,12 @@ __global__ __launch_bounds__(1024) void lookup_argmax_kernel(const float* __rest
     }
 }
 
-// One wave.  Lane i holds a[i]; the accepted count is the first draft row the model disagrees with (rows at / behind ndraft are
-// pads: never accepted, whatever they hold).  Everything is read before anything is written; the ring record goes first.
+// One wave: lookup_accept_rule (pc_lookup_common.h) on the per-row argmax.
 __global__ __launch_bounds__(64) void lookup_accept_kernel(const int32_t* __restrict__ amax, int rows, int32_t* hist, int32_t* hist_len,
                                                            int hist_cap, int64_t* ids, int32_t* pos, int32_t* past, const int32_t* ndraft,
                                                            int32_t* budget, int32_t* ring, int32_t* ctr, int ring_cap) {
-    const int lane = threadIdx.x;
-    const int k = rows - 1;
-    int nd = ndraft[0];
-    nd = nd < 0 ? 0 : (nd > k ? k : nd);
-    const int a = lane < rows ? amax[lane] : 0;
-    const bool miss = lane < nd && (int64_t)a != ids[1 + lane];
-    const unsigned long long mm = __ballot(miss);
-    const int acc = mm ? (int)__builtin_ctzll(mm) : nd;
-    const int bud = budget[0];
-    const int L = hist_len[0];
-    const int c = ctr[0];
-    const int p0 = pos[0], pl = past[0];
-    int emit = acc + 1 < bud ? acc + 1 : bud;
-    int room = L < 0 ? 0 : hist_cap - L;                  // (never binding on a history sized for the budget)
-    room = room < 0 ? 0 : room;
-    emit = emit < room ? emit : room;
-    emit = emit < 0 ? 0 : emit;
-    const int last = __shfl(a, emit > 0 ? emit - 1 : 0);
-    int32_t* rec = ring + (int64_t)(((unsigned)c) % (unsigned)ring_cap) * (rows + 1);
-    if (lane == 0) rec[0] = emit;
-    if (lane < emit) {
-        rec[1 + lane] = a;
-        hist[L + lane] = a;
-    }
-    if (lane == 0) {
-        ctr[0] = c + 1;
-        if (emit > 0) {
-            hist_len[0] = L + emit;
-            ids[0] = last;
-            pos[0] = p0 + emit;
-            past[0] = pl + emit;
-            budget[0] = bud - emit;
-        }
-    }
+    const int a = (int)threadIdx.x < rows ? amax[threadIdx.x] : 0;
+    lookup_accept_rule(a, rows, hist, hist_len, hist_cap, ids, pos, past, ndraft, budget, ring, ctr, ring_cap);
 }
 
 // One wave per slot: lookup_accept_kernel's rule on the slot's words, cut behind the first emitted stop id, with the slot's

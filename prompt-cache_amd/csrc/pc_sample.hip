@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "pc_common.h"
+#include "pc_lookup_common.h"
 
 namespace {
 
@@ -481,6 +482,56 @@ __global__ __launch_bounds__(kThreads) void sample_advance_slots_each_kernel(
     }
 }
 
+// pc_lookup_verify_sample, first launch: one workgroup per row of the k + 1-row verify forward.  Row i <= ndraft is drawn as the
+// one-token loop would draw it had drafts 1..i been emitted: Philox step draws + i, and a history of its own -- row_bits[i] =
+// history_bits with the bits of ids[1..i] set, built here -- so that sample_row and the shared bitmap stay read-only.  Pad rows
+// (i > ndraft) leave at once (uniform over the workgroup).
+__global__ __launch_bounds__(kThreads) void lookup_sample_rows_kernel(const float* __restrict__ logits, int64_t ldl, int V, int rows,
+                                                                      const pc_sample_params* __restrict__ prm,
+                                                                      const uint32_t* __restrict__ hist, uint32_t* row_bits,
+                                                                      const int32_t* __restrict__ draws, const int64_t* __restrict__ ids,
+                                                                      const int32_t* __restrict__ ndraft, int32_t* row_token,
+                                                                      float* processed_out) {
+    const int i = blockIdx.x;
+    int nd = ndraft[0];
+    nd = nd < 0 ? 0 : (nd > rows - 1 ? rows - 1 : nd);
+    if (i > nd) return;
+    const int hw = (V + 31) >> 5;
+    uint32_t* rb = row_bits + (int64_t)i * hw;
+    for (int w = threadIdx.x; w < hw; w += kThreads) rb[w] = hist[w];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int j = 1; j <= i; ++j) {
+            const int64_t t = ids[j];
+            if (t >= 0 && t < V) rb[t >> 5] |= 1u << (t & 31);
+        }
+    }
+    __syncthreads();
+    const uint32_t step = (uint32_t)draws[0] + (uint32_t)i;
+    const int bi = sample_row(logits + (int64_t)i * ldl, V, prm, rb, prm->seed, step, processed_out ? processed_out + (int64_t)i * V : nullptr);
+    if (threadIdx.x == 0) row_token[i] = bi;
+}
+
+// ... second launch, one wave: lookup_accept_rule on the rows' draws, then the sampled loop's own words -- the emitted tokens'
+// bits into the shared bitmap and the random stream advanced by what was emitted (the draws of rejected rows are not consumed:
+// the next replay draws step draws + emit again, for the token that then stands there).
+__global__ __launch_bounds__(64) void lookup_sample_accept_kernel(const int32_t* __restrict__ row_token, int rows, int V, uint32_t* hist_bits,
+                                                                  int32_t* draws, int32_t* hist, int32_t* hist_len, int hist_cap,
+                                                                  int64_t* ids, int32_t* pos, int32_t* past, const int32_t* ndraft,
+                                                                  int32_t* budget, int32_t* ring, int32_t* ctr, int ring_cap) {
+    const int lane = threadIdx.x;
+    int nd = ndraft[0];
+    nd = nd < 0 ? 0 : (nd > rows - 1 ? rows - 1 : nd);
+    const int a = lane <= nd ? row_token[lane] : 0;        // (pad rows were not drawn)
+    const int d = draws[0];
+    const int emit = lookup_accept_rule(a, rows, hist, hist_len, hist_cap, ids, pos, past, ndraft, budget, ring, ctr, ring_cap);
+    for (int j = 0; j < emit; ++j) {
+        const int t = __shfl(a, j);
+        if (lane == 0 && t >= 0 && t < V) hist_bits[t >> 5] |= 1u << (t & 31);
+    }
+    if (lane == 0 && emit > 0) draws[0] = d + emit;
+}
+
 }  // namespace
 
 PC_EXPORT int pc_sample_advance(const float* logits, int32_t vocab, const pc_sample_params* params_dev, uint32_t* history_bits,
@@ -530,4 +581,25 @@ PC_EXPORT int pc_sample_advance_slots_each(const float* logits, int64_t logits_r
                        vocab, params_dev, seeds, history_bits, ids, pos, len, cap, live, budget, stop_ids, ring, counters, draws,
                        ring_cap, processed_out);
     return pc_check_launch("sample_advance_slots_each_kernel");
+}
+
+PC_EXPORT int pc_lookup_verify_sample(const float* logits, int64_t ldl, int32_t vocab, int32_t rows, const pc_sample_params* params_dev,
+                                      uint32_t* history_bits, uint32_t* row_bits, int32_t* draws, int32_t* row_token, int32_t* hist,
+                                      int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* past_len,
+                                      const int32_t* ndraft, int32_t* budget, int32_t* ring, int32_t* counter, int32_t ring_cap,
+                                      float* processed_out, void* stream) {
+    PC_REQUIRE(logits && params_dev && history_bits && row_bits && draws && row_token && hist && hist_len && ids && pos && past_len &&
+                   ndraft && budget && ring && counter, PC_ERR_ARG, "pc_lookup_verify_sample: null pointer");
+    PC_REQUIRE(rows >= 1 && rows <= 16 && ldl >= vocab && ring_cap > 0 && hist_cap >= 1, PC_ERR_ARG,
+               "pc_lookup_verify_sample: need 1 <= rows <= 16, ldl >= vocab, ring_cap > 0, hist_cap >= 1");
+    PC_REQUIRE(vocab > 0 && vocab < (1 << 24), PC_ERR_ARG, "pc_lookup_verify_sample: vocab must be in [1, 2^24)");
+    PC_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)params_dev & 7) == 0, PC_ERR_ARG,
+               "pc_lookup_verify_sample: logits must be 4-byte and params 8-byte aligned");
+    hipLaunchKernelGGL(lookup_sample_rows_kernel, dim3(rows), dim3(kThreads), 0, (hipStream_t)stream, logits, ldl, vocab, rows,
+                       params_dev, history_bits, row_bits, draws, ids, ndraft, row_token, processed_out);
+    int rc = pc_check_launch("lookup_sample_rows_kernel");
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(lookup_sample_accept_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, row_token, rows, vocab, history_bits,
+                       draws, hist, hist_len, hist_cap, ids, pos, past_len, ndraft, budget, ring, counter, ring_cap);
+    return pc_check_launch("lookup_sample_accept_kernel");
 }

@@ -167,6 +167,8 @@ SIGNATURES = {
     "pc_sample_advance": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pc_lookup_draft": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "pc_lookup_verify": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "pc_lookup_verify_sample": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _i32, _vp, _vp]),
     "pc_lookup_draft_slots": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "pc_rope_append_slots_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                             _vp]),
@@ -775,6 +777,25 @@ def lookup_verify(logits, ldl: int, vocab: int, rows: int, row_argmax, hist, his
                                  hist.numel(), ids.data_ptr(), pos.data_ptr(), past.data_ptr(), ndraft.data_ptr(), budget.data_ptr(),
                                  ring.data_ptr(), counter.data_ptr(), ring_cap, current_stream() if stream is None else stream)
     check(rc, "pc_lookup_verify")
+
+
+def lookup_verify_sample(logits, ldl: int, vocab: int, rows: int, params, history, row_bits, draws, row_token, hist, hist_len, ids,
+                         pos, past, ndraft, budget, ring, counter, ring_cap: int, processed_out=None,
+                         stream: Optional[int] = None) -> None:
+    """Tail of a sampled prompt-lookup step (pc_lookup_verify_sample): pc_sample_advance's draw on every real row at the step of
+    its own token, longest agreeing draft prefix + one token, state advance.  ``params`` / ``history``: as in ``sample_advance``;
+    ``row_bits`` int32 [rows][ceil(vocab / 32)] and ``row_token`` int32 [rows] are scratch; ``draws``: the Philox step of the next
+    token; ``ring`` int32 [ring_cap][rows + 1] takes the record {count, tokens...}."""
+    hw = (vocab + 31) // 32
+    assert ring.numel() >= ring_cap * (rows + 1) and row_token.numel() >= rows and ids.numel() >= rows
+    assert row_bits.numel() >= rows * hw and history.numel() >= hw and row_bits.data_ptr() != history.data_ptr()
+    assert processed_out is None or processed_out.numel() >= rows * vocab
+    rc = load().pc_lookup_verify_sample(logits.data_ptr(), ldl, vocab, rows, params.data_ptr(), history.data_ptr(), row_bits.data_ptr(),
+                                        draws.data_ptr(), row_token.data_ptr(), hist.data_ptr(), hist_len.data_ptr(), hist.numel(),
+                                        ids.data_ptr(), pos.data_ptr(), past.data_ptr(), ndraft.data_ptr(), budget.data_ptr(),
+                                        ring.data_ptr(), counter.data_ptr(), ring_cap, _ptr(processed_out),
+                                        current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_verify_sample")
 
 
 def rope_append_slots(qkv, ld: int, in_layout: int, q_hi, q_lo, q_ts: int, cs, kv_base, cap, length, live, S: int, layer: int,

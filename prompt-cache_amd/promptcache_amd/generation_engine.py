@@ -94,12 +94,17 @@ class GenerationEngine:
     # (model/llama_hip.py SampleLoop; PC_DEVICE_SAMPLE=0: step through lm() and torch's sampler)
     device_sample_loop = os.environ.get("PC_DEVICE_SAMPLE", "1") != "0"
 
-    def __init__(self, lm: LanguageModel, verbose: bool = False, lookup: Optional[int] = None):
+    def __init__(self, lm: LanguageModel, verbose: bool = False, lookup: Optional[int] = None,
+                 lookup_sampled: Optional[bool] = None):
         """``lookup`` = k > 0 (None: ``PC_LOOKUP``, default 0 = off): plain-greedy generations draft up to k tokens per step by
-        prompt lookup and verify them in one k+1-row forward (model/llama_hip.py LookupLoop) where the model offers it."""
+        prompt lookup and verify them in one k+1-row forward (model/llama_hip.py LookupLoop) where the model offers it.
+        ``lookup_sampled`` (None: ``PC_LOOKUP_SAMPLE=1``, default off): with ``lookup`` > 0, every other generation of
+        ``generate`` -- sampled, or greedy with a repetition penalty -- does the same with the sampler on every row
+        (SampleLookupLoop) instead of the one-token SampleLoop; on identical logits the tokens are SampleLoop's."""
         self.lm = lm
         self.verbose = verbose
         self.lookup = int(os.environ.get("PC_LOOKUP", "0")) if lookup is None else int(lookup)
+        self.lookup_sampled = os.environ.get("PC_LOOKUP_SAMPLE", "0") == "1" if lookup_sampled is None else bool(lookup_sampled)
 
     # -- pieces of the loop ---------------------------------------------------------------------
     def _forward(self, ids: List[int], positions: List[int], past) -> Tuple[torch.Tensor, object, float]:
@@ -175,6 +180,10 @@ class GenerationEngine:
         # host reads step after step, one replay ahead while the step in flight cannot exhaust the budget (a replay behind the
         # last token would stream the weights for nothing); tokens of a step behind a stop are dropped.
         want_lookup = want_loop and self.lookup > 0 and hasattr(hf, "lookup_loop")
+        # ... and with ``lookup_sampled`` the other generations do the same in the sampled lookup loop (SampleLookupLoop): the
+        # first token, the seed, the history and the host's stop handling per token are the sampled loop's, the steps the lookup's
+        want_lookup_sample = (want_sample and self.lookup > 0 and self.lookup_sampled and hasattr(hf, "lookup_loop") and
+                              hasattr(hf, "lookup_available") and hf.lookup_available())
         lstep, got, queued = 0, 0, []
         loop_total = params.max_new_tokens - 1
 
@@ -249,6 +258,9 @@ class GenerationEngine:
                                               self._lookup_corpus(cache, token_ids))
                     elif want_loop:
                         loop = hf.greedy_loop(past, token, first_free + 1, params.max_new_tokens)
+                    elif want_lookup_sample:
+                        loop = hf.lookup_loop(past, token, first_free + 1, loop_total, min(self.lookup, 15),
+                                              self._lookup_corpus(cache, token_ids), params=params, seed=seed, history_ids=output_ids)
                     else:
                         loop = hf.sample_loop(past, token, first_free + 1, params.max_new_tokens, params, seed, output_ids)
                     if loop is not None:

@@ -276,6 +276,7 @@ class LookupLoop:
     ROWS_MAX = 16
     multi = True                     # a step yields a list of tokens (GenerationEngine)
     device_loop = os.environ.get("PC_DEVICE_LOOKUP", "1") != "0"
+    graph_tag = ()                   # appended to the step's graph key (a subclass with another last stage)
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3):
@@ -316,9 +317,14 @@ class LookupLoop:
         n.lookup_draft(st["hist"], st["hist_len"], st["ids"], st["pos"], st["ndraft"], k, self.nmax)
         out = m._forward_skinny(st["ids"][:k + 1], st["pos"][:k + 1], st["past"], self.arena, 1, k + 1, self.kv_ceiling - (k + 1),
                                 False, None)
-        n.lookup_verify(out, V, V, k + 1, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["past"], st["ndraft"],
-                        st["budget"], st["ring"], st["ctr"], self.RING)
+        self._verify(out, V)
         return out
+
+    def _verify(self, out, V: int) -> None:
+        """The last stage of a step: which rows' tokens are emitted, and the state advance."""
+        st = self.st
+        _native.lookup_verify(out, V, V, self.k + 1, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["past"],
+                              st["ndraft"], st["budget"], st["ring"], st["ctr"], self.RING)
 
     @torch.inference_mode()
     def enqueue(self) -> int:
@@ -367,6 +373,33 @@ class LookupLoop:
         e0, e1, done = self.events[i]
         done.synchronize()
         return e0.elapsed_time(e1)
+
+
+class SampleLookupLoop(LookupLoop):
+    """Sampled decode with prompt-lookup drafts, on the device: ``LookupLoop`` whose last stage is
+    ``pc_lookup_verify_sample``.  Row i of a step is drawn by ``pc_sample_advance``'s rule at Philox step ``draws + i`` under the
+    penalty history it would have had drafts 1..i been emitted; the draws that equal their drafts are accepted and the first one
+    that differs is emitted as it is, so token number n of a generation is drawn at step n whatever the drafts were: on identical
+    logits the tokens are ``SampleLoop``'s, one for one.  The state gains the parameter block and history bitmap of
+    ``SampleLoop``, ``draws`` (1: the first token was drawn at step 0, ``LlamaHIP.sample_token``) and per-row scratch.  One
+    graph serves every parameter set; protocol, memory-safety argument and the stepped mode are ``LookupLoop``'s."""
+
+    graph_tag = ("sample",)
+
+    @torch.inference_mode()
+    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, k: int, corpus_ids, params,
+                 seed: int, history_ids, nmax: int = 3):
+        super().__init__(model, arena, token, position, max_new, k, corpus_ids, nmax)
+        st = self.st
+        model._lookup_sample_state(st)
+        model._sample_state_fill(st, params, seed, history_ids)
+        st["draws"].fill_(1)
+
+    def _verify(self, out, V: int) -> None:
+        st = self.st
+        _native.lookup_verify_sample(out, V, V, self.k + 1, st["params"], st["bits"], st["row_bits"], st["draws"], st["row_token"],
+                                     st["hist"], st["hist_len"], st["ids"], st["pos"], st["past"], st["ndraft"], st["budget"],
+                                     st["ring"], st["ctr"], self.RING)
 
 
 class SlotLoop:
@@ -1989,7 +2022,7 @@ class LlamaHIP:
         """Parameter block and history bitmap of a sampled generation into the state ``st`` (ordered on the current stream)."""
         blk = sample_params_block(params, seed)
         st["params"].copy_(torch.frombuffer(bytearray(blk), dtype=torch.uint8))
-        st["hist"].copy_(_history_bits(history_ids, self.config.vocab_size))
+        st["bits" if "bits" in st else "hist"].copy_(_history_bits(history_ids, self.config.vocab_size))
 
     @torch.inference_mode()
     def sample_token(self, logits_row: torch.Tensor, params, seed: int, history_ids, step: int = 0) -> int:
@@ -2103,11 +2136,31 @@ class LlamaHIP:
             st["hist"] = torch.zeros(cap, dtype=torch.int32, device=dev)
         return st
 
+    @torch.inference_mode()
+    def _lookup_sample_state(self, st: dict) -> None:
+        """What ``SampleLookupLoop`` adds to the lookup state ``st``, once per model: pc_lookup_verify_sample's parameter block,
+        history bitmap (``bits``: ``hist`` is the token history here), ``draws`` word and per-row scratch."""
+        if "bits" in st:
+            return
+        dev, R = self.device, LookupLoop.ROWS_MAX
+        V = self.config.vocab_size
+        hw = (V + 31) // 32
+        st.update(params=torch.zeros(ctypes.sizeof(_native.SampleParams), dtype=torch.uint8, device=dev),
+                  bits=torch.zeros(hw, dtype=torch.int32, device=dev), draws=torch.zeros(1, dtype=torch.int32, device=dev),
+                  row_bits=torch.zeros(R * hw, dtype=torch.int32, device=dev), row_token=torch.zeros(R, dtype=torch.int32, device=dev))
+        # first launch of the kernels outside any capture, as in _lookup_state: zeroed words, budget 0 -> an empty record
+        warm = torch.zeros(1, dtype=torch.int32, device=dev)
+        zero = {n: torch.zeros_like(st[n]) for n in ("hist_len", "ids", "pos", "past", "ndraft", "budget", "ctr")}
+        _native.lookup_verify_sample(torch.zeros(V, dtype=torch.float32, device=dev), V, V, 1, st["params"], st["bits"],
+                                     st["row_bits"], st["draws"], st["row_token"], warm, zero["hist_len"], zero["ids"], zero["pos"],
+                                     zero["past"], zero["ndraft"], zero["budget"], torch.zeros(2, dtype=torch.int32, device=dev),
+                                     zero["ctr"], 1)
+
     def _lookup_graph(self, loop: "LookupLoop"):
         """The captured graph of ONE lookup step of ``loop`` (draft + ``k + 1``-row forward + verify), one per key."""
         arena, st, k = loop.arena, loop.st, loop.k
         key = ("loop", "lookup", k, arena.buf.data_ptr(), arena.cap, self._nsplit_key(1, k + 1, loop.kv_ceiling), loop.kv_ceiling,
-               loop.nmax, st["hist"].data_ptr(), st["hist"].numel(), self.fuse_norm)
+               loop.nmax, st["hist"].data_ptr(), st["hist"].numel(), self.fuse_norm) + loop.graph_tag
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2126,12 +2179,22 @@ class LlamaHIP:
         self._graphs[key] = ent
         return ent
 
-    def lookup_loop(self, past, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3):
+    def lookup_loop(self, past, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3, params=None,
+                    seed: int = 0, history_ids=None):
         """A device-side greedy decode loop with prompt-lookup drafts (``LookupLoop``: up to ``k + 1`` tokens per step, ``k`` in
         1..15) over the arena behind ``past``.  ``corpus_ids``: the ids the drafts may copy from besides the output itself --
         the context in key order; the history starts as ``corpus_ids ++ [token]``.  ``max_new``: the most tokens the loop
         emits.  None where ``greedy_loop`` gives None; a plain ``GreedyLoop`` where the model has no lookup step
-        (``lookup_available``)."""
+        (``lookup_available``).  With ``params`` (and ``seed`` / ``history_ids`` as in ``sample_loop``) the loop is the sampled one,
+        ``SampleLookupLoop``: ``SampleLoop``'s tokens, up to ``k + 1`` per step; a ``SampleLoop`` where the model has no lookup
+        step."""
+        if params is not None:
+            history_ids = [int(token)] if history_ids is None else history_ids
+            if not self.lookup_available():
+                return self.sample_loop(past, token, position, max_new, params, seed, history_ids)
+            arena = self._loop_arena(past)
+            return None if arena is None else SampleLookupLoop(self, arena, token, position, max_new, k, corpus_ids, params, seed,
+                                                               history_ids, nmax)
         if not self.lookup_available():
             return self.greedy_loop(past, token, position, max_new)
         arena = self._loop_arena(past)
