@@ -42,6 +42,11 @@ class GenerationParameters:
     def greedy(self) -> bool:
         return self.temperature < 1e-5 or self.top_p < 1e-8
 
+    @property
+    def plain_greedy(self) -> bool:
+        """Greedy decoding whose processed argmax is the raw argmax: the greedy device loops; everything else is sampled."""
+        return self.greedy and self.repetition_penalty <= 1.0
+
     def get_logits_processor(self):
         """Same processor chain, same order and thresholds as the reference (:32-42)."""
         from transformers.generation import logits_process as lp
@@ -85,6 +90,57 @@ class _Timer:
         torch.cuda.synchronize()
         self.ms = self.t0.elapsed_time(self.t1)
         return False
+
+
+class _Stream:
+    """What the host keeps per sequence, and the one rule for a token that came back from the device (``emit``).  ``index`` is
+    the sequence's number in ``generate_batch`` / ``serve``; ``slot``, ``k`` (its index in the loop) and ``device_stops`` (the
+    stop ids the device holds, None: all) are ``serve``'s; a loop is built or armed from ``seed``, ``past`` and ``first_free``."""
+
+    def __init__(self, render, params: GenerationParameters, stream_interval: int, prompt_ids: List[int], first_free: int,
+                 index: int = 0, seed: int = 0, slot: int = 0, device_stops: Optional[List[int]] = None):
+        self.render, self.params, self.stream_interval = render, params, stream_interval
+        self.output_ids, self.new_ids = list(prompt_ids), []
+        self.first_free, self.index, self.seed, self.slot, self.k, self.past = first_free, index, seed, slot, None, None
+        self.device_stops = params.stop_token_ids if device_stops is None else device_stops
+        self.total_ms = self.ttft_ms = 0.0
+        self.last_step, self.done = params.max_new_tokens - 1, False
+
+    def emit(self, token: int) -> Optional[Output]:
+        """Take the next token: append it, test the stop ids, and at a streaming point (every ``stream_interval`` tokens, the last
+        step, a stop id) render the text, cut it at a stop string and hold it back while its tail may still grow into one.
+        Sets ``done``; -> the Output to yield, if any.  The step is the number of tokens taken before this one."""
+        step = len(self.new_ids)
+        self.output_ids.append(token)
+        self.new_ids.append(token)
+        fin = token in self.params.stop_token_ids
+        out = None
+        if step % self.stream_interval == 0 or step == self.last_step or fin:
+            text, new_text, hit, partial = self.render(self.output_ids, self.new_ids, self.params.stop_str)
+            fin = fin or hit
+            if not partial:
+                out = Output(text, new_text, self.total_ms, self.ttft_ms)
+        self.done = fin or step >= self.last_step
+        return out
+
+    def ended_on_the_host(self, token: int) -> bool:
+        """After ``emit(token)``: the sequence ended for a reason its device loop cannot know -- a stop string, a stop id the
+        device does not hold -- so neither one of the device's stop ids nor the budget: the host must switch the slot off."""
+        return self.done and token not in self.device_stops and len(self.new_ids) - 1 != self.last_step
+
+
+def _reader(loop):
+    """-> ``(read, k)`` over any device loop: ``read(i)`` / ``read(j, i)`` gives the list of tokens of step ``i`` (of sequence
+    ``j``), empty when nothing more will come (the budget ran out, the slot is off), and a step gives ``k + 1`` tokens at most.
+    A one-token loop (``token``: GreedyLoop, SampleLoop, SlotLoop) is a multi-token loop (``tokens``: LookupLoop,
+    SampleLookupLoop, LookupSlotLoop) with k = 0.  A new kind of loop plugs in here."""
+    if hasattr(loop, "tokens"):
+        return loop.tokens, loop.k
+
+    def one(*at):
+        token = loop.token(*at)
+        return [] if token is None else [token]
+    return one, 0
 
 
 class GenerationEngine:
@@ -148,6 +204,82 @@ class GenerationEngine:
                 ids += t
         return ids + [int(x) for x in token_ids]
 
+    # -- the two pumps ----------------------------------------------------------------------------
+    @staticmethod
+    def _pump(loop, total: int):
+        """Read a single-sequence device loop: yields ``(token, ms)`` until ``total`` tokens came or a step is empty.  ``ms`` is the
+        step's device time on its first token and 0.0 on the others.  Every step of such a loop is one hipGraph replay that also
+        picks the token(s) and feeds the next replay (model/llama_hip.py GreedyLoop, SampleLoop: one token; LookupLoop,
+        SampleLookupLoop: 1..k+1 tokens).  The host keeps ONE replay in flight ahead of the step it reads, so the GPU never waits
+        for the host's stop handling, but only while the step in flight cannot exhaust the budget (a replay behind the last token
+        would stream the weights for nothing).  The consumer stops reading at a stop; a step enqueued past it, and the tokens of
+        a step behind it, are simply discarded."""
+        read, k = _reader(loop)
+        got = i = 0
+        while got < total:
+            if loop.n <= i:
+                loop.enqueue()
+            if loop.n == i + 1 and got + k + 1 < total:
+                loop.enqueue()                                     # the replay AFTER the one whose tokens are read below
+            toks, ms = read(i), loop.elapsed_ms(i)
+            if not toks:
+                return
+            for token in toks:
+                yield token, ms
+                ms = 0.0
+            got += len(toks)
+            i += 1
+
+    @staticmethod
+    def _pump_slots(loop, seqs: List[_Stream]):
+        """Read a batched device loop (SlotLoop, LookupSlotLoop) until every stream of ``seqs`` (``seqs[j]`` is sequence j of the
+        loop) is done; yields ``(index, Output)``.  One replay ahead as in ``_pump``, while the step in flight cannot exhaust
+        every budget.  A sequence ends at a stop id or its budget, which the device sees too, at an empty step (the device
+        switched the slot off) or for a reason only the host knows (``_Stream.ended_on_the_host``): then the host switches
+        the slot off between replays (``loop.kill``) and drops the rest of the step."""
+        read, k = _reader(loop)
+        i = 0
+        while not all(st.done for st in seqs):
+            room = max(st.last_step - (len(st.new_ids) - 1) for st in seqs if not st.done)
+            if loop.n <= i:
+                loop.enqueue()
+            if loop.n == i + 1 and room > k + 1:
+                loop.enqueue()                                     # the replay AFTER the one whose tokens are read below
+            ms = loop.elapsed_ms(i)
+            for j, st in enumerate(seqs):
+                if st.done:
+                    continue
+                toks = read(j, i)
+                if not toks:
+                    st.done = True
+                    continue
+                st.total_ms += ms
+                for token in toks:
+                    out = st.emit(token)
+                    kill = st.ended_on_the_host(token)
+                    if kill and not k:                             # (a one-token loop is told before the yield, a multi-token
+                        loop.kill(j)                               # loop after it: each as it was before there was one pump)
+                    if out is not None:
+                        yield st.index, out
+                    if kill and k:
+                        loop.kill(j)
+                    if st.done:
+                        break
+            i += 1
+
+    def _first_token(self, st: _Stream, token_ids: List[int], position_ids: List[int], cache) -> Optional[Output]:
+        """Prefill and first token of a sequence of ``generate_batch`` / ``serve``: the forward ``generate`` runs, the token drawn as
+        ``generate`` draws it (argmax, or step 0 of the random stream of ``st.seed`` on the device).  Fills ``st.past``."""
+        logits, st.past, ms = self._forward(token_ids, position_ids, cache)
+        st.ttft_ms = st.total_ms = ms
+        if self.verbose:
+            print(f"Prefill latency: {ms:.2f} ms")
+        if st.params.plain_greedy:
+            token = self._pick(st.params.get_logits_processor()(None, logits[:, -1, :])[0], True)
+        else:
+            token = self.lm.hf_model.sample_token(logits[0, -1], st.params, st.seed, st.output_ids)
+        return st.emit(token)
+
     # -- the generator ----------------------------------------------------------------------------
     @torch.inference_mode()
     def generate(self, token_ids: List[int], position_ids: List[int], params: GenerationParameters,
@@ -156,143 +288,110 @@ class GenerationEngine:
         processors = params.get_logits_processor()
         prompt_positions = list(position_ids)
         first_free = max(prompt_positions) + 1
-        output_ids, new_ids = list(token_ids), []
-        total_ms = ttft_ms = 0.0
-        past = None
+        st = _Stream(self._render, params, stream_interval, token_ids, first_free)
+        loop = past = None
 
-        # Greedy decoding whose processed argmax is the raw argmax (no repetition penalty: temperature, top-p and top-k
-        # all keep the largest logit largest) runs as a device-side loop when the model offers one: every step is one
-        # hipGraph replay that also picks the token and feeds it to the next replay (model/llama_hip.py GreedyLoop).
-        # The host keeps ONE replay in flight ahead of the token it is looking at, so stop conditions are evaluated
-        # exactly as below while the GPU never waits for the host; a step enqueued past a stop is simply discarded.
-        #
-        # Every other generation runs as the sampled device loop (model/llama_hip.py SampleLoop): the last node of each replay
-        # applies the reference's logits chain and draws the token on the GPU (pc_sample_advance).  The first token is drawn
-        # from the prefill logits by the same kernel at step 0 of the same random stream, whose seed comes from torch's default
-        # generator, so torch.manual_seed governs reproducibility.
-        loop = None
+        # Plain-greedy generations decode in the greedy device loop when the model offers one, every other generation in the
+        # sampled device loop: the last node of each replay applies the reference's logits chain and draws the token on the GPU
+        # (pc_sample_advance).  Its first token is drawn from the prefill logits by the same kernel at step 0 of the same random
+        # stream, whose seed comes from torch's default generator, so torch.manual_seed governs reproducibility.
         hf = getattr(self.lm, "hf_model", None)
-        plain_greedy = params.greedy and params.repetition_penalty <= 1.0
+        plain_greedy = params.plain_greedy
         want_loop = plain_greedy and not use_full_position_ids and hasattr(hf, "greedy_loop") and self.device_greedy_loop
         want_sample = not plain_greedy and not use_full_position_ids and hasattr(hf, "sample_loop") and self.device_sample_loop
         seed = int(torch.randint(0, 2 ** 62, (1,))) if want_sample else 0
-        # ... and with ``lookup`` = k > 0 a plain-greedy generation runs the lookup loop instead: a step yields 1..k+1 tokens.  The
-        # host reads step after step, one replay ahead while the step in flight cannot exhaust the budget (a replay behind the
-        # last token would stream the weights for nothing); tokens of a step behind a stop are dropped.
+        # ... and with ``lookup`` = k > 0 a plain-greedy generation runs the lookup loop instead: a step yields 1..k+1 tokens.
         want_lookup = want_loop and self.lookup > 0 and hasattr(hf, "lookup_loop")
         # ... and with ``lookup_sampled`` the other generations do the same in the sampled lookup loop (SampleLookupLoop): the
         # first token, the seed, the history and the host's stop handling per token are the sampled loop's, the steps the lookup's
         want_lookup_sample = (want_sample and self.lookup > 0 and self.lookup_sampled and hasattr(hf, "lookup_loop") and
                               hasattr(hf, "lookup_available") and hf.lookup_available())
-        lstep, got, queued = 0, 0, []
-        loop_total = params.max_new_tokens - 1
+
+        def pick(logits):
+            if want_sample:                                        # (the first token only: the loop draws every later one)
+                return hf.sample_token(logits[0, -1], params, seed, st.output_ids)
+            history = torch.as_tensor([st.output_ids], device=self.lm.device) if params.repetition_penalty > 1.0 else None
+            return self._pick(processors(history, logits[:, -1, :])[0], params.greedy)
+
+        def host_steps():
+            nonlocal past
+            while not st.done:
+                step = len(st.new_ids)
+                positions = (prompt_positions + list(range(first_free, first_free + step))) if use_full_position_ids \
+                    else [first_free + step]
+                logits, past, ms = self._forward([st.new_ids[-1]], positions, past)
+                yield pick(logits), ms
 
         try:
-            for step in range(params.max_new_tokens):
-                if loop is not None:
-                    if getattr(loop, "multi", False):
-                        if not queued:
-                            if loop.n <= lstep:
-                                loop.enqueue()
-                            if loop.n == lstep + 1 and got + loop.k + 1 < loop_total:
-                                loop.enqueue()                         # the replay AFTER the one whose tokens are read below
-                            queued = loop.tokens(lstep)
-                            total_ms += loop.elapsed_ms(lstep)
-                            got += len(queued)
-                            lstep += 1
-                            if not queued:                             # (the device budget ran out: nothing more will come)
-                                break
-                        token = queued.pop(0)
-                    else:
-                        if loop.n <= step and loop.n < params.max_new_tokens - 1:
-                            loop.enqueue()                             # the replay AFTER the one whose token is read below
-                        token = loop.token(step - 1)
-                        total_ms += loop.elapsed_ms(step - 1)
-                    output_ids.append(token)
-                    new_ids.append(token)
-                    done = token in params.stop_token_ids
-                    if step % stream_interval == 0 or step == params.max_new_tokens - 1 or done:
-                        text, new_text, hit, partial = self._render(output_ids, new_ids, params.stop_str)
-                        done = done or hit
-                        if not partial:
-                            yield Output(text, new_text, total_ms, ttft_ms)
-                    if done:
-                        break
-                    continue
-                if step == 0:
-                    if cache is not None and not isinstance(cache, StagedKV):
-                        # a plain list of [Hkv, S, D] views: add the batch dim like the reference does (:101-102)
-                        cache = [(k.unsqueeze(0), v.unsqueeze(0)) if k.dim() == 3 else (k, v) for k, v in cache]
-                    logits, past, ms = self._forward(list(token_ids), prompt_positions, cache)
-                    ttft_ms = ms
-                    if self.verbose:
-                        print(f"Prefill latency: {ms:.2f} ms")
+            if params.max_new_tokens < 1:
+                return
+            # 1. prefill and first token
+            if cache is not None and not isinstance(cache, StagedKV):
+                # a plain list of [Hkv, S, D] views: add the batch dim like the reference does (:101-102)
+                cache = [(k.unsqueeze(0), v.unsqueeze(0)) if k.dim() == 3 else (k, v) for k, v in cache]
+            logits, past, ms = self._forward(list(token_ids), prompt_positions, cache)
+            st.ttft_ms = st.total_ms = ms
+            if self.verbose:
+                print(f"Prefill latency: {ms:.2f} ms")
+            if want_sample:
+                want_sample = hf.can_loop(past)
+            out = st.emit(pick(logits))
+            if out is not None:
+                yield out
+            # 2. a device loop, where there is one and something is left to decode
+            if not st.done and (want_loop or want_sample):
+                # the first decoded token sits at position first_free + 1 (the reference's loop index starts at 1, :132)
+                token, position = st.new_ids[0], first_free + 1
+                if want_lookup or want_lookup_sample:
+                    sampled = dict(params=params, seed=seed, history_ids=st.output_ids) if want_lookup_sample else {}
+                    loop = hf.lookup_loop(past, token, position, st.last_step, min(self.lookup, 15),
+                                          self._lookup_corpus(cache, token_ids), **sampled)
+                elif want_loop:
+                    loop = hf.greedy_loop(past, token, position, params.max_new_tokens)
                 else:
-                    positions = (prompt_positions + list(range(first_free, first_free + step))) if use_full_position_ids \
-                        else [first_free + step]
-                    logits, past, ms = self._forward([new_ids[-1]], positions, past)
-                total_ms += ms
-
-                if step == 0 and want_sample:
-                    want_sample = hf.can_loop(past)
-                if want_sample:                                    # (step 0 only: the loop draws every later token)
-                    token = hf.sample_token(logits[0, -1], params, seed, output_ids)
-                else:
-                    history = torch.as_tensor([output_ids], device=self.lm.device) if params.repetition_penalty > 1.0 else None
-                    token = self._pick(processors(history, logits[:, -1, :])[0], params.greedy)
-                output_ids.append(token)
-                new_ids.append(token)
-
-                done = token in params.stop_token_ids
-                if step % stream_interval == 0 or step == params.max_new_tokens - 1 or done:
-                    text, new_text, hit, partial = self._render(output_ids, new_ids, params.stop_str)
-                    done = done or hit
-                    if not partial:
-                        yield Output(text, new_text, total_ms, ttft_ms)
-                if done:
+                    loop = hf.sample_loop(past, token, position, params.max_new_tokens, params, seed, st.output_ids)
+            # 3. the rest: that loop's tokens, or one forward per token
+            for token, ms in (host_steps() if loop is None else self._pump(loop, st.last_step)):
+                st.total_ms += ms
+                out = st.emit(token)
+                if out is not None:
+                    yield out
+                if st.done:                                        # (before the source is asked for more)
                     break
-                if step == 0 and (want_loop or want_sample) and params.max_new_tokens > 1:
-                    # the first decoded token sits at position first_free + 1 (the reference's loop index starts at 1, :132)
-                    if want_lookup:
-                        loop = hf.lookup_loop(past, token, first_free + 1, loop_total, min(self.lookup, 15),
-                                              self._lookup_corpus(cache, token_ids))
-                    elif want_loop:
-                        loop = hf.greedy_loop(past, token, first_free + 1, params.max_new_tokens)
-                    elif want_lookup_sample:
-                        loop = hf.lookup_loop(past, token, first_free + 1, loop_total, min(self.lookup, 15),
-                                              self._lookup_corpus(cache, token_ids), params=params, seed=seed, history_ids=output_ids)
-                    else:
-                        loop = hf.sample_loop(past, token, first_free + 1, params.max_new_tokens, params, seed, output_ids)
-                    if loop is not None:
-                        loop.enqueue()
         finally:
             # also when the consumer abandons the generator at a yield (GeneratorExit): a look-ahead replay enqueued past the last
             # token the caller saw wrote one arena row too many, and the model's loop state must be released
             if loop is not None:
-                loop.close(len(new_ids) - 1)                 # steps of the loop that produced a token (the first came from the prefill)
+                loop.close(len(st.new_ids) - 1)              # steps of the loop that produced a token (the first came from the prefill)
             del past, loop
             gc.collect()
 
     # -- several prompts at once ------------------------------------------------------------------
     MAX_BATCH = 16
 
+    def _no_batched_loop(self, greedy: bool, sampled: bool) -> Optional[str]:
+        """Why this model and engine cannot run a batched device loop for greedy and / or sampled sequences, or None."""
+        hf = getattr(self.lm, "hf_model", None)
+        if getattr(self.lm, "use_full_position_ids", False):
+            return "the model takes full position ids (per-key positions are re-based on the host every step)"
+        if not hasattr(hf, "slot_loop") or not hf.slot_loop_available():
+            return "the model has no batched decode loop (architecture, int8 weights or PC_DECODE_TAIL=1)"
+        if greedy and not self.device_greedy_loop:
+            return "PC_DEVICE_GREEDY=0"
+        if sampled and not self.device_sample_loop:
+            return "PC_DEVICE_SAMPLE=0"
+        return None
+
     def batch_plan(self, n_requests: int, params: GenerationParameters) -> Tuple[bool, str]:
         """``(batched, reason)``: whether ``generate_batch`` decodes ``n_requests`` sequences together in one device loop
         (``model/llama_hip.py`` SlotLoop) or runs them one after another through ``generate``, and why.  Host logic only."""
-        hf = getattr(self.lm, "hf_model", None)
-        plain_greedy = params.greedy and params.repetition_penalty <= 1.0
         if n_requests < 1:
             return False, "no requests"
         if n_requests > self.MAX_BATCH:
             return False, f"more than {self.MAX_BATCH} requests"
-        if getattr(self.lm, "use_full_position_ids", False):
-            return False, "the model takes full position ids (per-key positions are re-based on the host every step)"
-        if not hasattr(hf, "slot_loop") or not hf.slot_loop_available():
-            return False, "the model has no batched decode loop (architecture, int8 weights or PC_DECODE_TAIL=1)"
-        if plain_greedy and not self.device_greedy_loop:
-            return False, "PC_DEVICE_GREEDY=0"
-        if not plain_greedy and not self.device_sample_loop:
-            return False, "PC_DEVICE_SAMPLE=0"
+        why = self._no_batched_loop(params.plain_greedy, not params.plain_greedy)
+        if why is not None:
+            return False, why
         if len(params.stop_token_ids) > 8:
             return False, "more than 8 stop token ids"
         if params.max_new_tokens < 2:
@@ -348,112 +447,36 @@ class GenerationEngine:
                     yield k, out
             return
 
-        processors = params.get_logits_processor()
-        plain_greedy = params.greedy and params.repetition_penalty <= 1.0
+        plain_greedy = params.plain_greedy
         seed = 0 if plain_greedy else int(torch.randint(0, 2 ** 62, (1,)))
-        last_step = params.max_new_tokens - 1
-        n = len(requests)
-        output_ids = [list(t) for t, _, _ in requests]
-        new_ids: List[List[int]] = [[] for _ in range(n)]
-        total_ms, ttft_ms = [0.0] * n, [0.0] * n
-        done = [False] * n
-        pasts: list = [None] * n
-        first_free = [max(p) + 1 for _, p, _ in requests]
-        loop, members = None, []
-
-        def emit(k: int, step: int, token: int):
-            """generate's bookkeeping for one token of sequence k -> the Output to yield, if any."""
-            output_ids[k].append(token)
-            new_ids[k].append(token)
-            fin = token in params.stop_token_ids
-            out = None
-            if step % stream_interval == 0 or step == last_step or fin:
-                text, new_text, hit, partial = self._render(output_ids[k], new_ids[k], params.stop_str)
-                fin = fin or hit
-                if not partial:
-                    out = Output(text, new_text, total_ms[k], ttft_ms[k])
-            done[k] = fin or step == last_step
-            return out
-
+        seqs = [_Stream(self._render, params, stream_interval, t, max(p) + 1, index=k, seed=seed + k)
+                for k, (t, p, _) in enumerate(requests)]
+        loop, members, first = None, [], None
         try:
-            for k, (token_ids, position_ids, cache) in enumerate(requests):
-                logits, pasts[k], ms = self._forward(token_ids, position_ids, cache)
-                ttft_ms[k] = total_ms[k] = ms
-                if self.verbose:
-                    print(f"Prefill latency: {ms:.2f} ms")
-                if plain_greedy:
-                    token = self._pick(processors(None, logits[:, -1, :])[0], True)
-                else:
-                    token = hf.sample_token(logits[0, -1], params, seed + k, output_ids[k])
-                out = emit(k, 0, token)
+            for st, (token_ids, position_ids, cache) in zip(seqs, requests):
+                out = self._first_token(st, token_ids, position_ids, cache)
                 if out is not None:
-                    yield k, out
-            members = [k for k in range(n) if not done[k]]
-            if members and lookup > 0 and plain_greedy and hasattr(hf, "lookup_slot_loop"):
-                loop = hf.lookup_slot_loop([pasts[k] for k in members], [new_ids[k][-1] for k in members],
-                                           [first_free[k] + 1 for k in members], last_step, min(lookup, 15),
-                                           [self._lookup_corpus(requests[k][2], requests[k][0]) for k in members],
-                                           stop_ids=params.stop_token_ids, share_trunk=bool(share_trunk))
-            if loop is not None:
-                # a step yields 0..k+1 tokens per sequence: the host reads step after step, one replay ahead while the step in
-                # flight cannot exhaust every budget; tokens of a step behind a stop are dropped
-                lstep = 0
-                loop.enqueue()
-                while not all(done[k] for k in members):
-                    room = max(last_step - (len(new_ids[k]) - 1) for k in members if not done[k])
-                    if loop.n <= lstep or (loop.n == lstep + 1 and room > loop.k + 1):
-                        loop.enqueue()
-                    ms = loop.elapsed_ms(lstep)
-                    for j, k in enumerate(members):
-                        if done[k]:
-                            continue
-                        toks = loop.tokens(j, lstep)
-                        if not toks:                               # (the device switched the slot off: nothing more will come)
-                            done[k] = True
-                            continue
-                        total_ms[k] += ms
-                        for token in toks:
-                            out = emit(k, len(new_ids[k]), token)
-                            if out is not None:
-                                yield k, out
-                            if done[k]:
-                                if token not in params.stop_token_ids and len(new_ids[k]) - 1 != last_step:
-                                    loop.kill(j)                   # a stop string: the device cannot know
-                                break
-                    lstep += 1
-                return
+                    yield st.index, out
+            members = [st for st in seqs if not st.done]
             if members:
-                loop = hf.slot_loop([pasts[k] for k in members], [new_ids[k][-1] for k in members],
-                                    [first_free[k] + 1 for k in members], last_step, None if plain_greedy else params,
-                                    [seed + k for k in members], [output_ids[k] for k in members], params.stop_token_ids,
-                                    share_trunk=bool(share_trunk))
+                # the first decoded token sits at position first_free + 1, as in generate
+                first = ([st.past for st in members], [st.new_ids[-1] for st in members], [st.first_free + 1 for st in members],
+                         members[0].last_step)
+                if lookup > 0 and plain_greedy and hasattr(hf, "lookup_slot_loop"):
+                    loop = hf.lookup_slot_loop(*first, min(lookup, 15),
+                                               [self._lookup_corpus(requests[st.index][2], requests[st.index][0]) for st in members],
+                                               stop_ids=params.stop_token_ids, share_trunk=bool(share_trunk))
+                if loop is None:
+                    loop = hf.slot_loop(*first, None if plain_greedy else params, [st.seed for st in members],
+                                        [st.output_ids for st in members], params.stop_token_ids, share_trunk=bool(share_trunk))
                 if loop is None:
                     raise RuntimeError("generate_batch: the model refused a batched decode loop over these caches")
-                loop.enqueue()
-            for step in range(1, params.max_new_tokens):
-                if all(done):
-                    break
-                if loop.n <= step and loop.n < last_step:
-                    loop.enqueue()                                 # the replay AFTER the one whose tokens are read below
-                ms = loop.elapsed_ms(step - 1)
-                for j, k in enumerate(members):
-                    if done[k]:
-                        continue
-                    token = loop.token(j, step - 1)
-                    if token is None:                              # (the device switched the slot off: its arena is full)
-                        done[k] = True
-                        continue
-                    total_ms[k] += ms
-                    out = emit(k, step, token)
-                    if done[k] and token not in params.stop_token_ids and step != last_step:
-                        loop.kill(j)                               # a stop string: the device cannot know
-                    if out is not None:
-                        yield k, out
+                yield from self._pump_slots(loop, members)
         finally:
             # also when the consumer abandons the generator at a yield: every arena's length goes back to what was consumed
             if loop is not None:
-                loop.close([len(new_ids[k]) - 1 for k in members])
-            del pasts, loop
+                loop.close([len(st.new_ids) - 1 for st in members])
+            del seqs, members, first, st, loop
             gc.collect()
 
     # -- a stream of requests: continuous batching ------------------------------------------------
@@ -461,16 +484,8 @@ class GenerationEngine:
         """``(batched, reason)``: whether ``serve`` runs its requests through one device loop that admits new prompts as slots
         free up (``model/llama_hip.py`` SlotLoop, ``each=True``), or one after another through ``generate``, and why.  Host logic
         only.  Requests carry their own parameters, so both device loops must be on."""
-        hf = getattr(self.lm, "hf_model", None)
-        if getattr(self.lm, "use_full_position_ids", False):
-            return False, "the model takes full position ids (per-key positions are re-based on the host every step)"
-        if not hasattr(hf, "slot_loop") or not hf.slot_loop_available():
-            return False, "the model has no batched decode loop (architecture, int8 weights or PC_DECODE_TAIL=1)"
-        if not self.device_greedy_loop:
-            return False, "PC_DEVICE_GREEDY=0"
-        if not self.device_sample_loop:
-            return False, "PC_DEVICE_SAMPLE=0"
-        return True, "one device loop, new prompts admitted as slots free up"
+        why = self._no_batched_loop(True, True)
+        return (False, why) if why is not None else (True, "one device loop, new prompts admitted as slots free up")
 
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
@@ -513,125 +528,98 @@ class GenerationEngine:
         stats = self.last_serve_stats = dict(replays=0, rows=0, live_rows=0, requests=0)
         self.last_serve_trace = sched.trace
         tokens = self.last_serve_tokens = {}          # request index -> the tokens it decoded
-        seq = {}            # slot -> state of the running sequence
+        seq = {}            # slot -> stream of the running sequence
         loop, seed = None, None
         pending: list = []  # first fill: sequences waiting for the loop to be built
 
-        def first_token(index, slot, req):
-            """process + prefill + first token of a pulled request -> (state, Output | None)."""
-            nonlocal seed
-            prompt, p = unpack(req)
-            if p is None:
-                raise ValueError("serve: a bare prompt needs the default params")
-            ids, pos, _, cache = cache_engine.process(prompt, slot=slot)
-            plain = p.greedy and p.repetition_penalty <= 1.0
-            if not plain and seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)))
-            logits, past, ms = self._forward(list(ids), list(pos), cache)
-            if self.verbose:
-                print(f"Prefill latency: {ms:.2f} ms")
-            st = dict(index=index, slot=slot, p=p, plain=plain, output_ids=list(ids), new_ids=[], total_ms=ms, ttft_ms=ms,
-                      past=past, first_free=max(pos) + 1, last_step=p.max_new_tokens - 1, done=False, k=None,
-                      seed=0 if plain else seed + index)
-            tokens[index] = st["new_ids"]
-            if plain:
-                token = self._pick(p.get_logits_processor()(None, logits[:, -1, :])[0], True)
-            else:
-                token = hf.sample_token(logits[0, -1], p, st["seed"], st["output_ids"])
-            return st, emit(st, 0, token)
-
-        def emit(st, step, token):
-            p = st["p"]
-            st["output_ids"].append(token)
-            st["new_ids"].append(token)
-            fin = token in p.stop_token_ids
-            out = None
-            if step % stream_interval == 0 or step == st["last_step"] or fin:
-                text, new_text, hit, partial = self._render(st["output_ids"], st["new_ids"], p.stop_str)
-                fin = fin or hit
-                if not partial:
-                    out = Output(text, new_text, st["total_ms"], st["ttft_ms"])
-            st["done"] = fin or step >= st["last_step"]
-            return out
-
         def loop_args(st):
-            return (st["past"], st["new_ids"][-1], st["first_free"] + 1, st["last_step"], None if st["plain"] else st["p"], st["seed"],
-                    st["output_ids"], split_stop_ids(st["p"].stop_token_ids)[0])
+            return (st.past, st.new_ids[-1], st.first_free + 1, st.last_step, None if st.params.plain_greedy else st.params, st.seed,
+                    st.output_ids, st.device_stops)
 
         def admit_free_slots():
-            """Pull requests into free slots; sequences with more to decode enter the loop (or wait for it to be built)."""
+            """Pull requests into free slots: process, prefill and first token; sequences with more to decode enter the loop (or
+            wait for it to be built)."""
+            nonlocal seed
             while True:
                 nxt = sched.next_request()
                 if nxt is None:
                     return
                 index, slot, req = nxt
                 stats["requests"] += 1
-                st, out = first_token(index, slot, req)
+                prompt, p = unpack(req)
+                if p is None:
+                    raise ValueError("serve: a bare prompt needs the default params")
+                ids, pos, _, cache = cache_engine.process(prompt, slot=slot)
+                if not p.plain_greedy and seed is None:
+                    seed = int(torch.randint(0, 2 ** 62, (1,)))
+                st = _Stream(self._render, p, stream_interval, ids, max(pos) + 1, index=index, slot=slot,
+                             seed=0 if p.plain_greedy else seed + index, device_stops=split_stop_ids(p.stop_token_ids)[0])
+                tokens[index] = st.new_ids
+                out = self._first_token(st, list(ids), list(pos), cache)
                 if out is not None:
                     yield index, out
-                if st["done"]:
+                if st.done:
                     sched.dropped(slot, index, 0 if loop is None else loop.n)
                     continue
                 if loop is None:
                     pending.append(st)
                     sched.started(slot, index, 0)
                 else:
-                    trunk = sched.join(slot, st["past"].arena.layout) if share_trunk and loop.nsplit_trunk else None
-                    st["k"] = loop.admit(slot, *loop_args(st), trunk=trunk)
+                    trunk = sched.join(slot, st.past.arena.layout) if share_trunk and loop.nsplit_trunk else None
+                    st.k = loop.admit(slot, *loop_args(st), trunk=trunk)
                     sched.started(slot, index, loop.n)
                 seq[slot] = st
 
         try:
             yield from admit_free_slots()
             if pending:
-                args = [loop_args(st) for st in pending]
-                slots_ = [st["slot"] for st in pending]
-                trunks = sched.group_first_fill(slots_, [st["past"].arena.layout for st in pending]) if share_trunk else None
-                loop = hf.slot_loop([a[0] for a in args], [a[1] for a in args], [a[2] for a in args], [a[3] for a in args],
-                                    [a[4] for a in args], [a[5] for a in args], [a[6] for a in args], [a[7] for a in args],
-                                    slots=S, slot_index=slots_, each=True, max_keys=cache_engine.max_ctx_length, trunks=trunks)
+                slots_ = [st.slot for st in pending]
+                trunks = sched.group_first_fill(slots_, [st.past.arena.layout for st in pending]) if share_trunk else None
+                # (loop_args per sequence -> one list per argument)
+                loop = hf.slot_loop(*map(list, zip(*map(loop_args, pending))), slots=S, slot_index=slots_, each=True,
+                                    max_keys=cache_engine.max_ctx_length, trunks=trunks)
                 if loop is None:
                     raise RuntimeError("serve: the model refused a batched decode loop over these caches")
                 for k, st in enumerate(pending):
-                    st["k"] = k
+                    st.k = k
                 pending.clear()
             i = 0
             while seq:
+                # the look-ahead rule of _pump_slots over sequences that start at different replays (slot_scheduler.wants_look_ahead)
                 while loop.n <= i:
                     loop.enqueue()
                 if loop.n == i + 1 and wants_look_ahead(
-                        [(loop._start[st["k"]], st["last_step"] - max(0, i - loop._start[st["k"]])) for st in seq.values()], i):
+                        [(loop._start[st.k], st.last_step - max(0, i - loop._start[st.k])) for st in seq.values()], i):
                     loop.enqueue()                                 # the replay AFTER the one whose tokens are read below
                 ms = loop.elapsed_ms(i)
                 stats["rows"] += S
                 for slot in sorted(seq):
                     st = seq[slot]
-                    if loop._start[st["k"]] > i:
+                    if loop._start[st.k] > i:
                         continue
-                    token = loop.token(st["k"], i)
+                    token = loop.token(st.k, i)
                     out = None
                     if token is None:                              # (the device switched the slot off: its arena is full)
-                        st["done"] = True
+                        st.done = True
                     else:
                         stats["live_rows"] += 1
-                        st["total_ms"] += ms
-                        step = i - loop._start[st["k"]] + 1
-                        out = emit(st, step, token)
-                        if st["done"] and token not in split_stop_ids(st["p"].stop_token_ids)[0] and step != st["last_step"]:
-                            loop.kill(st["k"])                     # a stop string or a stop id past the first 8: the device cannot know
-                    if st["done"]:
-                        loop.retire(st["k"], len(st["new_ids"]) - 1)
+                        st.total_ms += ms
+                        out = st.emit(token)
+                        if st.ended_on_the_host(token):
+                            loop.kill(st.k)                        # a stop string or a stop id past the first 8
+                    if st.done:
+                        loop.retire(st.k, len(st.new_ids) - 1)
                         del seq[slot]
-                        st["past"] = None
+                        st.past = None
                         sched.finished(slot, i)
                     if out is not None:
-                        yield st["index"], out
+                        yield st.index, out
                 yield from admit_free_slots()
                 i += 1
         finally:
             # also when the consumer abandons the generator at a yield: every arena's length goes back to what was consumed
             if loop is not None:
                 stats["replays"] = loop.n
-                loop.close({st["k"]: len(st["new_ids"]) - 1 for st in seq.values() if st["k"] is not None})
+                loop.close({st.k: len(st.new_ids) - 1 for st in seq.values() if st.k is not None})
             del seq, loop, pending
             gc.collect()
