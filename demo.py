@@ -47,7 +47,8 @@ def main():
     ap.add_argument("--lookup", type=int, default=None,
                     help="prompt-lookup speculative decoding for the greedy single-prompt generation: draft up to K tokens (1..15; "
                          "try 7) from the context per step and verify them in one K+1-row forward (default: PC_LOOKUP, else off); "
-                         "with --batch also for the batched loop (generate_batch(lookup=K): N * (K + 1) <= 64 rows per step)")
+                         "with --batch also for the batched loop (generate_batch(lookup=K): N * (K + 1) <= 64 rows per step) and "
+                         "with --serve for the serving loop (serve(lookup=K): sampled requests draft and verify too)")
     ap.add_argument("--lookup-sampled", action="store_true", default=None,
                     help="with --lookup K: sampled generations (and greedy ones with a repetition penalty) draft and verify too, "
                          "the sampler drawing every row (SampleLookupLoop; default: PC_LOOKUP_SAMPLE=1, else off)")
@@ -119,12 +120,12 @@ def main():
             for r in range(a.serve):
                 pr = Prompt(prompt_text[:cut] + f"<user>{synth.words(4 + r % 5, 5000 + r)}</user>" + prompt_text[cut:], preproc)
                 yield pr, dataclasses.replace(params, max_new_tokens=budgets[r % len(budgets)])
-        batched, why = gen_engine.serve_plan()
+        batched, why = gen_engine.serve_plan(a.lookup or 0, cache_engine.slots)
         for _pass in ("warm", "timed"):
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk):
+            for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk, lookup=a.lookup):
                 lasts[r] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -133,7 +134,7 @@ def main():
             st = gen_engine.last_serve_stats
             print(f"served {a.serve} prompts through {cache_engine.slots} slots: {n_tok} tokens in {dt * 1e3:8.2f} ms, prefills included: "
                   f"{n_tok / dt:8.1f} tokens/s aggregate, {st['replays']} replays, "
-                  f"{1.0 - st['live_rows'] / max(1, st['replays'] * cache_engine.slots):.2f} of the rows idle")
+                  f"{1.0 - st['live_rows'] / max(1, st['replays'] * cache_engine.slots):.2f} of the rows idle ({why})")
         else:
             print(f"served {a.serve} prompts one after another ({why}) in {dt * 1e3:8.2f} ms")
         print("Assistant[0]:", lasts[0].new_text[:120] + " ...")

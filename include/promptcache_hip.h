@@ -826,6 +826,65 @@ typedef struct pc_slot_state {   /* the S-slot device arrays of the captured ste
 
 int pc_slot_arm(const pc_slot_arm_block* host_block, int32_t nbytes, const pc_slot_state* state, int32_t S, void* stream);
 
+/* ---- prompt-lookup drafts under continuous batching (csrc/pc_sample.hip, csrc/pc_lookup.hip) --------------------------------------
+ * pc_lookup_verify_slots_each -- pc_lookup_verify_slots with the sampling state PER SLOT: pc_lookup_verify_sample's rule on the
+ * slot words of the section above, so that greedy and sampled sequences share one S * (k + 1)-row step and a sequence admitted
+ * into a running loop keeps the random stream it would have had alone.  Per slot b: params_dev[b] (pc_sample_params[S]; a block
+ * in greedy mode takes the argmax of its processed row), seeds[b], draws[b] (int32[S], the Philox step of the slot's stream),
+ * history_bits[b] (uint32 [S][ceil(vocab / 32)], the penalty history) and stop_ids[b][0..8).  For every RUNNING slot b and row
+ * i <= ndraft[b], t[b][i] = pc_sample_advance's draw on logits row b * (k + 1) + i with the random stream (seeds[b], step
+ * draws[b] + i) under the history history_bits[b] + {ids[b][1], ..., ids[b][i]}; pad rows (i > ndraft[b]) and rows of slots that
+ * do not run are not drawn.  Then pc_lookup_verify_slots' rule per slot with t in the place of the argmax -- the EMPTY record
+ * and ctr[b] += 1 for a slot that does not run, the cut behind the first emitted stop id (that token is emitted), live[b] = 0 on a
+ * stop id, on budget[b] reaching 0 or when the new len[b] + k + 1 > cap[b] -- and two additions: the bits of the emitted tokens
+ * are set in history_bits[b], and draws[b] += emit, counted behind the stop cut (the draws of rejected rows are not consumed:
+ * token number n of a sequence is always drawn at step n).  row_bits uint32 [S * (k + 1)][ceil(vocab / 32)] and row_token int32
+ * [S * (k + 1)] are scratch (row_bits must not alias history_bits).  1 <= S <= 16, 1 <= k <= 15, S * (k + 1) <= 64, vocab < 2^24,
+ * ldl >= vocab; logits 4-byte, params and seeds 8-byte aligned.  Two launches: S * (k + 1) workgroups, then one wave per slot.
+ * With every block plain greedy the words equal pc_lookup_verify_slots'; with S = 1 and no stop ids pc_lookup_verify_sample's; with
+ * ndraft = 0 everywhere the token, ids[b][0], pos, len, budget, draws and bitmap equal pc_sample_advance_slots_each's.  Ordinary
+ * vector stores only. */
+int pc_lookup_verify_slots_each(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k, const pc_sample_params* params_dev,
+                                const uint64_t* seeds, uint32_t* history_bits, uint32_t* row_bits, int32_t* draws, int32_t* row_token,
+                                int32_t* hist, int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* len,
+                                const int32_t* cap, int32_t* live, const int32_t* ndraft, int32_t* budget, const int32_t* stop_ids,
+                                int32_t* ring, int32_t* counters, int32_t ring_cap, void* stream);
+
+/* pc_lookup_slot_arm -- pc_slot_arm for the words of the lookup step: ONE launch between two replays writes every word of slot
+ * `slot` from a pinned host block, read with system-scope loads; live[slot] = 1 is the last store.  Written: kv_base, cap, len,
+ * leader, trunk, budget, counters (the replays enqueued so far: record c of every slot then still belongs to replay c), draws = 1,
+ * seed, parameter block, stop row, bitmap row (hist_words words), ids[slot][0], pos[slot][0], ndraft = 0, hist_len and the first
+ * hist_len ids of hist[slot] (row stride hist_cap).  No word of another slot is touched.  The block is pc_lookup_slot_arm_block,
+ * then hist_words uint32 of bitmap, then hist_len int32 of history ids; nbytes = sizeof(pc_lookup_slot_arm_block) + 4 * hist_words
+ * + 4 * hist_len, the last two each rounded up to a multiple of 8.  1 <= hist_len <= hist_cap < 2^24; S and k as in
+ * pc_lookup_verify_slots_each.  The host must not rewrite a block before its launch has finished. */
+typedef struct pc_lookup_slot_arm_block {
+    int32_t slot;                /* which of the S slots */
+    int32_t cap;                 /* rows per plane of the arena */
+    uint64_t kv_base;            /* address of the arena */
+    int32_t len;                 /* rows the arena holds */
+    int32_t pos;                 /* position id of the token fed next */
+    int64_t id;                  /* that token */
+    int32_t leader;              /* shared trunk: leading slot, -1: on its own */
+    int32_t trunk;               /* shared rows */
+    int32_t budget;              /* tokens left */
+    int32_t counter;             /* ring counter (the loop's, so that ring records line up across slots) */
+    int32_t hist_words;          /* uint32 words of history bitmap behind the struct */
+    int32_t hist_len;            /* int32 history ids behind the bitmap (the last one is `id`) */
+    uint64_t seed;
+    pc_sample_params params;
+    int32_t stop_ids[8];         /* unused entries: -1 */
+} pc_lookup_slot_arm_block;
+
+typedef struct pc_lookup_slot_state {   /* the S-slot device arrays of the captured lookup step */
+    uint64_t* kv_base; int32_t* cap; int32_t* len; int32_t* live; int32_t* leader; int32_t* trunk; int64_t* ids; int32_t* pos;
+    int32_t* ndraft; int32_t* budget; int32_t* hist_len; int32_t* counters; int32_t* draws; uint64_t* seeds; pc_sample_params* params;
+    int32_t* stop_ids; uint32_t* history_bits; int32_t* hist;
+} pc_lookup_slot_state;
+
+int pc_lookup_slot_arm(const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state, int32_t S, int32_t k,
+                       int32_t hist_cap, void* stream);
+
 /* Diagnostics used by the GPU test-suite: dumps the MFMA C/D lane map and the LDS transpose-read
  * map the attention kernel relies on (probe_kernel in csrc/pc_misc.hip). */
 /* dev hook (tools/gemm_trace.py): weight-streaming launches issued by this thread stamp per-wave wall-clock times

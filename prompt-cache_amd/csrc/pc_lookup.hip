@@ -1,6 +1,7 @@
 // Prompt-lookup speculative decoding, the two ends of a device-side step (model/llama_hip.py LookupLoop):
 //   pc_lookup_draft   first node: copy the tokens that followed the most recent earlier occurrence of the history's suffix
 //   pc_lookup_verify  last node:  per-row argmax of the k+1-row forward, longest agreeing prefix + one bonus token, state advance
+// (and, between two replays of the step over slots, pc_lookup_slot_arm: admission of one sequence into a running loop)
 // Between them runs the ordinary <= 16-row forward over the ids / positions / past length these kernels keep in device words,
 // so a replay of the captured step needs nothing from the host.  The result is greedy decoding (the accepted tokens ARE the
 // model's argmax at their positions); only the number of tokens per weight stream varies.
@@ -138,66 +139,68 @@ __global__ __launch_bounds__(64) void lookup_accept_kernel(const int32_t* __rest
     lookup_accept_rule(a, rows, hist, hist_len, hist_cap, ids, pos, past, ndraft, budget, ring, ctr, ring_cap);
 }
 
-// One wave per slot: lookup_accept_kernel's rule on the slot's words, cut behind the first emitted stop id, with the slot's
-// length where the B = 1 form has `past`.  A slot that did not run (idle, or no room for a step's rows) leaves an EMPTY record
-// and nothing else -- its counter keeps pace with the replays, so that record c of every slot belongs to replay c -- and a
-// live slot without room is switched off.
+// One wave per slot: lookup_accept_slots_rule (pc_lookup_common.h) on the per-row argmax.
 __global__ __launch_bounds__(64) void lookup_accept_slots_kernel(const int32_t* __restrict__ amax, int rows, int32_t* hist, int32_t* hist_len,
                                                                  int hist_cap, int64_t* ids, int32_t* pos, int32_t* len,
                                                                  const int32_t* __restrict__ cap, int32_t* live, const int32_t* ndraft,
                                                                  int32_t* budget, const int32_t* __restrict__ stop_ids, int32_t* ring,
                                                                  int32_t* ctr, int ring_cap) {
-    const int lane = threadIdx.x, b = blockIdx.x;
-    const int k = rows - 1;
-    const int c = ctr[b];
-    int32_t* rec = ring + ((int64_t)b * ring_cap + (int64_t)(((unsigned)c) % (unsigned)ring_cap)) * (rows + 1);
-    if (!lookup_slot_runs(cap, len, live, b, k)) {
-        if (lane == 0) {
-            rec[0] = 0;
-            ctr[b] = c + 1;
-            if (live[b] != 0) live[b] = 0;
-        }
-        return;
+    int a;
+    lookup_accept_slots_rule(amax + blockIdx.x * rows, rows, blockIdx.x, hist, hist_len, hist_cap, ids, pos, len, cap, live, ndraft, budget,
+                             stop_ids, ring, ctr, ring_cap, a);
+}
+
+// ---- pc_lookup_slot_arm: every word of ONE slot of the lookup step from a pinned host block, one launch -----------------------
+// pc_slot_arm (pc_slots.hip) for the words of pc_lookup_verify_slots_each's step: the launch sits on the stream between two
+// replays, the block is host memory read with system-scope loads, live[slot] = 1 is the last store.  One workgroup: the header
+// goes through LDS, the bitmap row and the history ids are copied by all threads, two 32-bit words per load.
+constexpr int kLookupArmWords = (int)(sizeof(pc_lookup_slot_arm_block) / 8);
+
+__global__ __launch_bounds__(kDraftThreads) void lookup_slot_arm_kernel(const unsigned long long* __restrict__ src, pc_lookup_slot_state st,
+                                                                        int S, int k, int hw, int hist_cap) {
+    typedef __attribute__((address_space(1))) unsigned long long g64;
+    __shared__ __attribute__((aligned(8))) unsigned long long h[kLookupArmWords];
+    const int tid = threadIdx.x;
+    if (tid < kLookupArmWords) h[tid] = __hip_atomic_load((g64*)(src + tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __syncthreads();
+    const pc_lookup_slot_arm_block& b = *(const pc_lookup_slot_arm_block*)h;
+    const int s = b.slot, hl = b.hist_len;
+    if (s < 0 || s >= S || b.hist_words != hw || hl < 1 || hl > hist_cap) return;      // (the block changed under the launch: touch nothing)
+    const unsigned long long* bits = src + kLookupArmWords;
+    const unsigned long long* hids = bits + (hw + 1) / 2;
+    uint32_t* row = st.history_bits + (int64_t)s * hw;
+    for (int i = tid; 2 * i < hw; i += kDraftThreads) {
+        const unsigned long long w = __hip_atomic_load((g64*)(bits + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        row[2 * i] = (uint32_t)w;
+        if (2 * i + 1 < hw) row[2 * i + 1] = (uint32_t)(w >> 32);
     }
-    hist += (int64_t)b * hist_cap;
-    ids += (int64_t)b * rows;
-    pos += (int64_t)b * rows;
-    int nd = ndraft[b];
-    nd = nd < 0 ? 0 : (nd > k ? k : nd);
-    const int a = lane < rows ? amax[b * rows + lane] : 0;
-    const bool miss = lane < nd && (int64_t)a != ids[1 + lane];
-    const unsigned long long mm = __ballot(miss);
-    const int acc = mm ? (int)__builtin_ctzll(mm) : nd;
-    const int bud = budget[b];
-    const int L = hist_len[b];
-    const int p0 = pos[0], pl = len[b], cp = cap[b];
-    int emit = acc + 1 < bud ? acc + 1 : bud;
-    int room = L < 0 ? 0 : hist_cap - L;
-    room = room < 0 ? 0 : room;
-    emit = emit < room ? emit : room;
-    emit = emit < 0 ? 0 : emit;
-    bool stop = false;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) stop = stop || a == stop_ids[b * 8 + j];
-    const unsigned long long sm = __ballot(stop && lane < emit);
-    if (sm) emit = (int)__builtin_ctzll(sm) + 1;              // the stop id itself is emitted
-    const int last = __shfl(a, emit > 0 ? emit - 1 : 0);
-    if (lane == 0) rec[0] = emit;
-    if (lane < emit) {
-        rec[1 + lane] = a;
-        hist[L + lane] = a;
+    int32_t* hrow = st.hist + (int64_t)s * hist_cap;
+    for (int i = tid; 2 * i < hl; i += kDraftThreads) {
+        const unsigned long long w = __hip_atomic_load((g64*)(hids + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        hrow[2 * i] = (int32_t)(uint32_t)w;
+        if (2 * i + 1 < hl) hrow[2 * i + 1] = (int32_t)(uint32_t)(w >> 32);
     }
-    if (lane == 0) {
-        ctr[b] = c + 1;
-        if (emit > 0) {
-            hist_len[b] = L + emit;
-            ids[0] = last;
-            pos[0] = p0 + emit;
-            len[b] = pl + emit;
-            budget[b] = bud - emit;
-        }
-        if (sm != 0 || bud - emit <= 0 || pl + emit + k + 1 > cp) live[b] = 0;
+    if (tid == 0) {
+        st.kv_base[s] = b.kv_base;
+        st.cap[s] = b.cap;
+        st.len[s] = b.len;
+        st.leader[s] = b.leader;
+        st.trunk[s] = b.trunk;
+        st.budget[s] = b.budget;
+        st.counters[s] = b.counter;
+        st.draws[s] = 1;
+        st.seeds[s] = b.seed;
+        st.params[s] = b.params;
+        st.ids[(int64_t)s * (k + 1)] = b.id;
+        st.pos[(int64_t)s * (k + 1)] = b.pos;
+        st.ndraft[s] = 0;
+        st.hist_len[s] = hl;
+    } else if (tid >= 64 && tid < 72) {
+        st.stop_ids[s * 8 + tid - 64] = b.stop_ids[tid - 64];
     }
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) st.live[s] = 1;
 }
 
 }  // namespace
@@ -259,4 +262,27 @@ PC_EXPORT int pc_lookup_verify_slots(const float* logits, int64_t ldl, int32_t v
     hipLaunchKernelGGL(lookup_accept_slots_kernel, dim3(S), dim3(64), 0, (hipStream_t)stream, row_argmax, k + 1, hist, hist_len, hist_cap,
                        ids, pos, len, cap, live, ndraft, budget, stop_ids, ring, counters, ring_cap);
     return pc_check_launch("lookup_accept_slots_kernel");
+}
+
+PC_EXPORT int pc_lookup_slot_arm(const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state, int32_t S,
+                                 int32_t k, int32_t hist_cap, void* stream) {
+    PC_REQUIRE(host_block && state, PC_ERR_ARG, "pc_lookup_slot_arm: null pointer");
+    PC_REQUIRE(state->kv_base && state->cap && state->len && state->live && state->leader && state->trunk && state->ids && state->pos &&
+                   state->ndraft && state->budget && state->hist_len && state->counters && state->draws && state->seeds && state->params &&
+                   state->stop_ids && state->history_bits && state->hist, PC_ERR_ARG, "pc_lookup_slot_arm: null pointer in the slot state");
+    PC_REQUIRE(S >= 1 && S <= 16 && k >= 1 && k < kMaxRows && S * (k + 1) <= kMaxSlotRows && hist_cap >= 1 && hist_cap < (1 << 24), PC_ERR_ARG,
+               "pc_lookup_slot_arm: need 1 <= S <= 16, 1 <= k <= %d, S * (k + 1) <= %d, 1 <= hist_cap < 2^24", kMaxRows - 1, kMaxSlotRows);
+    PC_REQUIRE(((uintptr_t)host_block & 7) == 0 && ((uintptr_t)state->params & 7) == 0 && ((uintptr_t)state->seeds & 7) == 0 &&
+                   ((uintptr_t)state->kv_base & 7) == 0 && ((uintptr_t)state->ids & 7) == 0, PC_ERR_ARG,
+               "pc_lookup_slot_arm: the block and the 64-bit state arrays must be 8-byte aligned");
+    const int32_t slot = host_block->slot, hw = host_block->hist_words, hl = host_block->hist_len;   // (pinned HOST memory: readable here)
+    PC_REQUIRE(slot >= 0 && slot < S, PC_ERR_ARG, "pc_lookup_slot_arm: slot outside [0, S)");
+    PC_REQUIRE(hw >= 1 && hw <= (1 << 19) && hl >= 1 && hl <= hist_cap, PC_ERR_ARG,
+               "pc_lookup_slot_arm: need 1 <= hist_words <= 2^19 and 1 <= hist_len <= hist_cap");
+    PC_REQUIRE((int64_t)nbytes == (int64_t)sizeof(pc_lookup_slot_arm_block) + (((int64_t)hw * 4 + 7) & ~(int64_t)7) +
+                                      (((int64_t)hl * 4 + 7) & ~(int64_t)7), PC_ERR_ARG,
+               "pc_lookup_slot_arm: nbytes must be sizeof(pc_lookup_slot_arm_block) + 4 * hist_words + 4 * hist_len, each rounded up to 8");
+    hipLaunchKernelGGL(lookup_slot_arm_kernel, dim3(1), dim3(kDraftThreads), 0, (hipStream_t)stream, (const unsigned long long*)host_block,
+                       *state, S, k, hw, hist_cap);
+    return pc_check_launch("lookup_slot_arm_kernel");
 }

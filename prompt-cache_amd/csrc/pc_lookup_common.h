@@ -69,3 +69,69 @@ __device__ __forceinline__ int lookup_accept_rule(int a, int rows, int32_t* hist
     }
     return emit;
 }
+
+// The accept rule of a prompt-lookup step over SLOTS (pc_lookup_verify_slots, pc_lookup_verify_slots_each), by one wave for
+// slot b: lookup_accept_rule on the slot's words, cut behind the first emitted stop id, with the slot's length where the B = 1
+// form has `past`.  tok[i] = the model's token for draft row i of the slot (rows behind ndraft are pads: not read).  A slot that
+// did not run (idle, or no room for a step's rows) leaves an EMPTY record and nothing else -- its counter keeps pace with the
+// replays, so that record c of every slot belongs to replay c -- and a live slot without room is switched off.
+// -> emit, the number of tokens the step yields (the same in every lane; -1: the slot did not run); a = this lane's token.
+__device__ __forceinline__ int lookup_accept_slots_rule(const int32_t* __restrict__ tok, int rows, int b, int32_t* hist, int32_t* hist_len,
+                                                        int hist_cap, int64_t* ids, int32_t* pos, int32_t* len,
+                                                        const int32_t* __restrict__ cap, int32_t* live, const int32_t* ndraft,
+                                                        int32_t* budget, const int32_t* __restrict__ stop_ids, int32_t* ring,
+                                                        int32_t* ctr, int ring_cap, int& a) {
+    const int lane = threadIdx.x;
+    const int k = rows - 1;
+    const int c = ctr[b];
+    int32_t* rec = ring + ((int64_t)b * ring_cap + (int64_t)(((unsigned)c) % (unsigned)ring_cap)) * (rows + 1);
+    a = 0;
+    if (!lookup_slot_runs(cap, len, live, b, k)) {
+        if (lane == 0) {
+            rec[0] = 0;
+            ctr[b] = c + 1;
+            if (live[b] != 0) live[b] = 0;
+        }
+        return -1;
+    }
+    hist += (int64_t)b * hist_cap;
+    ids += (int64_t)b * rows;
+    pos += (int64_t)b * rows;
+    int nd = ndraft[b];
+    nd = nd < 0 ? 0 : (nd > k ? k : nd);
+    a = lane <= nd ? tok[lane] : 0;
+    const bool miss = lane < nd && (int64_t)a != ids[1 + lane];
+    const unsigned long long mm = __ballot(miss);
+    const int acc = mm ? (int)__builtin_ctzll(mm) : nd;
+    const int bud = budget[b];
+    const int L = hist_len[b];
+    const int p0 = pos[0], pl = len[b], cp = cap[b];
+    int emit = acc + 1 < bud ? acc + 1 : bud;
+    int room = L < 0 ? 0 : hist_cap - L;
+    room = room < 0 ? 0 : room;
+    emit = emit < room ? emit : room;
+    emit = emit < 0 ? 0 : emit;
+    bool stop = false;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) stop = stop || a == stop_ids[b * 8 + j];
+    const unsigned long long sm = __ballot(stop && lane < emit);
+    if (sm) emit = (int)__builtin_ctzll(sm) + 1;              // the stop id itself is emitted
+    const int last = __shfl(a, emit > 0 ? emit - 1 : 0);
+    if (lane == 0) rec[0] = emit;
+    if (lane < emit) {
+        rec[1 + lane] = a;
+        hist[L + lane] = a;
+    }
+    if (lane == 0) {
+        ctr[b] = c + 1;
+        if (emit > 0) {
+            hist_len[b] = L + emit;
+            ids[0] = last;
+            pos[0] = p0 + emit;
+            len[b] = pl + emit;
+            budget[b] = bud - emit;
+        }
+        if (sm != 0 || bud - emit <= 0 || pl + emit + k + 1 > cp) live[b] = 0;
+    }
+    return emit;
+}

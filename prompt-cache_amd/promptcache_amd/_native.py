@@ -64,6 +64,20 @@ class SlotState(C.Structure):
                                    "seeds", "params", "stop_ids", "history_bits")]
 
 
+class LookupSlotArmBlock(C.Structure):
+    """``pc_lookup_slot_arm_block``: the header of the pinned host block of pc_lookup_slot_arm (``hist_words`` uint32 of bitmap,
+    then ``hist_len`` int32 of history ids follow)."""
+    _fields_ = [("slot", _i32), ("cap", _i32), ("kv_base", C.c_uint64), ("len", _i32), ("pos", _i32), ("id", _i64),
+                ("leader", _i32), ("trunk", _i32), ("budget", _i32), ("counter", _i32), ("hist_words", _i32), ("hist_len", _i32),
+                ("seed", C.c_uint64), ("params", SampleParams), ("stop_ids", _i32 * 8)]
+
+
+class LookupSlotState(C.Structure):
+    """``pc_lookup_slot_state``: the S-slot device arrays pc_lookup_slot_arm writes into."""
+    _fields_ = [(f, _vp) for f in ("kv_base", "cap", "len", "live", "leader", "trunk", "ids", "pos", "ndraft", "budget", "hist_len",
+                                   "counters", "draws", "seeds", "params", "stop_ids", "history_bits", "hist")]
+
+
 KV_ROW_STAGED = 1
 KV_ROW_TABLE_MAX_SEG = 1024
 
@@ -192,6 +206,9 @@ SIGNATURES = {
     "pc_sample_advance_slots_each": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                                _i32, _vp, _vp]),
     "pc_slot_arm": (C.c_int, [_vp, _i32, C.POINTER(SlotState), _i32, _vp]),
+    "pc_lookup_verify_slots_each": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "pc_lookup_slot_arm": (C.c_int, [_vp, _i32, C.POINTER(LookupSlotState), _i32, _i32, _i32, _vp]),
     "pc_quant_act_i8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_rmsnorm_quant_i8": (C.c_int, [_vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_outlier_corr": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -941,6 +958,44 @@ def slot_arm(host_pinned, nbytes: int, state: SlotState, S: int, stream: Optiona
     """Write every state word of one slot from the pinned host block ``host_pinned`` (pc_slot_arm), ordered on the stream."""
     rc = load().pc_slot_arm(host_pinned.data_ptr(), nbytes, C.byref(state), S, current_stream() if stream is None else stream)
     check(rc, "pc_slot_arm")
+
+
+def lookup_verify_slots_each(logits, ldl: int, vocab: int, S: int, k: int, params, seeds, history_bits, row_bits, draws, row_token,
+                             hist, hist_len, ids, pos, length, cap, live, ndraft, budget, stop_ids, ring, counters, ring_cap: int,
+                             stream: Optional[int] = None) -> None:
+    """``lookup_verify_slots`` with per-slot sampling state (pc_lookup_verify_slots_each): pc_sample_advance's draw on every real row
+    of every running slot -- ``params`` holds S ``SampleParams``, ``history_bits`` uint32 [S][ceil(vocab / 32)], ``draws`` int32 [S]
+    -- then the accept rule per slot, the emitted tokens' bits and ``draws[b] += emit``.  ``row_bits`` / ``row_token``: scratch."""
+    R, hw = S * (k + 1), (vocab + 31) // 32
+    assert ring.numel() >= S * ring_cap * (k + 2) and row_token.numel() >= R and ids.numel() >= R and stop_ids.numel() >= 8 * S
+    assert row_bits.numel() >= R * hw and history_bits.numel() >= S * hw and params.numel() >= S * C.sizeof(SampleParams)
+    assert hist.dim() == 2 and hist.shape[0] == S and hist.is_contiguous()
+    rc = load().pc_lookup_verify_slots_each(logits.data_ptr(), ldl, vocab, S, k, params.data_ptr(), seeds.data_ptr(),
+                                            history_bits.data_ptr(), row_bits.data_ptr(), draws.data_ptr(), row_token.data_ptr(),
+                                            hist.data_ptr(), hist_len.data_ptr(), hist.shape[1], ids.data_ptr(), pos.data_ptr(),
+                                            length.data_ptr(), cap.data_ptr(), live.data_ptr(), ndraft.data_ptr(), budget.data_ptr(),
+                                            stop_ids.data_ptr(), ring.data_ptr(), counters.data_ptr(), ring_cap,
+                                            current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_verify_slots_each")
+
+
+def lookup_slot_arm_bytes(hist_words: int, hist_len: int) -> int:
+    """Bytes of a pc_lookup_slot_arm block with ``hist_words`` words of history bitmap and ``hist_len`` history ids."""
+    return C.sizeof(LookupSlotArmBlock) + ((4 * hist_words + 7) & ~7) + ((4 * hist_len + 7) & ~7)
+
+
+def lookup_slot_state(kv_base, cap, length, live, leader, trunk, ids, pos, ndraft, budget, hist_len, counters, draws, seeds, params,
+                      stop_ids, history_bits, hist) -> LookupSlotState:
+    return LookupSlotState(*[t.data_ptr() for t in (kv_base, cap, length, live, leader, trunk, ids, pos, ndraft, budget, hist_len,
+                                                     counters, draws, seeds, params, stop_ids, history_bits, hist)])
+
+
+def lookup_slot_arm(host_pinned, nbytes: int, state: LookupSlotState, S: int, k: int, hist_cap: int, stream: Optional[int] = None) -> None:
+    """Write every word of one slot of the lookup step from the pinned host block ``host_pinned`` (pc_lookup_slot_arm), ordered on
+    the stream."""
+    rc = load().pc_lookup_slot_arm(host_pinned.data_ptr(), nbytes, C.byref(state), S, k, hist_cap,
+                                   current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_slot_arm")
 
 
 def sample_params_bytes(temperature: float, repetition_penalty: float, top_p: float, top_k: int, seed: int) -> bytes:

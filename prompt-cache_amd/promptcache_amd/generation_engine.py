@@ -480,16 +480,40 @@ class GenerationEngine:
             gc.collect()
 
     # -- a stream of requests: continuous batching ------------------------------------------------
-    def serve_plan(self) -> Tuple[bool, str]:
-        """``(batched, reason)``: whether ``serve`` runs its requests through one device loop that admits new prompts as slots
-        free up (``model/llama_hip.py`` SlotLoop, ``each=True``), or one after another through ``generate``, and why.  Host logic
-        only.  Requests carry their own parameters, so both device loops must be on."""
+    def serve_plan(self, lookup: int = 0, slots: Optional[int] = None) -> Tuple[bool, str]:
+        """``(batched, reason)``: whether ``serve`` runs its requests through one device loop that admits new prompts as slots free
+        up (``model/llama_hip.py`` SlotLoop, ``each=True``), or one after another through ``generate``, and why.  Host logic only.
+        Requests carry their own parameters, so both device loops must be on.  ``lookup`` = k > 0 (``serve(lookup=k)`` over
+        ``slots`` slots): the reason also says which form of the loop runs -- the one with prompt-lookup drafts
+        (LookupSlotLoop, ``each=True``) or today's one-token loop, and why."""
         why = self._no_batched_loop(True, True)
-        return (False, why) if why is not None else (True, "one device loop, new prompts admitted as slots free up")
+        if why is not None:
+            return False, why
+        k, why = self._serve_drafts(lookup, slots)
+        if k:
+            return True, (f"one device loop with prompt-lookup drafts (lookup, k = {k}): up to k + 1 tokens per sequence and replay, "
+                          "new prompts admitted as slots free up")
+        if why is not None:
+            return True, "one device loop, one token per replay: " + why
+        return True, "one device loop, new prompts admitted as slots free up"
+
+    def _serve_drafts(self, lookup: int, slots: Optional[int]) -> Tuple[int, Optional[str]]:
+        """``(k, None)``: ``serve(lookup=...)`` over ``slots`` slots runs the lookup form with k drafts per sequence and replay (k
+        above 15 is taken as 15); ``(0, why)``: it runs the one-token loop (``why`` None: ``lookup`` is off)."""
+        k = min(int(lookup), 15)
+        if k <= 0:
+            return 0, None
+        hf = getattr(self.lm, "hf_model", None)
+        offered = getattr(hf, "lookup_available", None)
+        if not hasattr(hf, "lookup_slot_loop") or offered is None or not offered():
+            return 0, "the model has no lookup step"
+        if slots is not None and int(slots) * (k + 1) > 64:
+            return 0, f"{int(slots)} slots x (k + 1 = {k + 1}) rows exceed the 64 rows of the weight-streaming projections"
+        return k, None
 
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
-              share_trunk: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
+              share_trunk: Optional[bool] = None, lookup: Optional[int] = None) -> Generator[Tuple[int, Output], None, None]:
         """Continuous batching over ``cache_engine.slots`` slots.  ``requests``: any iterable -- it may be lazy -- of ``Prompt`` or
         ``(Prompt, GenerationParameters)``; ``params`` is the default for bare prompts.  Requests are numbered in the order they
         are pulled; yields ``(index, Output)``.  A request is pulled when a slot is free: ``cache_engine.process(prompt, slot=k)``,
@@ -503,9 +527,17 @@ class GenerationEngine:
         not refilled while members live.  The split counts of the attention are fixed from the slot buffers' capacity, so a
         sequence's tokens do not depend on who joins later.  Where ``serve_plan`` says no, the requests run one after another
         through ``generate``.  Abandoning the generator rewinds every arena.  ``last_serve_stats`` / ``last_serve_trace`` /
-        ``last_serve_tokens``: replays and live rows, the scheduler's trace and the decoded tokens per request of the newest run."""
+        ``last_serve_tokens``: replays and live rows, the scheduler's trace and the decoded tokens per request of the newest run.
+        ``lookup`` = k > 0 (None: ``PC_SERVE_LOOKUP``, default 0 = off; the engine's own ``lookup`` is NOT consulted; k above 15
+        is taken as 15): every sequence drafts up to k tokens per replay by prompt lookup in ``_lookup_corpus`` and its own
+        output, and one ``slots * (k + 1)``-row step verifies them with the request's own sampler on every row
+        (``LlamaHIP.lookup_slot_loop(each=True)``): on identical logits the tokens are the one-token loop's, sampled
+        ones included.  Where the model has no lookup step or ``slots * (k + 1) > 64`` (``serve_plan(lookup, slots)``) today's
+        loop runs.  With ``share_trunk`` the step reads a group's shared rows once for all draft rows of the group.  In the
+        lookup form ``last_serve_stats`` gains ``tokens`` (decoded in the loop) and ``steps`` (replays)."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
+        lookup = min(int(os.environ.get("PC_SERVE_LOOKUP", "0")) if lookup is None else int(lookup), 15)
 
         def unpack(req):
             if isinstance(req, (tuple, list)):
@@ -524,12 +556,15 @@ class GenerationEngine:
 
         hf = self.lm.hf_model
         S = cache_engine.slots
+        drafts = self._serve_drafts(lookup, S)[0]     # k > 0: the lookup form (serve_plan(lookup, S) names the form and why)
         sched = SlotScheduler(S, requests, share_trunk=bool(share_trunk))
         stats = self.last_serve_stats = dict(replays=0, rows=0, live_rows=0, requests=0)
+        if drafts:
+            stats.update(tokens=0, steps=0)
         self.last_serve_trace = sched.trace
         tokens = self.last_serve_tokens = {}          # request index -> the tokens it decoded
         seq = {}            # slot -> stream of the running sequence
-        loop, seed = None, None
+        loop, seed, read_k = None, None, 0
         pending: list = []  # first fill: sequences waiting for the loop to be built
 
         def loop_args(st):
@@ -556,6 +591,8 @@ class GenerationEngine:
                              seed=0 if p.plain_greedy else seed + index, device_stops=split_stop_ids(p.stop_token_ids)[0])
                 tokens[index] = st.new_ids
                 out = self._first_token(st, list(ids), list(pos), cache)
+                if drafts:
+                    st.corpus = self._lookup_corpus(cache, ids)        # (behind the prefill: the staged layout is carried out)
                 if out is not None:
                     yield index, out
                 if st.done:
@@ -566,7 +603,7 @@ class GenerationEngine:
                     sched.started(slot, index, 0)
                 else:
                     trunk = sched.join(slot, st.past.arena.layout) if share_trunk and loop.nsplit_trunk else None
-                    st.k = loop.admit(slot, *loop_args(st), trunk=trunk)
+                    st.k = loop.admit(slot, *loop_args(st), *((st.corpus,) if read_k else ()), trunk=trunk)
                     sched.started(slot, index, loop.n)
                 seq[slot] = st
 
@@ -576,20 +613,30 @@ class GenerationEngine:
                 slots_ = [st.slot for st in pending]
                 trunks = sched.group_first_fill(slots_, [st.past.arena.layout for st in pending]) if share_trunk else None
                 # (loop_args per sequence -> one list per argument)
-                loop = hf.slot_loop(*map(list, zip(*map(loop_args, pending))), slots=S, slot_index=slots_, each=True,
-                                    max_keys=cache_engine.max_ctx_length, trunks=trunks)
+                pasts, toks0, poss, max_news, paramss, seeds_, hists, stops = map(list, zip(*map(loop_args, pending)))
+                if drafts:
+                    loop = hf.lookup_slot_loop(pasts, toks0, poss, max_news, drafts, [st.corpus for st in pending], stop_ids=stops,
+                                               slots=S, max_keys=cache_engine.max_ctx_length, trunks=trunks, each=True,
+                                               slot_index=slots_, params=paramss, seeds=seeds_, histories=hists,
+                                               hist_cap=2 * cache_engine.max_ctx_length)
+                if loop is None:
+                    loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
+                                        max_keys=cache_engine.max_ctx_length, trunks=trunks)
                 if loop is None:
                     raise RuntimeError("serve: the model refused a batched decode loop over these caches")
                 for k, st in enumerate(pending):
                     st.k = k
                 pending.clear()
             i = 0
+            if loop is not None:
+                read, read_k = _reader(loop)                       # (one read loop for k = 0 and k > 0)
             while seq:
-                # the look-ahead rule of _pump_slots over sequences that start at different replays (slot_scheduler.wants_look_ahead)
+                # the look-ahead rule of _pump_slots over sequences that start at different replays (slot_scheduler.wants_look_ahead):
+                # the step in flight cannot exhaust a budget -- a sequence has room for more than its k + 1 tokens
                 while loop.n <= i:
                     loop.enqueue()
                 if loop.n == i + 1 and wants_look_ahead(
-                        [(loop._start[st.k], st.last_step - max(0, i - loop._start[st.k])) for st in seq.values()], i):
+                        [(loop._start[st.k], st.last_step - (len(st.new_ids) - 1)) for st in seq.values()], i, read_k):
                     loop.enqueue()                                 # the replay AFTER the one whose tokens are read below
                 ms = loop.elapsed_ms(i)
                 stats["rows"] += S
@@ -597,22 +644,29 @@ class GenerationEngine:
                     st = seq[slot]
                     if loop._start[st.k] > i:
                         continue
-                    token = loop.token(st.k, i)
-                    out = None
-                    if token is None:                              # (the device switched the slot off: its arena is full)
+                    toks = read(st.k, i)
+                    outs = []
+                    if not toks:                                   # (the device switched the slot off: its arena is full)
                         st.done = True
                     else:
                         stats["live_rows"] += 1
                         st.total_ms += ms
-                        out = st.emit(token)
-                        if st.ended_on_the_host(token):
-                            loop.kill(st.k)                        # a stop string or a stop id past the first 8
+                        for token in toks:
+                            out = st.emit(token)
+                            if read_k:
+                                stats["tokens"] += 1
+                            if out is not None:
+                                outs.append(out)
+                            if st.ended_on_the_host(token):
+                                loop.kill(st.k)                    # a stop string or a stop id past the first 8
+                            if st.done:                            # (the rest of the step lies behind the sequence's end)
+                                break
                     if st.done:
-                        loop.retire(st.k, len(st.new_ids) - 1)
+                        loop.retire(st.k, len(st.new_ids) - 1)     # the TOKENS consumed (= the replays of a one-token loop)
                         del seq[slot]
                         st.past = None
                         sched.finished(slot, i)
-                    if out is not None:
+                    for out in outs:
                         yield st.index, out
                 yield from admit_free_slots()
                 i += 1
@@ -620,6 +674,8 @@ class GenerationEngine:
             # also when the consumer abandons the generator at a yield: every arena's length goes back to what was consumed
             if loop is not None:
                 stats["replays"] = loop.n
+                if drafts:
+                    stats["steps"] = loop.n
                 loop.close({st.k: len(st.new_ids) - 1 for st in seq.values() if st.k is not None})
             del seq, loop, pending
             gc.collect()

@@ -402,6 +402,17 @@ class SampleLookupLoop(LookupLoop):
                                      st["ring"], st["ctr"], self.RING)
 
 
+def lookup_admit_history(corpus, token: int, max_new: int, hist_cap: int) -> list:
+    """The draft history a sequence enters a ``LookupSlotLoop(each=True)`` with: ``corpus ++ [token]``, the OLDEST corpus ids
+    dropped until ``hist_len + max_new <= hist_cap`` (the buffer is fixed when the loop is built: the captured step holds it).
+    ValueError when ``max_new + 1`` alone does not fit."""
+    if max_new + 1 > hist_cap:
+        raise ValueError(f"lookup admission: max_new + 1 = {max_new + 1} ids do not fit a draft history of {hist_cap}")
+    keep = hist_cap - max_new - 1
+    ids = [int(t) for t in corpus]
+    return ids[max(0, len(ids) - keep):] + [int(token)]
+
+
 class SlotLoop:
     """Batched decode: up to 16 sequences, each in a batch-1 arena of its own, advanced together by one captured step.
 
@@ -751,8 +762,14 @@ class LookupSlotLoop:
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
-                 slots: Optional[int] = None, max_keys: Optional[int] = None, trunks=None):
+                 slots: Optional[int] = None, max_keys: Optional[int] = None, trunks=None, each: bool = False, slot_index=None,
+                 params=None, seeds=None, histories=None, hist_cap: Optional[int] = None):
         n = len(arenas)
+        self.each = bool(each)
+        if each:
+            self._init_each(model, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, slots, max_keys, trunks, slot_index,
+                            params, seeds, histories, hist_cap)
+            return
         S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= n)
         assert 1 <= n <= S <= SlotLoop.MAX_SLOTS and 1 <= k <= 15 and S * (k + 1) <= self.MAX_ROWS, (n, S, k)
         assert len(tokens) == n and len(positions) == n and len(corpora) == n and len(stop_ids) <= 8 and max_new >= 1
@@ -826,6 +843,158 @@ class LookupSlotLoop:
         self._ring3d = st["ring"].view(S, self.RING, k + 2)
         torch.cuda.current_stream().synchronize()        # (the pageable sources of the copies above may go now)
 
+    # ---- per-slot sampling state and admission (each=True) ---------------------------------------------------
+    def _init_each(self, model, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, slots, max_keys, trunks, slot_index,
+                   params, seeds, histories, hist_cap):
+        """The loop over ``pc_lookup_verify_slots_each``: every initial sequence enters through ``admit``'s path, at replay 0.
+        ``max_new`` / ``params`` / ``stop_ids``: one value for all sequences or a list with one per sequence.  ``hist_cap``: the
+        ids a slot's draft history holds (fixed here: the captured step holds the buffer), default 8192."""
+        n = len(arenas)
+        idx = list(range(n)) if slot_index is None else [int(i) for i in slot_index]
+        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= max(idx) + 1)
+        assert 1 <= n and len(set(idx)) == n and 0 <= min(idx) and max(idx) < S <= SlotLoop.MAX_SLOTS, (n, idx, S)
+        assert 1 <= k <= 15 and S * (k + 1) <= self.MAX_ROWS, (S, k)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+        max_news, paramss = per(max_new), per(params)
+        stops = list(stop_ids) if len(stop_ids) and isinstance(stop_ids[0], (list, tuple)) else [tuple(stop_ids)] * n
+        assert len(tokens) == n and len(positions) == n and len(corpora) == n and len(max_news) == n and len(paramss) == n and len(stops) == n
+        self.m, self.S, self.k, self.nmax, self.max_new = model, S, int(k), int(nmax), max(max_news)
+        self.idx, self.arenas, self.len0, self.trunks = [], [], [], []
+        trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
+        shared = any(l is not None for l, _ in trunks)
+        for j, (l, T) in enumerate(trunks):
+            assert l is None or (trunks[l] == (l, T) and 0 < T <= arenas[j].length and T <= arenas[l].length), (j, trunks)
+        if max_keys is None:
+            max_keys = (max(a.length + mn for a, mn in zip(arenas, max_news)) + k + 1 + 63) // 64 * 64
+        self.max_keys = int(max_keys)
+        self.nsplit = model._slot_nsplit(S, self.max_keys)
+        self.nsplit_trunk = model._slot_nsplit(1, self.max_keys) if shared else 0
+        st = self.st = model._lookup_slot_state(S, k, 8192 if hist_cap is None else int(hist_cap), each=True)
+        self.hist_cap = st["hist"].shape[1]
+        model._live_loop = self
+        st["live"].zero_()
+        st["leader"].fill_(-1)
+        st["trunk"].zero_()
+        st["ndraft"].zero_()
+        st["ctr"].zero_()
+        self.logits = st["logits"]
+        self.n = 0
+        self.events = {}
+        self.host = torch.zeros((self.RING, S, k + 2), dtype=torch.int32, pin_memory=True)
+        self._ring3d = st["ring"].view(S, self.RING, k + 2)
+        self._start, self._end, self._killed = [], [], []
+        self._slot_seq = [None] * S            # the newest sequence of every slot
+        self._retired = set()
+        hw = (model.config.vocab_size + 31) // 32
+        self._arm_cap = _native.lookup_slot_arm_bytes(hw, self.hist_cap)
+        self._arm_ring = [[torch.zeros(self._arm_cap, dtype=torch.uint8, pin_memory=True), torch.cuda.Event(), False] for _ in range(4)]
+        self._arm_next = 0
+        self._arm_state = _native.lookup_slot_state(st["kv_base"], st["cap"], st["len"], st["live"], st["leader"], st["trunk"], st["ids"],
+                                                    st["pos"], st["ndraft"], st["budget"], st["hist_len"], st["ctr"], st["draws"],
+                                                    st["seeds"], st["params_each"], st["stop"], st["bits"], st["hist"])
+        seeds = [0] * n if seeds is None else list(seeds)
+        histories = [()] * n if histories is None else list(histories)
+        for j in range(n):
+            l, T = trunks[j]
+            self._admit(idx[j], arenas[j], tokens[j], positions[j], max_news[j], paramss[j], seeds[j], histories[j], stops[j],
+                        corpora[j], None if l is None else (idx[l], T))
+
+    @torch.inference_mode()
+    def admit(self, slot_index: int, past, token: int, position: int, max_new: int, params, seed: int, history, stop_ids, corpus,
+              trunk=None) -> int:
+        """A new sequence into slot ``slot_index`` of a running ``each=True`` loop, from the next replay on (``SlotLoop.admit``'s
+        contract): the arena behind ``past`` feeds ``token`` at ``position`` and may emit ``max_new`` tokens, with its own ``params``
+        (None / plain greedy: argmax), random stream ``seed`` (continuing at step 1), penalty ``history`` ids, up to 8
+        ``stop_ids`` and the ``corpus`` its drafts may copy from (``lookup_admit_history``: the oldest ids go where the history
+        buffer is too small).  ``trunk = (leader slot, T)``.  Only legal when the slot's previous sequence was retired.
+        -> the new sequence's index."""
+        if not self.each:
+            raise RuntimeError("LookupSlotLoop.admit needs a loop built with each=True")
+        a = self.m._loop_arena(past)
+        if a is None:
+            raise RuntimeError("LookupSlotLoop.admit: the cache is not a staged batch-1 arena")
+        a.materialize()
+        return self._admit(int(slot_index), a, token, position, max_new, params, seed, history, stop_ids, corpus, trunk)
+
+    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, corpus, trunk) -> int:
+        m, k = self.m, self.k
+        if getattr(m, "_live_loop", None) is not self:
+            raise RuntimeError("LookupSlotLoop: another device loop on this model took over")
+        if not 0 <= s < self.S or max_new < 1:
+            raise ValueError(f"LookupSlotLoop.admit: slot {s} outside [0, {self.S}) or max_new < 1")
+        hist = lookup_admit_history(corpus, token, int(max_new), self.hist_cap)
+        prev = self._slot_seq[s]
+        if prev is not None and prev not in self._retired:
+            raise RuntimeError(f"LookupSlotLoop.admit: the sequence in slot {s} was not retired")
+        running = [j for j in self._slot_seq if j is not None and j not in self._retired]
+        if any(a is self.arenas[j] for j in running):
+            raise RuntimeError("LookupSlotLoop.admit: the arena belongs to a running sequence")
+        need = a.length + max_new + k + 2
+        if need > a.cap:
+            a = a.grown(max(need, 2 * a.cap))
+        m._tail_done(a, 0, 1, a.length)
+        leader, T = (-1, 0) if trunk is None else (int(trunk[0]), int(trunk[1]))
+        if leader >= 0:
+            lead = self._slot_seq[leader] if leader != s else None
+            la = a if leader == s else (None if lead is None else self.arenas[lead])
+            if not self.nsplit_trunk or la is None or not 0 < T <= a.length or T > la.cap:
+                raise ValueError(f"LookupSlotLoop.admit: no trunk of {T} rows led by slot {leader} in this loop")
+            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1" and la is not a and \
+                    not torch.equal(a.buf[:, :, :, :, :T], la.buf[:, :, :, :, :T]):
+                raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of the sequence for slot {s} differ from its trunk leader's "
+                                   f"(slot {leader})")
+        stop_ids = [int(t) for t in stop_ids]
+        assert len(stop_ids) <= 8, "at most 8 stop ids live on the device (the host kills for the rest)"
+        sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
+        blk_p = sample_params_block(params, 0) if sampled else _native.sample_params_bytes(0.0, 1.0, 1.0, -1, 0)
+        V = m.config.vocab_size
+        hw = (V + 31) // 32
+        # the next pinned block of the ring, once the launch that read it last has finished (SlotLoop._admit's rule)
+        ent = self._arm_ring[self._arm_next]
+        self._arm_next = (self._arm_next + 1) % len(self._arm_ring)
+        if ent[2]:
+            ent[1].synchronize()
+        arr = ent[0].numpy()
+        b = _native.LookupSlotArmBlock.from_buffer(arr)
+        b.slot, b.cap, b.kv_base, b.len, b.pos, b.id = s, a.cap, a.buf.data_ptr(), a.length, int(position), int(token)
+        b.leader, b.trunk, b.budget, b.counter, b.hist_words, b.hist_len = leader, T, int(max_new), self.n, hw, len(hist)
+        b.seed = int(seed) & (2 ** 63 - 1)
+        b.params = _native.SampleParams.from_buffer_copy(blk_p)
+        for j in range(8):
+            b.stop_ids[j] = stop_ids[j] if j < len(stop_ids) else -1
+        del b
+        n0 = ctypes.sizeof(_native.LookupSlotArmBlock)
+        hb = arr[n0:n0 + 4 * hw].view(np.int32)
+        if sampled:
+            hb[:] = _history_bits(history, V).numpy()
+        else:
+            hb[:] = 0
+        n1 = n0 + ((4 * hw + 7) & ~7)
+        arr[n1:n1 + 4 * len(hist)].view(np.int32)[:] = np.asarray(hist, dtype=np.int32)
+        _native.lookup_slot_arm(ent[0], _native.lookup_slot_arm_bytes(hw, len(hist)), self._arm_state, self.S, k, self.hist_cap)
+        ent[1].record()
+        ent[2] = True
+        if prev is not None:
+            self._end[prev] = self.n
+        j = len(self.arenas)
+        self.arenas.append(a)
+        self.len0.append(a.length)
+        self.idx.append(s)
+        self.trunks.append((None, 0) if leader < 0 else (leader, T))
+        self._start.append(self.n)
+        self._end.append(None)
+        self._killed.append(None)
+        self._slot_seq[s] = j
+        return j
+
+    def retire(self, j: int, consumed_tokens: int) -> None:
+        """Sequence ``j`` is over and its consumer used ``consumed_tokens`` of its tokens: its arena's ``length`` goes to exactly that
+        (``close``'s rule, for one sequence) -- before the buffer is staged again for the slot's next sequence."""
+        a = self.arenas[j]
+        a.length = self.len0[j] + int(consumed_tokens)
+        a.tail_base, a.tail_len = -1, 0
+        self._retired.add(j)
+
     @torch.inference_mode()
     def enqueue(self) -> int:
         m = self.m
@@ -849,7 +1018,12 @@ class LookupSlotLoop:
         return i
 
     def tokens(self, j: int, i: int):
-        """The tokens sequence ``j`` emitted at step ``i`` (empty: the sequence was over, or had no budget left)."""
+        """The tokens sequence ``j`` emitted at step ``i`` (empty: the sequence was over, or had no budget left).  ``each=True``:
+        ``i`` is the global replay index -- empty before the sequence's start and from the replay its slot's next sequence entered."""
+        if self.each:
+            if i < self._start[j] or (self._end[j] is not None and i >= self._end[j]):
+                return []
+            j = self.idx[j]
         self.events[i][2].synchronize()
         rec = self.host[i % self.RING][j]
         c = int(rec[0])
@@ -857,6 +1031,12 @@ class LookupSlotLoop:
 
     def kill(self, j: int) -> None:
         """Switch sequence ``j`` off from the next replay on (ordered behind the replays already enqueued)."""
+        if self.each:
+            if self._end[j] is not None:                  # (the slot holds a later sequence)
+                return
+            if self._killed[j] is None:
+                self._killed[j] = self.n
+            j = self.idx[j]
         self.st["live"][j: j + 1].fill_(0)
 
     def elapsed_ms(self, i: int) -> float:
@@ -866,8 +1046,13 @@ class LookupSlotLoop:
 
     def close(self, consumed) -> None:
         """``consumed[j]``: how many of its TOKENS sequence j's consumer used.  Each arena's ``length`` goes to exactly that (rows
-        behind it -- rejected drafts, look-ahead replays -- are rewritten before anything reads them); the loop state is released."""
+        behind it -- rejected drafts, look-ahead replays -- are rewritten before anything reads them); the loop state is released.
+        ``each=True``: a dict over the sequences that were not retired one by one."""
+        if isinstance(consumed, dict):
+            consumed = [consumed.get(j) for j in range(len(self.arenas))]
         for a, l0, c in zip(self.arenas, self.len0, consumed):
+            if c is None:
+                continue
             a.length = l0 + int(c)
             a.tail_base, a.tail_len = -1, 0
         if getattr(self.m, "_live_loop", None) is self:
@@ -2356,18 +2541,25 @@ class LlamaHIP:
     # ---- prompt-lookup drafts in the slot loop (LookupSlotLoop) ----------------------------------------------------------
     def lookup_slot_loop(self, pasts, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
                          slots: Optional[int] = None, max_keys: Optional[int] = None, share_trunk: bool = False,
-                         min_trunk: Optional[int] = None, trunks=None) -> Optional["LookupSlotLoop"]:
+                         min_trunk: Optional[int] = None, trunks=None, each: bool = False, slot_index=None, params=None, seeds=None,
+                         histories=None, hist_cap: Optional[int] = None) -> Optional["LookupSlotLoop"]:
         """``slot_loop`` with prompt-lookup drafts: up to ``k + 1`` greedy tokens per sequence and step (``LookupSlotLoop``).
         ``corpora[j]``: the ids sequence j's drafts may copy from besides its own output (``lookup_loop``'s ``corpus_ids``).  None
         where ``slot_loop`` gives None, where the model has no lookup step (``lookup_available``) and where ``S * (k + 1)``
         exceeds the 64 rows of the weight-streaming projections -- the caller then runs ``slot_loop``.  ``share_trunk`` /
         ``min_trunk`` / ``trunks``: ``slot_loop``'s -- sequences that staged the same leading module rows read them from one
         arena, once per step for all draft rows of the group (``pc_attn_verify_slots_trunk``); a batch without such a group runs
-        the unshared step, bit for bit."""
+        the unshared step, bit for bit.
+        ``each``: the step ends in ``pc_lookup_verify_slots_each`` -- ``params`` (None / plain greedy: argmax),
+        ``max_new`` and ``stop_ids`` may then be lists with one entry per sequence, ``seeds`` / ``histories`` are ``slot_loop``'s,
+        sequence j sits in slot ``slot_index[j]`` and ``LookupSlotLoop.admit`` puts new sequences into slots whose sequence was
+        retired.  ``hist_cap``: the ids a slot's draft history holds, fixed for the loop (default 8192)."""
         n = len(pasts)
-        if not (self.slot_loop_available() and self.lookup_available()) or not 1 <= n <= SlotLoop.MAX_SLOTS or len(stop_ids) > 8:
+        per_seq_stops = each and len(stop_ids) and isinstance(stop_ids[0], (list, tuple))
+        if not (self.slot_loop_available() and self.lookup_available()) or not 1 <= n <= SlotLoop.MAX_SLOTS or \
+                (max(map(len, stop_ids)) if per_seq_stops else len(stop_ids)) > 8:
             return None
-        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= n)
+        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= (n if slot_index is None else max(slot_index) + 1))
         if not 1 <= k <= 15 or not n <= S <= SlotLoop.MAX_SLOTS or S * (k + 1) > LookupSlotLoop.MAX_ROWS:
             return None
         arenas = []
@@ -2379,6 +2571,9 @@ class LlamaHIP:
             arenas.append(a)
         if trunks is None and share_trunk:
             trunks = common_trunks([a.layout for a in arenas], min_trunk)
+        if each:
+            return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
+                                  slot_index, params, seeds, histories, hist_cap)
         return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks)
 
     def lookup_trunk_available(self) -> bool:
@@ -2386,7 +2581,7 @@ class LlamaHIP:
         return bool(self.lookup_available() and self.slot_loop_available())
 
     @torch.inference_mode()
-    def _lookup_slot_state(self, S: int, k: int, hist_need: int) -> dict:
+    def _lookup_slot_state(self, S: int, k: int, hist_need: int, each: bool = False) -> dict:
         """Device words of the (S, k) lookup step (one set per (S, k): the captured steps hold their addresses).  The history
         buffer grows in powers of two; the graph key carries its address."""
         sts = self.__dict__.setdefault("_lookup_slot_sts", {})
@@ -2407,6 +2602,14 @@ class LlamaHIP:
             while cap < hist_need:
                 cap *= 2
             st["hist"] = torch.zeros((S, cap), dtype=torch.int32, device=dev)
+        if each and "bits" not in st:
+            # per-slot sampling state of the each=True step (pc_lookup_verify_slots_each): parameter blocks, seeds, penalty
+            # bitmaps (``hist`` is the token history here), draw counters and the per-row scratch
+            R, hw = S * (k + 1), (V + 31) // 32
+            z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)
+            st.update(params_each=z(S * ctypes.sizeof(_native.SampleParams), torch.uint8), seeds=z(S, torch.int64),
+                      bits=z((S, hw), torch.int32), draws=z(S, torch.int32), row_bits=z(R * hw, torch.int32),
+                      row_token=z(R, torch.int32))
         return st
 
     def _lookup_slot_graph(self, loop: "LookupSlotLoop"):
@@ -2414,6 +2617,9 @@ class LlamaHIP:
         st, S, k = loop.st, loop.S, loop.k
         key = ("slots", "lookup", S, k, loop.nsplit) + (("trunk", loop.nsplit_trunk) if loop.nsplit_trunk else ()) + \
             (loop.nmax, st["hist"].data_ptr(), st["hist"].shape[1])
+        each = bool(getattr(loop, "each", False))
+        if each:
+            key += ("each",)
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2424,18 +2630,19 @@ class LlamaHIP:
         # nothing but the record counters, which are put back behind it with the live words
         live, ctr = st["live"].clone(), st["ctr"].clone()
         st["live"].zero_()
-        self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk)
+        self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk, **({"each": True} if each else {}))
         torch.cuda.synchronize()
         prime_graph_capture(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk)
+            self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk, **({"each": True} if each else {}))
         st["live"].copy_(live)
         st["ctr"].copy_(ctr)
         self._graphs[key] = (g, st["hist"])
         return g
 
-    def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3, nsplit_trunk: int = 0) -> None:
+    def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3, nsplit_trunk: int = 0,
+                              each: bool = False) -> None:
         """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
         k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
         projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop.
@@ -2503,6 +2710,11 @@ class LlamaHIP:
                 pending = KQ
             n.rmsnorm_frag(x, self.norm, xh, xl, R, hid, eps, slabs, pending)
             n.gemm_skinny(self.lm_head_f, xh, xl, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
+        if each:                      # the sampler on every row, per slot
+            n.lookup_verify_slots_each(st["logits"], V, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
+                                       st["row_token"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"], st["cap"],
+                                       st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
+            return
         n.lookup_verify_slots(st["logits"], V, V, S, k, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"],
                               st["cap"], st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
 

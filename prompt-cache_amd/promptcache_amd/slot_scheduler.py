@@ -145,12 +145,12 @@ class SlotScheduler:
         return None
 
 
-def wants_look_ahead(seqs, i: int) -> bool:
+def wants_look_ahead(seqs, i: int, k: int = 0) -> bool:
     """Whether replay i + 1 is enqueued before the host reads replay i's tokens.  ``seqs``: ``(start, left)`` of every running
-    sequence -- the replay it entered at, the steps its budget still allows from replay max(i, start) on.  Yes when a sequence
-    enters at i + 1 or one has budget beyond replay i: the GPU then never waits for the host; a stop id or stop string the host
-    has not seen yet wastes at most that one replay."""
-    return any(start > i or left > 1 for start, left in seqs)
+    sequence -- the replay it entered at, the tokens its budget still allows from replay max(i, start) on.  Yes when a sequence
+    enters at i + 1 or one has budget beyond replay i, which yields ``k + 1`` tokens at most: the GPU then never waits for the host;
+    a stop id or stop string the host has not seen yet wastes at most that one replay."""
+    return any(start > i or left > k + 1 for start, left in seqs)
 
 
 def replay_count(max_new_tokens: List[int], slots: int) -> int:

@@ -7,6 +7,12 @@ counts the host simulation gives for the same lengths (slot_scheduler.replay_cou
 
     python tools/serve_bench.py [--out profiles/r10_serve.json]
     python tools/serve_bench.py --only-serve        # (b) alone, warm + one: the run to put under rocprofv3 --kernel-trace --stats
+    python tools/serve_bench.py --lookup 3 7 --repeats 5 [--out profiles/serve_lookup_bench.json]
+
+--lookup K [K ...]: prompt-lookup drafts in the serving loop (serve(lookup=K)) against plain serve, legs interleaved in
+one process: per K a leg whose corpus is the plain leg's own output of the request behind what serve gives it (every draft right)
+and a leg with an empty corpus (nothing to copy but the sequence's own output).  Medians of --repeats; tokens per second over the
+whole run, prefills included, plus replays and tokens per replay.
 """
 import argparse
 import dataclasses
@@ -42,13 +48,13 @@ def waves(ge, eng, prompts, lens, slots):
     return time.perf_counter() - t0, sum(lens), replays
 
 
-def served(ge, eng, prompts, lens):
+def served(ge, eng, prompts, lens, lookup=0):
     """(b): serve.  -> (seconds, tokens decoded, replays, idle-row fraction)."""
     base = GenerationParameters(temperature=0.0, stop_token_ids=[], stop_str=[])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _r, _out in ge.serve(eng, ((p, dataclasses.replace(base, max_new_tokens=n)) for p, n in zip(prompts, lens)),
-                             stream_interval=10 ** 9):
+                             stream_interval=10 ** 9, lookup=lookup):
         pass
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -56,8 +62,49 @@ def served(ge, eng, prompts, lens):
     return dt, sum(len(t) for t in ge.last_serve_tokens.values()), st["replays"], 1.0 - st["live_rows"] / max(1, st["replays"] * eng.slots)
 
 
+def lookup_legs(ge, eng, prompts, lens, ks, repeats, slots):
+    """Plain serve and, per k, serve(lookup=k) with a full-acceptance and an empty corpus, interleaved.  -> the result dict."""
+    real = type(ge)._lookup_corpus
+    served(ge, eng, prompts, lens)                                    # (the plain leg's outputs: what a right draft copies)
+    answers = {r: list(t) for r, t in ge.last_serve_tokens.items()}
+
+    def leg(k, corpus):
+        order = iter(range(len(prompts)))                             # (asked once per request, in the order they are pulled)
+        if corpus == "right":
+            ge._lookup_corpus = lambda cache, ids: real(cache, ids) + answers[next(order)]
+        elif corpus == "none":
+            ge._lookup_corpus = lambda cache, ids: []
+        try:
+            dt, n, replays, idle = served(ge, eng, prompts, lens, k)
+        finally:
+            ge.__dict__.pop("_lookup_corpus", None)
+        same = sum(answers[r] == list(t) for r, t in ge.last_serve_tokens.items())
+        return dict(tok_s=n / dt, replays=replays, tokens=n, seconds=dt, same_as_plain=same)
+    legs = [("plain", 0, None)] + [(f"lookup{k}_{c}", k, c) for k in ks for c in ("right", "none")]
+    for name, k, c in legs[1:]:
+        leg(k, c)                                                     # warm: the (S, k) step is captured
+    runs = {name: [] for name, _, _ in legs}
+    for _ in range(repeats):
+        for name, k, c in legs:
+            runs[name].append(leg(k, c))
+            print(f"{name}: {runs[name][-1]['tok_s']:.1f} tok/s, {runs[name][-1]['replays']} replays", file=sys.stderr, flush=True)
+    out = {}
+    for name, rs in runs.items():
+        out[name] = {"tok_s": round(statistics.median(r["tok_s"] for r in rs), 1), "replays": rs[-1]["replays"], "tokens": rs[-1]["tokens"],
+                     "tokens_per_replay": round(rs[-1]["tokens"] / max(1, rs[-1]["replays"]), 2),
+                     "requests_equal_to_plain": rs[-1]["same_as_plain"]}
+    for name in out:
+        out[name]["over_plain"] = round(out[name]["tok_s"] / out["plain"]["tok_s"], 3)
+    return {"shape": "llama2-7b (random init)", "requests": len(prompts), "slots": slots, "max_new_tokens": lens,
+            "how": "greedy; decoded tokens per second over the whole serve run, prefills included; plain serve and serve(lookup=k) legs "
+                   f"interleaved in one process, {repeats} repetitions, median; 'right': the corpus holds the plain leg's output of the "
+                   "request (every draft right), 'none': an empty corpus (nothing to copy but the sequence's own output)",
+            "legs": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lookup", type=int, nargs="*", default=[])
     ap.add_argument("--requests", type=int, default=32)
     ap.add_argument("--slots", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=3)
@@ -77,6 +124,13 @@ def main():
     ge = GenerationEngine(lm)
     assert ge.serve_plan()[0], ge.serve_plan()[1]
     served(ge, eng, prompts, lens)                                    # warm: graphs captured, code objects loaded
+    if args.lookup:
+        line = json.dumps(lookup_legs(ge, eng, prompts, lens, args.lookup, args.repeats, args.slots))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     if args.only_serve:
         dt, n, replays, idle = served(ge, eng, prompts, lens)
         print(json.dumps({"serve_tok_s": round(n / dt, 1), "replays": replays, "idle_row_fraction": round(idle, 3)}))
