@@ -413,7 +413,253 @@ def lookup_admit_history(corpus, token: int, max_new: int, hist_cap: int) -> lis
     return ids[max(0, len(ids) - keep):] + [int(token)]
 
 
-class SlotLoop:
+def _is_sampled(params) -> bool:
+    """Whether ``params`` take the sampled chain (None / greedy without a repetition penalty: the argmax of the raw row)."""
+    return params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
+
+
+def _slot_trunks(trunks, lengths) -> list:
+    """The shared trunks of a slot loop, normalised and checked: per sequence ``(leader index | None, T)`` -- rows [0, T) of the
+    sequence's arena are the bytes of the same rows of the leader's, and every step reads them from the leader's arena once for
+    the group.  None: nobody shares.  A leader leads itself over the same T rows, and both arenas (``lengths``) hold them."""
+    n = len(lengths)
+    trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
+    for k, (l, T) in enumerate(trunks):
+        assert l is None or (trunks[l] == (l, T) and 0 < T <= lengths[k] and T <= lengths[l]), (k, trunks)
+    return trunks
+
+
+def _trunk_verify(a, la, T: int, who: str, leader: str) -> None:
+    """``PC_TRUNK_VERIFY=1``: rows [0, T) of arena ``a`` must be the bytes of the same rows of its trunk leader's arena ``la``."""
+    if os.environ.get("PC_TRUNK_VERIFY", "0") == "1" and la is not a and not torch.equal(a.buf[:, :, :, :, :T], la.buf[:, :, :, :, :T]):
+        raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of {who} differ from its trunk leader's ({leader})")
+
+
+def _fill_arm_block(arr, header, fields: dict, seed: int, params, stop_ids, history, vocab: int) -> int:
+    """The host block of ``pc_slot_arm`` / ``pc_lookup_slot_arm`` into ``arr`` (writable uint8): the header (``header``: the ctypes
+    image, ``SlotArmBlock`` | ``LookupSlotArmBlock``) with ``fields`` by name, ``hist_words``, the seed's low 63 bits, the parameter
+    block of ``params`` and eight stop ids (-1: none), then the penalty bitmap of ``history`` (zeros where ``params`` do not
+    sample).  -> the offset behind the bitmap, padded to 8 bytes (where the lookup block's history ids go)."""
+    hw, sampled = (vocab + 31) // 32, _is_sampled(params)
+    b = header.from_buffer(arr)
+    for name, v in fields.items():
+        setattr(b, name, v)
+    b.hist_words = hw
+    b.seed = int(seed) & (2 ** 63 - 1)
+    b.params = _native.SampleParams.from_buffer_copy(sample_params_block(params, 0) if sampled else
+                                                     _native.sample_params_bytes(0.0, 1.0, 1.0, -1, 0))   # greedy: argmax of the raw row
+    for j in range(8):
+        b.stop_ids[j] = stop_ids[j] if j < len(stop_ids) else -1
+    del b
+    n0 = ctypes.sizeof(header)
+    arr[n0:n0 + 4 * hw].view(np.int32)[:] = _history_bits(history, vocab).numpy() if sampled else 0
+    return n0 + ((4 * hw + 7) & ~7)
+
+
+class _SlotLoopHost:
+    """The host side of a batched device loop, once for ``SlotLoop`` and ``LookupSlotLoop``: slots and arenas,
+    shared trunks, the per-sequence tables, admission into a running ``each=True`` loop through a ring of pinned arm blocks, and
+    the replay / ring / event protocol ``GenerationEngine`` drives.  What a leaf says itself: the ring record (``_record``), the
+    split counts, its state words and graph, the arm launch, when a slot may be taken again and its own bookkeeping."""
+
+    RING = 1024
+    MAX_SLOTS = 16
+    MAX_ROWS = 64                    # rows of one step, S * (k + 1): what the weight-streaming projections take
+    k = 0                            # draft rows per slot
+    ctr0 = 0                         # the device step counter at replay 0 (step i's record lands in ring row (ctr0 + i) % RING)
+
+    def _build(self, model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each,
+               max_keys, corpora=None, hist_cap=None) -> None:
+        """``each``: the step with per-slot sampling state -- ``max_new`` / ``params`` / ``stop_ids`` are one value for all
+        sequences or a list with one per sequence, and every initial sequence enters through ``admit``'s path, at replay 0."""
+        n, k = len(arenas), self.k
+        idx = list(range(n)) if slot_index is None else [int(i) for i in slot_index]
+        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= max(idx) + 1)
+        assert 1 <= n and len(set(idx)) == n and 0 <= min(idx) and max(idx) < S <= self.MAX_SLOTS, (n, idx, S)
+        assert S * (k + 1) <= self.MAX_ROWS, (S, k)
+        per = lambda v: list(v) if each and isinstance(v, (list, tuple)) else [v] * n
+        max_news, paramss = per(max_new), per(params)
+        stops = list(stop_ids) if each and len(stop_ids) and isinstance(stop_ids[0], (list, tuple)) else [tuple(stop_ids)] * n
+        assert len(tokens) == n and len(positions) == n and len(max_news) == n and len(paramss) == n and len(stops) == n
+        assert (corpora is None or len(corpora) == n) and (each or (len(stop_ids) <= 8 and max_new >= 1))
+        self.m, self.S, self.each, self.max_new = model, S, bool(each), max(max_news)
+        self.idx, self.arenas, self.len0, self.trunks = [], [], [], []
+        self._start = []                  # the replay at which sequence k entered the loop
+        self._killed = []                 # step count at which kill(k) took effect
+        self._slot_seq = [None] * S       # the newest sequence of every slot
+        self._retired = set()
+        self.n = 0
+        self.events = {}                  # step -> (start, end, tokens on the host); steps the ring no longer holds are dropped
+        if not each:
+            arenas = [self._prepared(a, max_new) for a in arenas]
+        trunks = _slot_trunks(trunks, [a.length for a in arenas])
+        if not each:
+            for j, (l, T) in enumerate(trunks):
+                if l is not None:
+                    _trunk_verify(arenas[j], arenas[l], T, f"sequence {j}", f"sequence {l}")
+        self._split_counts([a.length for a in arenas], max_news, trunks, max_keys)
+        st = self.st = self._make_state(tokens, corpora, hist_cap)
+        model._live_loop = self
+        self.logits = st["logits"]
+        self.host = torch.zeros((self.RING, S) + self._record, dtype=torch.int32, pin_memory=True)
+        self._ring = st["ring"].view((S, self.RING) + self._record)
+        if each:
+            st["live"].zero_()
+            st["leader"].fill_(-1)
+            st["trunk"].zero_()
+            nbytes, self._arm_state = self._arm_setup((model.config.vocab_size + 31) // 32)
+            self._arm_ring = [[torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True), torch.cuda.Event(), False] for _ in range(4)]
+            self._arm_next = 0
+            seeds = [0] * n if seeds is None else list(seeds)
+            histories = [()] * n if histories is None else list(histories)
+            for j, (l, T) in enumerate(trunks):
+                self._admit(idx[j], arenas[j], tokens[j], positions[j], max_news[j], paramss[j], seeds[j], histories[j], stops[j],
+                            None if l is None else (idx[l], T), None if corpora is None else corpora[j])
+            return
+        for s, a, trunk in zip(idx, arenas, trunks):
+            self._enter(s, a, trunk, max_new, stop_ids)
+
+        def col(vals, dtype, fill=0):
+            t = torch.full((S,), fill, dtype=dtype)
+            for s, v in zip(idx, vals):
+                t[s] = v
+            return t
+        st["kv_base"].copy_(col([a.buf.data_ptr() for a in arenas], torch.int64), non_blocking=True)
+        st["cap"].copy_(col([a.cap for a in arenas], torch.int32), non_blocking=True)
+        st["len"].copy_(col(self.len0, torch.int32), non_blocking=True)
+        st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
+        st["leader"].copy_(col([-1 if l is None else idx[l] for l, _ in trunks], torch.int32, -1), non_blocking=True)
+        st["trunk"].copy_(col([T for _, T in trunks], torch.int32), non_blocking=True)
+        st["budget"].copy_(col([max_new] * n, torch.int32), non_blocking=True)
+        self._fill_state(col, tokens, positions, max_new, params, seeds, histories, stop_ids)
+        torch.cuda.current_stream().synchronize()        # (the pageable sources of the copies above may go now)
+
+    def _prepared(self, a, max_new: int):
+        """The arena a sequence decodes in: room for every row the loop can write (no address may move under the captured step),
+        and rows are appended without residuals: a residual tail ends here."""
+        need = a.length + max_new + self.k + 2
+        if need > a.cap:
+            a = a.grown(max(need, 2 * a.cap))
+        self.m._tail_done(a, 0, 1, a.length)
+        return a
+
+    def _enter(self, s: int, a, trunk, max_new: int, stop_ids) -> int:
+        """Sequence number ``len(arenas)`` sits in slot ``s`` from replay ``n`` on: one more row of every per-sequence table."""
+        k, prev = len(self.arenas), self._slot_seq[s]
+        self.arenas.append(a)
+        self.len0.append(a.length)
+        self.idx.append(s)
+        self.trunks.append(trunk)
+        self._start.append(self.n)
+        self._killed.append(None)
+        self._slot_seq[s] = k
+        self._entered(k, prev, max_new, stop_ids)
+        return k
+
+    def _admit_arena(self, past):
+        name = type(self).__name__
+        if not self.each:
+            raise RuntimeError(f"{name}.admit needs a loop built with each=True")
+        a = self.m._loop_arena(past)
+        if a is None:
+            raise RuntimeError(f"{name}.admit: the cache is not a staged batch-1 arena")
+        return a
+
+    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, trunk, corpus=None) -> int:
+        m, name = self.m, type(self).__name__
+        if getattr(m, "_live_loop", None) is not self:
+            raise RuntimeError(f"{name}: another device loop on this model took over")
+        if not 0 <= s < self.S or max_new < 1:
+            raise ValueError(f"{name}.admit: slot {s} outside [0, {self.S}) or max_new < 1")
+        running, extra, hist = self._admit_check(s, corpus, token, int(max_new))
+        if any(a is self.arenas[k] for k in running):
+            raise RuntimeError(f"{name}.admit: the arena belongs to a running sequence")
+        a.materialize()
+        a = self._prepared(a, max_new)
+        leader, T = (-1, 0) if trunk is None else (int(trunk[0]), int(trunk[1]))
+        if leader >= 0:
+            lead = self._slot_seq[leader] if leader != s else None
+            la = a if leader == s else (None if lead is None else self.arenas[lead])
+            if not self.nsplit_trunk or la is None or not 0 < T <= a.length or T > la.cap:
+                raise ValueError(f"{name}.admit: no trunk of {T} rows led by slot {leader} in this loop")
+            _trunk_verify(a, la, T, f"the sequence for slot {s}", f"slot {leader}")
+        stop_ids = [int(t) for t in stop_ids]
+        assert len(stop_ids) <= 8, "at most 8 stop ids live on the device (the host kills for the rest)"
+        # the next pinned block of the ring, once the launch that read it last has finished
+        ent = self._arm_ring[self._arm_next]
+        self._arm_next = (self._arm_next + 1) % len(self._arm_ring)
+        if ent[2]:
+            ent[1].synchronize()
+        arr = ent[0].numpy()
+        fields = dict(slot=s, cap=a.cap, kv_base=a.buf.data_ptr(), len=a.length, pos=int(position), id=int(token), leader=leader,
+                      trunk=T, budget=int(max_new), counter=self.ctr0 + self.n, **extra)
+        off = _fill_arm_block(arr, self._arm_header, fields, seed, params, stop_ids, history, m.config.vocab_size)
+        self._arm(ent[0], arr, off, hist)
+        ent[1].record()
+        ent[2] = True
+        return self._enter(s, a, (None, 0) if leader < 0 else (leader, T), max_new, stop_ids)
+
+    def _set_length(self, a, length: int) -> None:
+        a.length = length
+
+    def retire(self, k: int, consumed: int) -> None:
+        """Sequence ``k`` is over and its consumer used ``consumed`` of what it produced (``close``'s unit): its arena's ``length``
+        goes to exactly that (``close``'s rule, for one sequence) -- before the buffer is staged again for the slot's next sequence."""
+        self._set_length(self.arenas[k], self.len0[k] + int(consumed))
+        self._retired.add(k)
+
+    @torch.inference_mode()
+    def enqueue(self) -> int:
+        if getattr(self.m, "_live_loop", None) is not self:
+            raise RuntimeError(f"{type(self).__name__}: another device loop on this model took over (one device-side generation "
+                               "per model at a time)")
+        g = self._graph()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        i = self.n
+        r = (self.ctr0 + i) % self.RING
+        if i >= self.RING:
+            self._ring_row_reused(i - self.RING)         # (row r still holds step i - RING)
+        self.host[r].copy_(self._ring[:, r], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self.events[i] = (e0, e1, done)
+        self.events.pop(i - self.RING, None)             # nobody can ask for a step whose ring row is being reused
+        self.n += 1
+        return i
+
+    def _ring_row_reused(self, step: int) -> None:
+        pass
+
+    def kill(self, k: int) -> None:
+        """Switch sequence ``k`` off from the next replay on (ordered behind the replays already enqueued)."""
+        s = self.idx[k]
+        self.st["live"][s: s + 1].fill_(0)
+        if self._killed[k] is None:
+            self._killed[k] = self.n
+
+    def elapsed_ms(self, i: int) -> float:
+        e0, e1, done = self.events[i]
+        done.synchronize()
+        return e0.elapsed_time(e1)
+
+    def close(self, consumed) -> None:
+        """``consumed[k]``: how much of what sequence k produced its consumer used (``SlotLoop``: steps, ``LookupSlotLoop``:
+        tokens).  Each arena's ``length`` goes to exactly that (rows behind it -- look-ahead replays, rejected drafts -- are dead:
+        rewritten before anything reads them), and the loop state is released.  An ``each=True`` loop: a dict over the sequences
+        that were not retired one by one."""
+        if isinstance(consumed, dict):
+            consumed = [consumed.get(k) for k in range(len(self.arenas))]
+        for a, l0, c in zip(self.arenas, self.len0, consumed):
+            if c is not None:
+                self._set_length(a, l0 + int(c))
+        if getattr(self.m, "_live_loop", None) is self:
+            self.m._live_loop = None
+
+
+class SlotLoop(_SlotLoopHost):
     """Batched decode: up to 16 sequences, each in a batch-1 arena of its own, advanced together by one captured step.
 
     GreedyLoop's protocol over SLOTS.  Every replay runs the layer stack over ``S`` rows (one per slot), RoPE + append and the
@@ -426,150 +672,77 @@ class SlotLoop:
     ``enqueue()`` -> step index; ``token(k, i)`` waits for step i only; ``logits`` is the ``[S][V]`` fp32 tensor of the last
     replay (row = slot index ``slot_index[k]``)."""
 
-    RING = 1024
-    MAX_SLOTS = 16
+    _record = ()                     # a step leaves one token per slot: ``host`` is [RING][S]
+    _arm_header = _native.SlotArmBlock
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, params=None, seeds=None, histories=None,
                  stop_ids=(), slots: Optional[int] = None, slot_index=None, trunks=None, each: bool = False,
                  max_keys: Optional[int] = None):
-        n = len(arenas)
-        idx = list(range(n)) if slot_index is None else [int(i) for i in slot_index]
-        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= max(idx) + 1)
-        assert 1 <= n and len(set(idx)) == n and 0 <= min(idx) and max(idx) < S <= self.MAX_SLOTS, (n, idx, S)
-        self.each = bool(each)
-        if each:
-            self._init_each(model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, S, idx, trunks, max_keys)
-            return
-        assert len(tokens) == n and len(positions) == n and len(stop_ids) <= 8 and max_new >= 1
-        self.m, self.S, self.idx, self.max_new = model, S, idx, max_new
-        grown = []
-        for a in arenas:                              # no address may move under the captured step
-            need = a.length + max_new + 2
-            grown.append(a.grown(max(need, 2 * a.cap)) if need > a.cap else a)
-            model._tail_done(grown[-1], 0, 1, a.length)       # rows are appended without residuals: a residual tail ends here
-        self.arenas = grown
-        self.len0 = [a.length for a in grown]
-        # shared trunks (slot_loop(share_trunk=True)): per sequence (leader index | None, T) -- rows [0, T) of the sequence's arena
-        # are the bytes of the same rows of the leader's, and every step reads them from the leader's arena once for the group
-        self.trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
-        self.nsplit_trunk = 0
-        if any(l is not None for l, _ in self.trunks):
-            for k, (l, T) in enumerate(self.trunks):
-                assert l is None or (self.trunks[l] == (l, T) and 0 < T <= self.len0[k] and T <= self.len0[l]), (k, self.trunks)
-            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1":
-                for k, (l, T) in enumerate(self.trunks):
-                    if l is not None and l != k and not torch.equal(grown[k].buf[:, :, :, :, :T], grown[l].buf[:, :, :, :, :T]):
-                        raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of sequence {k} differ from its trunk leader's "
-                                           f"(sequence {l})")
-            self.nsplit_trunk = model._slot_nsplit(len({l for l, _ in self.trunks if l is not None}), max(T for _, T in self.trunks))
-            self.nsplit = model._slot_nsplit(S, max(l0 - T for l0, (_, T) in zip(self.len0, self.trunks)) + max_new + 1)
-        else:
-            self.nsplit = model._slot_nsplit(S, max(self.len0) + max_new + 1)
-        if max_keys is not None:                          # split counts from the caller's bound, not from this batch
-            self.nsplit = model._slot_nsplit(S, int(max_keys))
-            if self.nsplit_trunk:
-                self.nsplit_trunk = model._slot_nsplit(1, int(max_keys))
-        st = self.st = model._slot_state(S)
-        model._live_loop = self
-        self.sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
-        self.ctr0 = 1 if self.sampled else 0           # (a sampled stream drew its first token at step 0: sample_token)
-        V = model.config.vocab_size
-        hw = (V + 31) // 32
+        self._alive = []                  # host mirror of the live words, after the newest step whose tokens were looked at
+        self._seen = 0                    # steps whose tokens the mirror has taken in
+        self._last = []                   # index of the last step that produced a token for sequence k (-1: none yet)
+        self._max_new, self._stops = [], []
+        self._active = []                 # sequences the mirror still follows
+        self._build(model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each,
+                    max_keys)
 
-        def col(vals, dtype, fill=0):
-            t = torch.full((S,), fill, dtype=dtype)
-            for k, v in zip(idx, vals):
-                t[k] = v
-            return t
-        st["kv_base"].copy_(col([a.buf.data_ptr() for a in grown], torch.int64), non_blocking=True)
-        st["cap"].copy_(col([a.cap for a in grown], torch.int32), non_blocking=True)
-        st["len"].copy_(col(self.len0, torch.int32), non_blocking=True)
+    def _split_counts(self, lens, max_news, trunks, max_keys) -> None:
+        """From raw key counts.  ``max_keys``: the caller's bound, instead of this batch's."""
+        m, S = self.m, self.S
+        shared = any(l is not None for l, _ in trunks)
+        if self.each:
+            if max_keys is None:
+                max_keys = max(l0 + mn for l0, mn in zip(lens, max_news)) + 1
+            self.nsplit = m._slot_nsplit(S, int(max_keys))
+            self.nsplit_trunk = m._slot_nsplit(1, int(max_keys)) if shared else 0
+            return
+        self.nsplit_trunk = 0
+        if shared:
+            self.nsplit_trunk = m._slot_nsplit(len({l for l, _ in trunks if l is not None}), max(T for _, T in trunks))
+            self.nsplit = m._slot_nsplit(S, max(l0 - T for l0, (_, T) in zip(lens, trunks)) + max_news[0] + 1)
+        else:
+            self.nsplit = m._slot_nsplit(S, max(lens) + max_news[0] + 1)
+        if max_keys is not None:
+            self.nsplit = m._slot_nsplit(S, int(max_keys))
+            if self.nsplit_trunk:
+                self.nsplit_trunk = m._slot_nsplit(1, int(max_keys))
+
+    def _make_state(self, tokens, corpora, hist_cap) -> dict:
+        return self.m._slot_state(self.S)
+
+    def _graph(self):
+        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each)
+
+    def _fill_state(self, col, tokens, positions, max_new, params, seeds, histories, stop_ids) -> None:
+        """The state words of the loop over ``pc_sample_advance_slots``: one parameter block and one stop list for all slots."""
+        st, S, n = self.st, self.S, len(tokens)
+        sampled = _is_sampled(params)
+        self.ctr0 = 1 if sampled else 0                # (a sampled stream drew its first token at step 0: sample_token)
+        V = self.m.config.vocab_size
         st["pos"].copy_(col(positions, torch.int32), non_blocking=True)
         st["ids"].copy_(col(tokens, torch.int64), non_blocking=True)
-        st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
-        if self.nsplit_trunk:
-            st["leader"].copy_(col([-1 if l is None else idx[l] for l, _ in self.trunks], torch.int32, -1), non_blocking=True)
-            st["trunk"].copy_(col([T for _, T in self.trunks], torch.int32), non_blocking=True)
-        st["budget"].copy_(col([max_new] * n, torch.int32), non_blocking=True)
         st["ctr"].fill_(self.ctr0)
         st["stop"].copy_(torch.tensor(list(stop_ids) + [-1] * (8 - len(stop_ids)), dtype=torch.int32), non_blocking=True)
         seeds = [0] * n if seeds is None else list(seeds)
         st["seeds"].copy_(col([sd & (2 ** 63 - 1) for sd in seeds], torch.int64), non_blocking=True)
-        if self.sampled:
+        if sampled:
             blk = sample_params_block(params, 0)
-            hist = torch.zeros((S, hw), dtype=torch.int32)
-            for k, h in zip(idx, histories):
-                hist[k] = _history_bits(h, V)
+            hist = torch.zeros((S, (V + 31) // 32), dtype=torch.int32)
+            for s, h in zip(self.idx, histories):
+                hist[s] = _history_bits(h, V)
             st["hist"].copy_(hist, non_blocking=True)
         else:
             blk = _native.sample_params_bytes(0.0, 1.0, 1.0, -1, 0)        # greedy: the argmax of the raw row
         st["params"].copy_(torch.frombuffer(bytearray(blk), dtype=torch.uint8))
-        self.stop_ids = set(int(t) for t in stop_ids)
-        self.logits = st["logits"]
-        self.n = 0
-        self.events = {}                  # step -> (start, end, tokens on the host); steps the ring no longer holds are dropped
-        self.host = torch.empty((self.RING, S), dtype=torch.int32, pin_memory=True)
-        self._ring2d = st["ring"].view(S, self.RING)
-        self._alive = [True] * n          # host mirror of the live words, after the newest step whose tokens were looked at
-        self._seen = 0                    # steps whose tokens the mirror has taken in
-        self._last = [-1] * n             # index of the last step that produced a token for sequence k (-1: none yet)
-        self._killed = [None] * n         # step count at which kill(k) took effect
-        self._start = [0] * n             # the replay at which sequence k entered the loop
-        self._max_new = [max_new] * n
-        self._stops = [self.stop_ids] * n
-        self._active = list(range(n))     # sequences the mirror still follows
-        self._retired = set()
-        torch.cuda.current_stream().synchronize()        # (the pageable sources of the copies above may go now)
 
     # ---- per-slot sampling state and admission (each=True) ---------------------------------------------------------------
-    def _init_each(self, model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, S, idx, trunks, max_keys):
-        """The loop over ``pc_sample_advance_slots_each``: every initial sequence enters through ``admit``'s path, at replay 0.
-        ``max_new`` / ``params`` / ``stop_ids``: one value for all sequences or a list with one per sequence."""
-        n = len(arenas)
-        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
-        max_news, paramss = per(max_new), per(params)
-        stops = list(stop_ids) if len(stop_ids) and isinstance(stop_ids[0], (list, tuple)) else [tuple(stop_ids)] * n
-        assert len(tokens) == n and len(positions) == n and len(max_news) == n and len(paramss) == n and len(stops) == n
-        self.m, self.S, self.idx, self.max_new = model, S, [], max(max_news)
-        self.arenas, self.len0, self.trunks = [], [], []
-        trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
-        shared = any(l is not None for l, _ in trunks)
-        for k, (l, T) in enumerate(trunks):
-            assert l is None or (trunks[l] == (l, T) and 0 < T <= arenas[k].length and T <= arenas[l].length), (k, trunks)
-        if max_keys is None:
-            max_keys = max(a.length + mn for a, mn in zip(arenas, max_news)) + 1
-        self.nsplit = model._slot_nsplit(S, int(max_keys))
-        self.nsplit_trunk = model._slot_nsplit(1, int(max_keys)) if shared else 0
-        st = self.st = model._slot_state(S)
-        model._live_loop = self
-        self.sampled, self.ctr0 = True, 0      # (ring-only counters; every stream drew its first token at step 0: draws start at 1)
-        self.stop_ids = set()
-        st["live"].zero_()
-        st["leader"].fill_(-1)
-        st["trunk"].zero_()
-        self.logits = st["logits"]
-        self.n = 0
-        self.events = {}
-        self.host = torch.empty((self.RING, S), dtype=torch.int32, pin_memory=True)
-        self._ring2d = st["ring"].view(S, self.RING)
-        self._alive, self._last, self._killed, self._start, self._max_new, self._stops = [], [], [], [], [], []
-        self._seen, self._active = 0, []
-        self._slot_seq = [None] * S            # the newest sequence of every slot
-        self._retired = set()
-        hw = (model.config.vocab_size + 31) // 32
-        self._arm_bytes = _native.slot_arm_bytes(hw)
-        self._arm_ring = [[torch.zeros(self._arm_bytes, dtype=torch.uint8, pin_memory=True), torch.cuda.Event(), False] for _ in range(4)]
-        self._arm_next = 0
-        self._arm_state = _native.slot_state(st["kv_base"], st["cap"], st["len"], st["pos"], st["ids"], st["live"], st["leader"],
-                                             st["trunk"], st["budget"], st["ctr"], st["draws"], st["seeds"], st["params_each"],
-                                             st["stop_each"], st["hist"])
-        seeds = [0] * n if seeds is None else list(seeds)
-        histories = [()] * n if histories is None else list(histories)
-        for k in range(n):
-            l, T = trunks[k]
-            self._admit(idx[k], arenas[k], tokens[k], positions[k], max_news[k], paramss[k], seeds[k], histories[k], stops[k],
-                        None if l is None else (idx[l], T))
+    def _arm_setup(self, hw: int):
+        """(every stream drew its first token at step 0: draws start at 1, and the counters index the ring only)"""
+        st = self.st
+        return _native.slot_arm_bytes(hw), _native.slot_state(
+            st["kv_base"], st["cap"], st["len"], st["pos"], st["ids"], st["live"], st["leader"], st["trunk"], st["budget"], st["ctr"],
+            st["draws"], st["seeds"], st["params_each"], st["stop_each"], st["hist"])
 
     @torch.inference_mode()
     def admit(self, slot_index: int, past, token: int, position: int, max_new: int, params, seed: int, history, stop_ids,
@@ -579,19 +752,9 @@ class SlotLoop:
         stream ``seed`` (continuing at step 1), ``history`` ids and up to 8 ``stop_ids``.  ``trunk = (leader slot, T)``: rows [0, T) are
         read from the arena of that slot.  Only legal when the slot's previous sequence is over on the host mirror (stopped, out of
         budget or killed) and was retired.  -> the new sequence's index."""
-        if not self.each:
-            raise RuntimeError("SlotLoop.admit needs a loop built with each=True")
-        a = self.m._loop_arena(past)
-        if a is None:
-            raise RuntimeError("SlotLoop.admit: the cache is not a staged batch-1 arena")
-        return self._admit(int(slot_index), a, token, position, max_new, params, seed, history, stop_ids, trunk)
+        return self._admit(int(slot_index), self._admit_arena(past), token, position, max_new, params, seed, history, stop_ids, trunk)
 
-    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, trunk) -> int:
-        m, st = self.m, self.st
-        if getattr(m, "_live_loop", None) is not self:
-            raise RuntimeError("SlotLoop: another device loop on this model took over")
-        if not 0 <= s < self.S or max_new < 1:
-            raise ValueError(f"SlotLoop.admit: slot {s} outside [0, {self.S}) or max_new < 1")
+    def _admit_check(self, s: int, corpus, token, max_new: int):
         prev = self._slot_seq[s]
         if prev is not None:
             if self._alive[prev] and self._killed[prev] is None:
@@ -599,94 +762,20 @@ class SlotLoop:
             self._alive[prev] = False
             if prev in self._active:
                 self._active.remove(prev)
-        if any(a is self.arenas[k] for k in self._active):
-            raise RuntimeError("SlotLoop.admit: the arena belongs to a running sequence")
-        a.materialize()
-        need = a.length + max_new + 2
-        if need > a.cap:
-            a = a.grown(max(need, 2 * a.cap))
-        m._tail_done(a, 0, 1, a.length)
-        leader, T = (-1, 0) if trunk is None else (int(trunk[0]), int(trunk[1]))
-        if leader >= 0:
-            lead = self._slot_seq[leader] if leader != s else None
-            la = a if leader == s else (None if lead is None else self.arenas[lead])
-            if not self.nsplit_trunk or la is None or not 0 < T <= a.length or T > la.cap:
-                raise ValueError(f"SlotLoop.admit: no trunk of {T} rows led by slot {leader} in this loop")
-            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1" and la is not a and \
-                    not torch.equal(a.buf[:, :, :, :, :T], la.buf[:, :, :, :, :T]):
-                raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of the sequence for slot {s} differ from its trunk leader's "
-                                   f"(slot {leader})")
-        stop_ids = [int(t) for t in stop_ids]
-        assert len(stop_ids) <= 8, "at most 8 stop ids live on the device (the host kills for the rest)"
-        sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
-        blk_p = sample_params_block(params, 0) if sampled else _native.sample_params_bytes(0.0, 1.0, 1.0, -1, 0)
-        V = m.config.vocab_size
-        hw = (V + 31) // 32
-        # the next pinned block of the ring, once the launch that read it last has finished
-        ent = self._arm_ring[self._arm_next]
-        self._arm_next = (self._arm_next + 1) % len(self._arm_ring)
-        if ent[2]:
-            ent[1].synchronize()
-        arr = ent[0].numpy()
-        b = _native.SlotArmBlock.from_buffer(arr)
-        b.slot, b.cap, b.kv_base, b.len, b.pos, b.id = s, a.cap, a.buf.data_ptr(), a.length, int(position), int(token)
-        b.leader, b.trunk, b.budget, b.counter, b.draws, b.hist_words = leader, T, int(max_new), self.ctr0 + self.n, 1, hw
-        b.seed = int(seed) & (2 ** 63 - 1)
-        b.params = _native.SampleParams.from_buffer_copy(blk_p)
-        for j in range(8):
-            b.stop_ids[j] = stop_ids[j] if j < len(stop_ids) else -1
-        hb = arr[ctypes.sizeof(_native.SlotArmBlock):ctypes.sizeof(_native.SlotArmBlock) + 4 * hw].view(np.int32)
-        if sampled:
-            hb[:] = _history_bits(history, V).numpy()
-        else:
-            hb[:] = 0
-        del b
-        _native.slot_arm(ent[0], self._arm_bytes, self._arm_state, self.S)
-        ent[1].record()
-        ent[2] = True
-        k = len(self.arenas)
-        self.arenas.append(a)
-        self.len0.append(a.length)
-        self.idx.append(s)
-        self.trunks.append((None, 0) if leader < 0 else (leader, T))
+        return self._active, {"draws": 1}, None
+
+    def _arm(self, block, arr, off: int, hist) -> None:
+        _native.slot_arm(block, off, self._arm_state, self.S)
+
+    def _entered(self, k: int, prev, max_new: int, stop_ids) -> None:
         self._alive.append(True)
         self._last.append(-1)
-        self._killed.append(None)
-        self._start.append(self.n)
         self._max_new.append(int(max_new))
-        self._stops.append(set(stop_ids))
+        self._stops.append(set(int(t) for t in stop_ids))
         self._active.append(k)
-        self._slot_seq[s] = k
-        return k
 
-    def retire(self, k: int, consumed: int) -> None:
-        """Sequence ``k`` is over and its consumer used ``consumed`` of its steps: its arena's ``length`` goes to exactly that
-        (``close``'s rule, for one sequence) -- before the buffer is staged again for the slot's next sequence."""
-        self.arenas[k].length = self.len0[k] + int(consumed)
-        self._retired.add(k)
-
-    @torch.inference_mode()
-    def enqueue(self) -> int:
-        m, st = self.m, self.st
-        if getattr(m, "_live_loop", None) is not self:
-            raise RuntimeError("SlotLoop: another device loop on this model took over (one device-side generation per model "
-                               "at a time)")
-        g = m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        i = self.n
-        r = (self.ctr0 + i) % self.RING
-        if i >= self.RING:
-            self._advance_mirror(i - self.RING)          # (row r still holds step i - RING: the mirror takes it in first)
-        self.host[r].copy_(self._ring2d[:, r], non_blocking=True)
-        done = torch.cuda.Event()
-        done.record()
-        self.events[i] = (e0, e1, done)
-        self.events.pop(i - self.RING, None)             # nobody can ask for a step whose ring row is being reused
-        self.n += 1
-        return i
+    def _ring_row_reused(self, step: int) -> None:
+        self._advance_mirror(step)                       # (the mirror takes the row's step in first)
 
     def _advance_mirror(self, upto: int) -> None:
         """Take the tokens of steps [seen, upto] into the host mirror of the live words (the rule of pc_sample_advance_slots)."""
@@ -716,32 +805,8 @@ class SlotLoop:
             return None
         return int(self.host[(self.ctr0 + i) % self.RING][self.idx[k]])
 
-    def kill(self, k: int) -> None:
-        """Switch sequence ``k`` off from the next replay on (ordered behind the replays already enqueued)."""
-        s = self.idx[k]
-        self.st["live"][s: s + 1].fill_(0)
-        if self._killed[k] is None:
-            self._killed[k] = self.n
 
-    def elapsed_ms(self, i: int) -> float:
-        e0, e1, done = self.events[i]
-        done.synchronize()
-        return e0.elapsed_time(e1)
-
-    def close(self, consumed) -> None:
-        """``consumed[k]``: how many of the loop's steps sequence k's consumer used.  Each arena's ``length`` goes to exactly that
-        (rows a look-ahead replay wrote past it are dead), and the loop state is released."""
-        if isinstance(consumed, dict):                   # an each=True loop: the sequences that were not retired one by one
-            for k, c in consumed.items():
-                self.arenas[k].length = self.len0[k] + int(c)
-        else:
-            for a, l0, c in zip(self.arenas, self.len0, consumed):
-                a.length = l0 + int(c)
-        if getattr(self.m, "_live_loop", None) is self:
-            self.m._live_loop = None
-
-
-class LookupSlotLoop:
+class LookupSlotLoop(_SlotLoopHost):
     """Batched decode with prompt-lookup drafts: ``SlotLoop``'s slots x ``LookupLoop``'s ``k + 1`` rows.
 
     Every replay of the ONE captured step runs ``pc_lookup_draft_slots`` -> the layer stack over ``R = S * (k + 1)`` rows (row
@@ -757,147 +822,79 @@ class LookupSlotLoop:
     reads a group's shared rows from the leader's arena, once for all draft rows of all members
     (``pc_attn_verify_slots_trunk``); ``nsplit_trunk`` > 0 says so."""
 
-    RING = 1024
-    MAX_ROWS = 64
+    _arm_header = _native.LookupSlotArmBlock
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
                  slots: Optional[int] = None, max_keys: Optional[int] = None, trunks=None, each: bool = False, slot_index=None,
                  params=None, seeds=None, histories=None, hist_cap: Optional[int] = None):
-        n = len(arenas)
-        self.each = bool(each)
-        if each:
-            self._init_each(model, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, slots, max_keys, trunks, slot_index,
-                            params, seeds, histories, hist_cap)
-            return
-        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= n)
-        assert 1 <= n <= S <= SlotLoop.MAX_SLOTS and 1 <= k <= 15 and S * (k + 1) <= self.MAX_ROWS, (n, S, k)
-        assert len(tokens) == n and len(positions) == n and len(corpora) == n and len(stop_ids) <= 8 and max_new >= 1
-        self.m, self.S, self.k, self.nmax, self.max_new = model, S, int(k), int(nmax), int(max_new)
-        grown = []
-        for a in arenas:                              # no address may move under the captured step
-            need = a.length + max_new + k + 2
-            grown.append(a.grown(max(need, 2 * a.cap)) if need > a.cap else a)
-            model._tail_done(grown[-1], 0, 1, a.length)
-        self.arenas = grown
-        self.len0 = [a.length for a in grown]
-        # shared trunks, as in SlotLoop: per sequence (leader index | None, T), checked on the arenas the loop uses
-        self.trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
+        assert 1 <= k <= 15, k
+        self.k, self.nmax = int(k), int(nmax)
+        self._record = (self.k + 2,)      # a step leaves {count, tokens...} per slot: ``host`` is [RING][S][k + 2]
+        self._end = []                    # the replay at which the slot's next sequence entered (None: none has)
+        self._build(model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each,
+                    max_keys, corpora, hist_cap)
+
+    def _split_counts(self, lens, max_news, trunks, max_keys) -> None:
+        """From ``max_keys`` (kept): the caller's bound of all keys of a sequence, or this batch's, rounded up to 64 -- in a loop
+        with shared trunks and no bound from the caller, of a sequence's OWN keys behind its trunk (the trunk has a split count
+        of its own)."""
+        m, k = self.m, self.k
+        shared = any(l is not None for l, _ in trunks)
         self.nsplit_trunk = 0
-        shared = any(l is not None for l, _ in self.trunks)
-        if shared:
-            for j, (l, T) in enumerate(self.trunks):
-                assert l is None or (self.trunks[l] == (l, T) and 0 < T <= self.len0[j] and T <= self.len0[l]), (j, self.trunks)
-            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1":
-                for j, (l, T) in enumerate(self.trunks):
-                    if l is not None and l != j and not torch.equal(grown[j].buf[:, :, :, :, :T], grown[l].buf[:, :, :, :, :T]):
-                        raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of sequence {j} differ from its trunk leader's "
-                                           f"(sequence {l})")
-        # max_keys: the bound the split counts are taken from -- of all keys of a sequence, or, in a loop with shared trunks
-        # and no bound from the caller, of a sequence's OWN keys behind its trunk (the trunk has a split count of its own)
-        if max_keys is not None:                          # split counts from the caller's bound, not from this batch
+        if max_keys is None and self.each:
+            max_keys = (max(l0 + mn for l0, mn in zip(lens, max_news)) + k + 1 + 63) // 64 * 64
+        if max_keys is not None:
             self.max_keys = int(max_keys)
             if shared:
-                self.nsplit_trunk = model._slot_nsplit(1, self.max_keys)
+                self.nsplit_trunk = m._slot_nsplit(1, self.max_keys)
         elif shared:
-            self.nsplit_trunk = model._slot_nsplit(len({l for l, _ in self.trunks if l is not None}), max(T for _, T in self.trunks))
-            self.max_keys = (max(l0 - T for l0, (_, T) in zip(self.len0, self.trunks)) + max_new + k + 1 + 63) // 64 * 64
+            self.nsplit_trunk = m._slot_nsplit(len({l for l, _ in trunks if l is not None}), max(T for _, T in trunks))
+            self.max_keys = (max(l0 - T for l0, (_, T) in zip(lens, trunks)) + max_news[0] + k + 1 + 63) // 64 * 64
         else:
-            self.max_keys = (max(self.len0) + max_new + k + 1 + 63) // 64 * 64
-        self.nsplit = model._slot_nsplit(S, self.max_keys)
-        hists = [[int(t) for t in c] + [int(tok)] for c, tok in zip(corpora, tokens)]
-        st = self.st = model._lookup_slot_state(S, k, max(map(len, hists)) + max_new)
-        model._live_loop = self
-        R1 = k + 1
+            self.max_keys = (max(lens) + max_news[0] + k + 1 + 63) // 64 * 64
+        self.nsplit = m._slot_nsplit(self.S, self.max_keys)
 
-        def col(vals, dtype, fill=0):
-            t = torch.full((S,), fill, dtype=dtype)
-            t[:n] = torch.tensor(list(vals), dtype=dtype)
-            return t
-        st["kv_base"].copy_(col([a.buf.data_ptr() for a in grown], torch.int64), non_blocking=True)
-        st["cap"].copy_(col([a.cap for a in grown], torch.int32), non_blocking=True)
-        st["len"].copy_(col(self.len0, torch.int32), non_blocking=True)
-        st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
-        st["leader"].copy_(col([-1 if l is None else l for l, _ in self.trunks], torch.int32, -1), non_blocking=True)
-        st["trunk"].copy_(col([T for _, T in self.trunks], torch.int32), non_blocking=True)
-        st["budget"].copy_(col([max_new] * n, torch.int32), non_blocking=True)
-        st["hist_len"].copy_(col(map(len, hists), torch.int32), non_blocking=True)
+    def _make_state(self, tokens, corpora, hist_cap) -> dict:
+        """``each``: ``hist_cap`` ids of draft history per slot (default 8192), fixed here: the captured step holds the buffer."""
+        m, S, k = self.m, self.S, self.k
+        if self.each:
+            st = m._lookup_slot_state(S, k, 8192 if hist_cap is None else int(hist_cap), each=True)
+            self.hist_cap = st["hist"].shape[1]
+        else:
+            self._hists = [[int(t) for t in c] + [int(tok)] for c, tok in zip(corpora, tokens)]
+            st = m._lookup_slot_state(S, k, max(map(len, self._hists)) + self.max_new)
         st["ndraft"].zero_()
         st["ctr"].zero_()
-        ids = torch.zeros((S, R1), dtype=torch.int64)
-        pos = torch.zeros((S, R1), dtype=torch.int32)
+        return st
+
+    def _graph(self):
+        self.m._lo_mode = 0                # appended rows carry no residual planes, as in default decode
+        return self.m._lookup_slot_graph(self)
+
+    def _fill_state(self, col, tokens, positions, max_new, params, seeds, histories, stop_ids) -> None:
+        """The state words of the loop over ``pc_lookup_verify_slots``: greedy, one stop list for all slots."""
+        st, S, hists = self.st, self.S, self.__dict__.pop("_hists")
+        st["hist_len"].copy_(col(map(len, hists), torch.int32), non_blocking=True)
+        ids = torch.zeros((S, self.k + 1), dtype=torch.int64)
+        pos = torch.zeros((S, self.k + 1), dtype=torch.int32)
         hist = torch.zeros((S, max(map(len, hists))), dtype=torch.int32)
-        for j, h in enumerate(hists):
-            ids[j], pos[j] = int(tokens[j]), int(positions[j])
-            hist[j, :len(h)] = torch.tensor(h, dtype=torch.int32)
+        for s, h, tok, p in zip(self.idx, hists, tokens, positions):
+            ids[s], pos[s] = int(tok), int(p)
+            hist[s, :len(h)] = torch.tensor(h, dtype=torch.int32)
         st["ids"].copy_(ids, non_blocking=True)
         st["pos"].copy_(pos, non_blocking=True)
         st["hist"][:, :hist.shape[1]].copy_(hist, non_blocking=True)
         stop = torch.full((S, 8), -1, dtype=torch.int32)
         stop[:, :len(stop_ids)] = torch.tensor([int(t) for t in stop_ids], dtype=torch.int32)
         st["stop"].copy_(stop, non_blocking=True)
-        self.logits = st["logits"]
-        self.n = 0
-        self.events = {}
-        self.host = torch.zeros((self.RING, S, k + 2), dtype=torch.int32, pin_memory=True)
-        self._ring3d = st["ring"].view(S, self.RING, k + 2)
-        torch.cuda.current_stream().synchronize()        # (the pageable sources of the copies above may go now)
 
     # ---- per-slot sampling state and admission (each=True, DESIGN 3.22) ---------------------------------------------------
-    def _init_each(self, model, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, slots, max_keys, trunks, slot_index,
-                   params, seeds, histories, hist_cap):
-        """The loop over ``pc_lookup_verify_slots_each``: every initial sequence enters through ``admit``'s path, at replay 0.
-        ``max_new`` / ``params`` / ``stop_ids``: one value for all sequences or a list with one per sequence.  ``hist_cap``: the
-        ids a slot's draft history holds (fixed here: the captured step holds the buffer), default 8192."""
-        n = len(arenas)
-        idx = list(range(n)) if slot_index is None else [int(i) for i in slot_index]
-        S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= max(idx) + 1)
-        assert 1 <= n and len(set(idx)) == n and 0 <= min(idx) and max(idx) < S <= SlotLoop.MAX_SLOTS, (n, idx, S)
-        assert 1 <= k <= 15 and S * (k + 1) <= self.MAX_ROWS, (S, k)
-        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
-        max_news, paramss = per(max_new), per(params)
-        stops = list(stop_ids) if len(stop_ids) and isinstance(stop_ids[0], (list, tuple)) else [tuple(stop_ids)] * n
-        assert len(tokens) == n and len(positions) == n and len(corpora) == n and len(max_news) == n and len(paramss) == n and len(stops) == n
-        self.m, self.S, self.k, self.nmax, self.max_new = model, S, int(k), int(nmax), max(max_news)
-        self.idx, self.arenas, self.len0, self.trunks = [], [], [], []
-        trunks = [(None, 0)] * n if trunks is None else [(None, 0) if l is None else (int(l), int(T)) for l, T in trunks]
-        shared = any(l is not None for l, _ in trunks)
-        for j, (l, T) in enumerate(trunks):
-            assert l is None or (trunks[l] == (l, T) and 0 < T <= arenas[j].length and T <= arenas[l].length), (j, trunks)
-        if max_keys is None:
-            max_keys = (max(a.length + mn for a, mn in zip(arenas, max_news)) + k + 1 + 63) // 64 * 64
-        self.max_keys = int(max_keys)
-        self.nsplit = model._slot_nsplit(S, self.max_keys)
-        self.nsplit_trunk = model._slot_nsplit(1, self.max_keys) if shared else 0
-        st = self.st = model._lookup_slot_state(S, k, 8192 if hist_cap is None else int(hist_cap), each=True)
-        self.hist_cap = st["hist"].shape[1]
-        model._live_loop = self
-        st["live"].zero_()
-        st["leader"].fill_(-1)
-        st["trunk"].zero_()
-        st["ndraft"].zero_()
-        st["ctr"].zero_()
-        self.logits = st["logits"]
-        self.n = 0
-        self.events = {}
-        self.host = torch.zeros((self.RING, S, k + 2), dtype=torch.int32, pin_memory=True)
-        self._ring3d = st["ring"].view(S, self.RING, k + 2)
-        self._start, self._end, self._killed = [], [], []
-        self._slot_seq = [None] * S            # the newest sequence of every slot
-        self._retired = set()
-        hw = (model.config.vocab_size + 31) // 32
-        self._arm_cap = _native.lookup_slot_arm_bytes(hw, self.hist_cap)
-        self._arm_ring = [[torch.zeros(self._arm_cap, dtype=torch.uint8, pin_memory=True), torch.cuda.Event(), False] for _ in range(4)]
-        self._arm_next = 0
-        self._arm_state = _native.lookup_slot_state(st["kv_base"], st["cap"], st["len"], st["live"], st["leader"], st["trunk"], st["ids"],
-                                                    st["pos"], st["ndraft"], st["budget"], st["hist_len"], st["ctr"], st["draws"],
-                                                    st["seeds"], st["params_each"], st["stop"], st["bits"], st["hist"])
-        seeds = [0] * n if seeds is None else list(seeds)
-        histories = [()] * n if histories is None else list(histories)
-        for j in range(n):
-            l, T = trunks[j]
-            self._admit(idx[j], arenas[j], tokens[j], positions[j], max_news[j], paramss[j], seeds[j], histories[j], stops[j],
-                        corpora[j], None if l is None else (idx[l], T))
+    def _arm_setup(self, hw: int):
+        st = self.st
+        return _native.lookup_slot_arm_bytes(hw, self.hist_cap), _native.lookup_slot_state(
+            st["kv_base"], st["cap"], st["len"], st["live"], st["leader"], st["trunk"], st["ids"], st["pos"], st["ndraft"], st["budget"],
+            st["hist_len"], st["ctr"], st["draws"], st["seeds"], st["params_each"], st["stop"], st["bits"], st["hist"])
 
     @torch.inference_mode()
     def admit(self, slot_index: int, past, token: int, position: int, max_new: int, params, seed: int, history, stop_ids, corpus,
@@ -908,155 +905,44 @@ class LookupSlotLoop:
         ``stop_ids`` and the ``corpus`` its drafts may copy from (``lookup_admit_history``: the oldest ids go where the history
         buffer is too small).  ``trunk = (leader slot, T)``.  Only legal when the slot's previous sequence was retired.
         -> the new sequence's index."""
-        if not self.each:
-            raise RuntimeError("LookupSlotLoop.admit needs a loop built with each=True")
-        a = self.m._loop_arena(past)
-        if a is None:
-            raise RuntimeError("LookupSlotLoop.admit: the cache is not a staged batch-1 arena")
-        a.materialize()
-        return self._admit(int(slot_index), a, token, position, max_new, params, seed, history, stop_ids, corpus, trunk)
+        return self._admit(int(slot_index), self._admit_arena(past), token, position, max_new, params, seed, history, stop_ids, trunk,
+                           corpus)
 
-    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, corpus, trunk) -> int:
-        m, k = self.m, self.k
-        if getattr(m, "_live_loop", None) is not self:
-            raise RuntimeError("LookupSlotLoop: another device loop on this model took over")
-        if not 0 <= s < self.S or max_new < 1:
-            raise ValueError(f"LookupSlotLoop.admit: slot {s} outside [0, {self.S}) or max_new < 1")
-        hist = lookup_admit_history(corpus, token, int(max_new), self.hist_cap)
+    def _admit_check(self, s: int, corpus, token, max_new: int):
+        hist = lookup_admit_history(corpus, token, max_new, self.hist_cap)
         prev = self._slot_seq[s]
         if prev is not None and prev not in self._retired:
             raise RuntimeError(f"LookupSlotLoop.admit: the sequence in slot {s} was not retired")
-        running = [j for j in self._slot_seq if j is not None and j not in self._retired]
-        if any(a is self.arenas[j] for j in running):
-            raise RuntimeError("LookupSlotLoop.admit: the arena belongs to a running sequence")
-        need = a.length + max_new + k + 2
-        if need > a.cap:
-            a = a.grown(max(need, 2 * a.cap))
-        m._tail_done(a, 0, 1, a.length)
-        leader, T = (-1, 0) if trunk is None else (int(trunk[0]), int(trunk[1]))
-        if leader >= 0:
-            lead = self._slot_seq[leader] if leader != s else None
-            la = a if leader == s else (None if lead is None else self.arenas[lead])
-            if not self.nsplit_trunk or la is None or not 0 < T <= a.length or T > la.cap:
-                raise ValueError(f"LookupSlotLoop.admit: no trunk of {T} rows led by slot {leader} in this loop")
-            if os.environ.get("PC_TRUNK_VERIFY", "0") == "1" and la is not a and \
-                    not torch.equal(a.buf[:, :, :, :, :T], la.buf[:, :, :, :, :T]):
-                raise RuntimeError(f"PC_TRUNK_VERIFY: rows [0, {T}) of the sequence for slot {s} differ from its trunk leader's "
-                                   f"(slot {leader})")
-        stop_ids = [int(t) for t in stop_ids]
-        assert len(stop_ids) <= 8, "at most 8 stop ids live on the device (the host kills for the rest)"
-        sampled = params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
-        blk_p = sample_params_block(params, 0) if sampled else _native.sample_params_bytes(0.0, 1.0, 1.0, -1, 0)
-        V = m.config.vocab_size
-        hw = (V + 31) // 32
-        # the next pinned block of the ring, once the launch that read it last has finished (SlotLoop._admit's rule)
-        ent = self._arm_ring[self._arm_next]
-        self._arm_next = (self._arm_next + 1) % len(self._arm_ring)
-        if ent[2]:
-            ent[1].synchronize()
-        arr = ent[0].numpy()
-        b = _native.LookupSlotArmBlock.from_buffer(arr)
-        b.slot, b.cap, b.kv_base, b.len, b.pos, b.id = s, a.cap, a.buf.data_ptr(), a.length, int(position), int(token)
-        b.leader, b.trunk, b.budget, b.counter, b.hist_words, b.hist_len = leader, T, int(max_new), self.n, hw, len(hist)
-        b.seed = int(seed) & (2 ** 63 - 1)
-        b.params = _native.SampleParams.from_buffer_copy(blk_p)
-        for j in range(8):
-            b.stop_ids[j] = stop_ids[j] if j < len(stop_ids) else -1
-        del b
-        n0 = ctypes.sizeof(_native.LookupSlotArmBlock)
-        hb = arr[n0:n0 + 4 * hw].view(np.int32)
-        if sampled:
-            hb[:] = _history_bits(history, V).numpy()
-        else:
-            hb[:] = 0
-        n1 = n0 + ((4 * hw + 7) & ~7)
-        arr[n1:n1 + 4 * len(hist)].view(np.int32)[:] = np.asarray(hist, dtype=np.int32)
-        _native.lookup_slot_arm(ent[0], _native.lookup_slot_arm_bytes(hw, len(hist)), self._arm_state, self.S, k, self.hist_cap)
-        ent[1].record()
-        ent[2] = True
+        return [j for j in self._slot_seq if j is not None and j not in self._retired], {"hist_len": len(hist)}, hist
+
+    def _arm(self, block, arr, off: int, hist) -> None:
+        """(the history ids behind the bitmap; the launch reads the bytes of THIS admission only)"""
+        arr[off:off + 4 * len(hist)].view(np.int32)[:] = np.asarray(hist, dtype=np.int32)
+        _native.lookup_slot_arm(block, off + ((4 * len(hist) + 7) & ~7), self._arm_state, self.S, self.k, self.hist_cap)
+
+    def _entered(self, j: int, prev, max_new: int, stop_ids) -> None:
         if prev is not None:
             self._end[prev] = self.n
-        j = len(self.arenas)
-        self.arenas.append(a)
-        self.len0.append(a.length)
-        self.idx.append(s)
-        self.trunks.append((None, 0) if leader < 0 else (leader, T))
-        self._start.append(self.n)
         self._end.append(None)
-        self._killed.append(None)
-        self._slot_seq[s] = j
-        return j
 
-    def retire(self, j: int, consumed_tokens: int) -> None:
-        """Sequence ``j`` is over and its consumer used ``consumed_tokens`` of its tokens: its arena's ``length`` goes to exactly that
-        (``close``'s rule, for one sequence) -- before the buffer is staged again for the slot's next sequence."""
-        a = self.arenas[j]
-        a.length = self.len0[j] + int(consumed_tokens)
+    def _set_length(self, a, length: int) -> None:
+        a.length = length
         a.tail_base, a.tail_len = -1, 0
-        self._retired.add(j)
-
-    @torch.inference_mode()
-    def enqueue(self) -> int:
-        m = self.m
-        if getattr(m, "_live_loop", None) is not self:
-            raise RuntimeError("LookupSlotLoop: another device loop on this model took over (one device-side generation per model "
-                               "at a time)")
-        m._lo_mode = 0                     # appended rows carry no residual planes, as in default decode
-        g = m._lookup_slot_graph(self)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        i = self.n
-        r = i % self.RING
-        self.host[r].copy_(self._ring3d[:, r], non_blocking=True)
-        done = torch.cuda.Event()
-        done.record()
-        self.events[i] = (e0, e1, done)
-        self.events.pop(i - self.RING, None)
-        self.n += 1
-        return i
 
     def tokens(self, j: int, i: int):
-        """The tokens sequence ``j`` emitted at step ``i`` (empty: the sequence was over, or had no budget left).  ``each=True``:
-        ``i`` is the global replay index -- empty before the sequence's start and from the replay its slot's next sequence entered."""
-        if self.each:
-            if i < self._start[j] or (self._end[j] is not None and i >= self._end[j]):
-                return []
-            j = self.idx[j]
+        """The tokens sequence ``j`` emitted at step ``i`` (empty: the sequence was over, or had no budget left).  ``i`` is the global
+        replay index -- empty before the sequence's start and from the replay its slot's next sequence entered (``each=True``)."""
+        if i < self._start[j] or (self._end[j] is not None and i >= self._end[j]):
+            return []
         self.events[i][2].synchronize()
-        rec = self.host[i % self.RING][j]
+        rec = self.host[i % self.RING][self.idx[j]]
         c = int(rec[0])
         return [int(t) for t in rec[1:1 + c]]
 
     def kill(self, j: int) -> None:
-        """Switch sequence ``j`` off from the next replay on (ordered behind the replays already enqueued)."""
-        if self.each:
-            if self._end[j] is not None:                  # (the slot holds a later sequence)
-                return
-            if self._killed[j] is None:
-                self._killed[j] = self.n
-            j = self.idx[j]
-        self.st["live"][j: j + 1].fill_(0)
-
-    def elapsed_ms(self, i: int) -> float:
-        e0, e1, done = self.events[i]
-        done.synchronize()
-        return e0.elapsed_time(e1)
-
-    def close(self, consumed) -> None:
-        """``consumed[j]``: how many of its TOKENS sequence j's consumer used.  Each arena's ``length`` goes to exactly that (rows
-        behind it -- rejected drafts, look-ahead replays -- are rewritten before anything reads them); the loop state is released.
-        ``each=True``: a dict over the sequences that were not retired one by one."""
-        if isinstance(consumed, dict):
-            consumed = [consumed.get(j) for j in range(len(self.arenas))]
-        for a, l0, c in zip(self.arenas, self.len0, consumed):
-            if c is None:
-                continue
-            a.length = l0 + int(c)
-            a.tail_base, a.tail_len = -1, 0
-        if getattr(self.m, "_live_loop", None) is self:
-            self.m._live_loop = None
+        """``SlotLoop.kill``; nothing once the slot holds a later sequence."""
+        if self._end[j] is None:
+            super().kill(j)
 
 
 class LlamaHIP:
@@ -2413,6 +2299,17 @@ class LlamaHIP:
         ``max_keys``: the upper bound of keys the split counts of the attention are taken from (default: from this batch).  A
         serving loop passes the capacity of the slot buffers, once: a sequence's bits must not depend on who joins later, and the
         attention's summation order depends on the split counts."""
+        front = self._slot_loop_front(pasts, stop_ids, each, share_trunk, min_trunk, trunks)
+        if front is None:
+            return None
+        arenas, trunks = front
+        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks,
+                        each, max_keys)
+
+    def _slot_loop_front(self, pasts, stop_ids, each: bool, share_trunk: bool, min_trunk, trunks):
+        """What ``slot_loop`` and ``lookup_slot_loop`` do before they build their loop -> (arenas, trunks), or None where there is
+        no batched loop: the model has none, more than 16 sequences, more than 8 stop ids (of one sequence, with ``each``), a
+        cache that is no batch-1 arena of its own."""
         per_seq_stops = each and len(stop_ids) and isinstance(stop_ids[0], (list, tuple))
         if not self.slot_loop_available() or not 1 <= len(pasts) <= SlotLoop.MAX_SLOTS or \
                 (max(map(len, stop_ids)) if per_seq_stops else len(stop_ids)) > 8:
@@ -2426,8 +2323,7 @@ class LlamaHIP:
             arenas.append(a)
         if trunks is None and share_trunk:
             trunks = common_trunks([a.layout for a in arenas], min_trunk)
-        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks,
-                        each, max_keys)
+        return arenas, trunks
 
     def _slot_nsplit(self, S: int, max_keys: int) -> int:
         """Splits of the key axis of pc_attn_decode_slots: enough workgroups to cover the chip at S slots, at least 256 keys
@@ -2555,22 +2451,15 @@ class LlamaHIP:
         sequence j sits in slot ``slot_index[j]`` and ``LookupSlotLoop.admit`` puts new sequences into slots whose sequence was
         retired.  ``hist_cap``: the ids a slot's draft history holds, fixed for the loop (default 8192)."""
         n = len(pasts)
-        per_seq_stops = each and len(stop_ids) and isinstance(stop_ids[0], (list, tuple))
-        if not (self.slot_loop_available() and self.lookup_available()) or not 1 <= n <= SlotLoop.MAX_SLOTS or \
-                (max(map(len, stop_ids)) if per_seq_stops else len(stop_ids)) > 8:
+        if not self.lookup_available() or not 1 <= n <= SlotLoop.MAX_SLOTS:
             return None
         S = slots if slots is not None else next(b for b in (1, 2, 4, 8, 16) if b >= (n if slot_index is None else max(slot_index) + 1))
         if not 1 <= k <= 15 or not n <= S <= SlotLoop.MAX_SLOTS or S * (k + 1) > LookupSlotLoop.MAX_ROWS:
             return None
-        arenas = []
-        for past in pasts:
-            a = self._loop_arena(past)
-            if a is None or any(a is b for b in arenas):
-                return None
-            a.materialize()
-            arenas.append(a)
-        if trunks is None and share_trunk:
-            trunks = common_trunks([a.layout for a in arenas], min_trunk)
+        front = self._slot_loop_front(pasts, stop_ids, each, share_trunk, min_trunk, trunks)
+        if front is None:
+            return None
+        arenas, trunks = front
         if each:
             return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
                                   slot_index, params, seeds, histories, hist_cap)
