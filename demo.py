@@ -52,15 +52,18 @@ def main():
     ap.add_argument("--lookup-sampled", action="store_true", default=None,
                     help="with --lookup K: sampled generations (and greedy ones with a repetition penalty) draft and verify too, "
                          "the sampler drawing every row (SampleLookupLoop; default: PC_LOOKUP_SAMPLE=1, else off)")
+    ap.add_argument("--weights", choices=("fp16", "mxfp4"), default=None,
+                    help="decoder weight format (default: PC_WEIGHTS, else fp16); mxfp4 = OCP MX 4-bit blocks, Llama family: the "
+                         "cached step and decode stream 4.25 bits per weight")
     a = ap.parse_args()
 
     if os.path.isdir(a.model):
         import json
         arch = json.load(open(os.path.join(a.model, "config.json"))).get("model_type", "llama")
-        lm = {"falcon": Falcon, "mpt": Mpt}.get(arch, Llama2)(a.model)
+        lm = {"falcon": Falcon, "mpt": Mpt}.get(arch, Llama2)(a.model, weight_format=a.weights)
     else:
         cls, shape = ADAPTERS[a.model]
-        lm = cls(shape, random_init=True)
+        lm = cls(shape, random_init=True, weight_format=a.weights)
     preproc = [lm.get_formatter()]
     cache_engine = CacheEngine(a.max_ctx, lm, module_kv=a.module_kv, slots=max(1, a.batch))
     gen_engine = GenerationEngine(lm, lookup=a.lookup, lookup_sampled=a.lookup_sampled)

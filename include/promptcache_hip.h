@@ -391,6 +391,34 @@ typedef struct pc_gemm_q8_args {
     const void* x_codes8; const float* x_scale; const void* x_flags;
 } pc_gemm_q8_args;
 int pc_gemm_q8(const pc_gemm_q8_args* args, void* stream);
+/* pc_gemm_w4 -- the projections of M <= 16 rows over MXFP4 weight images (csrc/pc_gemm_w4.hip): OCP MX blocks of 32 consecutive
+ *   input features of one output row, FP4 E2M1 codes (bits s e e m; codes 0..7 = 0, .5, 1, 1.5, 2, 3, 4, 6) under one E8M0 scale
+ *   byte (2^(byte - 127), block exponent clamped to [-13, 13] so that every dequantised weight is an fp16 normal or zero).
+ *   y[m][n] = sum_k (hi + lo)[m][k] W'[n][k] with W' the dequantised weight: pc_gemm's arithmetic on the fp16 image of W'.
+ *   Needs K % 128 == 0, N % 16 == 0.  The two images (_native.to_weight_frags_w4 from the quantiser's [N][K/2] codes -- low
+ *   nibble = lower feature -- and [N][K/32] scale bytes):
+ *   codes      [N/16][K/128][64][16 B]: lane l = 16*g + m of tile t holds, for the QUAD s of k-steps, row 16*t + m's features
+ *              128*s + 32*j + 8*g .. + 7 for j = 0..3, four bytes per j: one 16-byte load per lane feeds four k-steps
+ *   scales     [N/16][K/128][16] dwords: byte j of the dword of row m is the E8M0 byte of k-step 4*s + j (the four lanes of a
+ *              row read the same dword)
+ *   epilogue   PC_GEMM_EPI_STORE, PC_GEMM_EPI_ADD (y / ldy), PC_GEMM_EPI_SILU (of_hi, of_lo) as in pc_gemm_args
+ *   source     xf_hi + xf_lo (both), or (x, norm_weight, eps): the fp32 residual stream with RMSNorm folded in (STORE / SILU,
+ *              K <= 16384), as in pc_gemm_args
+ *   rows_dev   as in pc_gemm_args
+ *              (rows in [*rows_dev, M) are computed from zero activations and stored, as pc_gemm does)
+ *   The summation order is fixed and a row's result depends neither on M nor on the other rows (K is split eight ways inside
+ *   a workgroup as a function of K alone, never across workgroups). */
+typedef struct pc_gemm_w4_args {
+    uint32_t struct_bytes;
+    int32_t epilogue;
+    const void* codes; const void* scales;
+    const void* xf_hi; const void* xf_lo;
+    const float* x; const void* norm_weight; float eps;
+    int32_t M, N, K;
+    const int32_t* rows_dev;
+    float* y; int64_t ldy; void* of_hi; void* of_lo;
+} pc_gemm_w4_args;
+int pc_gemm_w4(const pc_gemm_w4_args* args, void* stream);
 /* pc_rmsnorm_frag -- LlamaRMSNorm (llama2.py:103-108) on the fp32 residual stream, output as fragment planes;
  *   optional prologue x += slabs[0] + ... + slabs[nslabs-1] (each [rows][hidden], the residual adds of
  *   llama2.py:638 / :644 fed by a K-sliced pc_gemm), written back to x in place. */
@@ -432,7 +460,9 @@ int pc_gelu_split(const float* x, const float* x2, void* out_hi, void* out_lo, i
 int pc_add3(float* x, const float* a, const float* b, int64_t n, void* stream);
 /* pc_rope_append_ex -- pc_rope_append that also writes the fp16 residuals of the appended K / V rows (k_lo, v_lo,
  *   both or neither: [B][Hkv][rows][D] with the given strides, row = key index - lo_row0; lo_row0 = past_len for a
- *   compact buffer of the new rows, 0 for an arena-shaped one that also carries residuals of earlier rows).  pc_attn consumes them: the keys / values a pass appends enter
+ *   compact buffer of the new rows, 0 for an arena-shaped one that also carries residuals of earlier rows; -1 / -2: the offset is
+ *   read on the device, as pc_attn's lo_row0 is: the past length the launch appends behind / past_len_dev[1], the base of a
+ *   residual tail -- what a captured graph needs, which replays at other past lengths).  pc_attn consumes them: the keys / values a pass appends enter
  *   (in2_offset != 0: every q / k_new / v_new input element is x[i] + x[i + in2_offset], the two row halves a stacked
  *   [hi; lo] projection leaves)
  *   its own attention in split precision, as in the reference's fp32 pass (llama2.py:361-388), while the arena keeps the

@@ -68,6 +68,9 @@ __global__ __launch_bounds__(256) void rope_append_kernel(
     const int t = blockIdx.x, b = blockIdx.y;
     if (past_len_dev) past_len = *past_len_dev;
     if (past_lens) past_len = past_lens[b];
+    // lo_row0 < 0: the row offset comes from the device, as pc_attn's lo_row0 does: -1 = this pass's rows (past_len), -2 = the
+    // residual tail's base, past_len_dev[1] (a captured graph replays at other past lengths than the one it was captured at)
+    if (lo_row0 < 0) lo_row0 = lo_row0 == -2 ? past_len_dev[1] : past_len;
     const int half = D >> 1;
     const int cph = D >> 4;  // 8-pair chunks per head
     const int nq = H * cph, nk = Hkv * cph, nv = Hkv * (D >> 3);
@@ -210,8 +213,9 @@ PC_EXPORT int pc_rope_append_ex(const void* q, int64_t q_batch_stride, int64_t q
                                 int64_t in2_offset, void* stream) {
     PC_REQUIRE((k_lo == nullptr) == (v_lo == nullptr), PC_ERR_ARG, "pc_rope_append_ex: k_lo and v_lo go together");
     PC_REQUIRE(in2_offset % 8 == 0, PC_ERR_ARG, "pc_rope_append_ex: in2_offset must keep 16-byte alignment");
-    PC_REQUIRE(!k_lo || (lo_row0 >= 0 && lo_row0 <= past_len && lo_head_stride % 8 == 0), PC_ERR_ARG,
-               "pc_rope_append_ex: lo_row0 must lie in [0, past_len] and the lo strides keep 16-byte alignment");
+    PC_REQUIRE(!k_lo || (lo_row0 >= -2 && lo_row0 <= past_len && (lo_row0 != -2 || past_len_dev) && lo_head_stride % 8 == 0), PC_ERR_ARG,
+               "pc_rope_append_ex: lo_row0 must be -1 (this pass's rows), -2 (past_len_dev[1]) or lie in [0, past_len], and the lo "
+               "strides keep 16-byte alignment");
     return rope_append_impl(q, q_batch_stride, q_token_stride, q_out, q_out_lo, qo_batch_stride, qo_token_stride, k_new, v_new,
                             kv_new_batch_stride, kv_new_token_stride, k_arena, v_arena, arena_batch_stride,
                             arena_head_stride, cs, B, H, Hkv, D, q_len, past_len, cap, in_is_f32, past_len_dev, k_lo, v_lo,

@@ -137,10 +137,20 @@ class GemmQ8Args(C.Structure):
                 ("x_codes8", _vp), ("x_scale", _vp), ("x_flags", _vp)]
 
 
+class GemmW4Args(C.Structure):
+    """``pc_gemm_w4_args`` of include/promptcache_hip.h (field for field)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("epilogue", _i32),
+                ("codes", _vp), ("scales", _vp), ("xf_hi", _vp), ("xf_lo", _vp),
+                ("x", _vp), ("norm_weight", _vp), ("eps", _f32),
+                ("M", _i32), ("N", _i32), ("K", _i32), ("rows_dev", _vp),
+                ("y", _vp), ("ldy", _i64), ("of_hi", _vp), ("of_lo", _vp)]
+
+
 # name -> (restype, argtypes); mirrors include/promptcache_hip.h one to one
 SIGNATURES = {
     "pc_attn": (C.c_int, [C.POINTER(AttnArgs), _vp]),
     "pc_gemm": (C.c_int, [C.POINTER(GemmArgs), _vp]),
+    "pc_gemm_w4": (C.c_int, [C.POINTER(GemmW4Args), _vp]),
     "pc_gemm_q8": (C.c_int, [C.POINTER(GemmQ8Args), _vp]),
     "pc_gemm_part": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pc_dev_gemm_trace": (C.c_int, [_vp]),
@@ -587,6 +597,99 @@ def to_weight_frags_i8(q):
     assert N % 16 == 0 and K % 64 == 0 and q.dtype == torch.int8, (N, K, q.dtype)
     u = (q.to(torch.int16) + 128).to(torch.uint8)
     return u.view(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------
+# MXFP4 weights (OCP MX: 32-element blocks, E8M0 scale, FP4 E2M1 elements) -- pc_gemm_w4
+# ------------------------------------------------------------------------------------------------
+MXFP4_BLOCK = 32
+MXFP4_EXP_MIN, MXFP4_EXP_MAX = -13, 13      # block exponents: every dequantised weight stays an fp16 normal (or zero)
+_MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mxfp4(w):
+    """Round-to-nearest MXFP4 of an nn.Linear weight [N, K] (K % 32 == 0), on the weight's device, deterministic.
+
+    Block = 32 consecutive input features of one output row; block exponent ``e = clamp(floor(log2(amax)) - 2, -13, 13)``
+    (all-zero block: 0), E8M0 byte ``e + 127``; element ``v = w * 2^-e`` (exact) rounded to the nearest of
+    ``{0, .5, 1, 1.5, 2, 3, 4, 6}`` with ties to the even CODE, ``|v| > 6`` saturating; code bits ``s e e m``, anything that
+    rounds to zero is code 0.  A NaN or an infinity raises ``ValueError``.
+    Returns ``(codes uint8 [N, K/2], exps uint8 [N, K/32])``; in a byte the low nibble is the lower feature index."""
+    import torch
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4: K={K} is not a multiple of {MXFP4_BLOCK}")
+    wf = w.float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_mxfp4: the weight holds a NaN or an infinity")
+    blk = wf.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    # amax = mant * 2^ex with mant in [0.5, 1): floor(log2(amax)) = ex - 1 (exact; no transcendental involved)
+    _, ex = torch.frexp(amax)
+    e = torch.where(amax > 0, (ex.to(torch.int32) - 3).clamp_(MXFP4_EXP_MIN, MXFP4_EXP_MAX), torch.zeros_like(ex, dtype=torch.int32))
+    v = blk * ((127 - e) << 23).view(torch.float32)[:, :, None]      # 2^-e by its bit pattern: the product is exact
+    a = v.abs()
+    # the midpoints of the grid; a tie goes to the even code: 0.25 -> 0, 0.75 -> 2, 1.25 -> 2, 1.75 -> 4, 2.5 -> 4, 3.5 -> 6, 5 -> 6
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8) +
+            (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) + (a > 5.0).to(torch.uint8))
+    code = code + (((v < 0) & (code > 0)).to(torch.uint8) << 3)
+    code = code.view(N, K // 2, 2)
+    packed = code[:, :, 0] | (code[:, :, 1] << 4)
+    return packed.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes, exps):
+    """``(codes uint8 [N, K/2], exps uint8 [N, K/32])`` -> fp16 ``[N, K]``, exact: every value of the grid times ``2^e`` with
+    ``e`` in [-13, 13] is an fp16 normal or zero."""
+    import torch
+    N, K2 = codes.shape
+    K = 2 * K2
+    assert exps.shape == (N, K // MXFP4_BLOCK) and codes.dtype == torch.uint8 and exps.dtype == torch.uint8, (codes.shape, exps.shape)
+    lut = torch.tensor(_MXFP4_GRID + tuple(-g for g in _MXFP4_GRID), dtype=torch.float32, device=codes.device)
+    nib = torch.stack((codes & 15, codes >> 4), dim=2).view(N, K).long()
+    v = lut[nib].view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    scale = (exps.to(torch.int32) << 23).view(torch.float32)[:, :, None]     # 2^(byte - 127) by its bit pattern
+    return (v * scale).view(N, K).half()
+
+
+def to_weight_frags_w4(codes, exps):
+    """The two images ``pc_gemm_w4`` streams (include/promptcache_hip.h), from ``quantize_mxfp4``'s output; K % 128 == 0 and
+    N % 16 == 0.  Codes ``[N/16][K/128][64][16]`` bytes: lane 16 g + m of tile t holds, for the quad s of k-steps, row
+    16 t + m's features 128 s + 32 j + 8 g .. + 7 for j = 0..3 (four bytes per j).  Scales ``[N/16][K/128][16][4]`` bytes:
+    byte j of the dword of row m is the E8M0 byte of k-step 4 s + j."""
+    import torch
+    N, K2 = codes.shape
+    K = 2 * K2
+    if K % 128 or N % 16:
+        raise ValueError(f"to_weight_frags_w4: need N % 16 == 0 and K % 128 == 0 (N={N}, K={K})")
+    assert exps.shape == (N, K // 32) and codes.dtype == torch.uint8 and exps.dtype == torch.uint8, (codes.shape, exps.shape)
+    # a row's bytes: [s][j][g][4]  ->  image [t][s][g][m][j][4]
+    ci = codes.view(N // 16, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).contiguous().view(N // 16, K // 128, 64, 16)
+    si = exps.view(N // 16, 16, K // 128, 4).permute(0, 2, 1, 3).contiguous()
+    return ci, si
+
+
+def from_weight_frags_w4(ci, si):
+    """Inverse of ``to_weight_frags_w4`` (test helper): ``(codes [N, K/2], exps [N, K/32])``."""
+    nt, kq = ci.shape[0], ci.shape[1]
+    codes = ci.view(nt, kq, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5).contiguous().view(nt * 16, kq * 64)
+    exps = si.view(nt, kq, 16, 4).permute(0, 2, 1, 3).contiguous().view(nt * 16, kq * 4)
+    return codes, exps
+
+
+def gemm_w4(codes_img, scales_img, M: int, N: int, K: int, epilogue: int, xf_hi=None, xf_lo=None, x=None, norm_weight=None,
+            eps: float = 0.0, y=None, ldy: int = 0, of_hi=None, of_lo=None, rows_dev=None, stream: Optional[int] = None) -> None:
+    """One ``pc_gemm_w4`` call (M <= 16): the activation planes, or ``x`` + ``norm_weight`` for the folded RMSNorm."""
+    a = GemmW4Args()
+    a.struct_bytes = C.sizeof(GemmW4Args)
+    a.epilogue, a.M, a.N, a.K, a.eps, a.ldy = epilogue, M, N, K, eps, ldy
+    a.codes, a.scales = _ptr(codes_img) or None, _ptr(scales_img) or None
+    for k, v in (("xf_hi", xf_hi), ("xf_lo", xf_lo), ("x", x), ("norm_weight", norm_weight), ("y", y), ("of_hi", of_hi),
+                 ("of_lo", of_lo), ("rows_dev", rows_dev)):
+        if v is not None:
+            setattr(a, k, v.data_ptr())
+    rc = load().pc_gemm_w4(C.byref(a), current_stream() if stream is None else stream)
+    check(rc, "pc_gemm_w4")
 
 
 def to_act_frags(x):

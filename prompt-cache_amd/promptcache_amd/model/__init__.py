@@ -138,6 +138,11 @@ def _mpt_formatter() -> FormatConversation:
                               assistant=("", "<|im_end|>\n"))
 
 
+def _weight_format(kwargs) -> str:
+    """``weight_format=`` of an adapter, else the environment's ``PC_WEIGHTS`` (default ``fp16``)."""
+    return kwargs.get("weight_format") or os.environ.get("PC_WEIGHTS", "fp16")
+
+
 class _LlamaFamily(LanguageModel):
     """Shared constructor: a local HF checkpoint directory when one exists, else (explicitly requested)
     seeded random weights at the named shape with the deterministic stand-in tokenizer -- the build and
@@ -147,14 +152,16 @@ class _LlamaFamily(LanguageModel):
 
     def __init__(self, name: Optional[str] = None, device: str = "cuda:0", shape: Optional[LlamaShape] = None,
                  weights=None, tokenizer=None, random_init: bool = False, seed: int = 0, **_hf_kwargs):
-        from .llama_hip import LlamaHIP
+        from .llama_hip import LlamaHIP, check_weight_format
         from . import weights as W
 
+        fmt, int8 = _weight_format(_hf_kwargs), bool(_hf_kwargs.get("load_in_8bit", False))
         name = name or self._default_name
         if weights is not None:                                       # caller-supplied tensors (tests)
             assert shape is not None, "pass shape= together with weights="
         elif os.path.isdir(name):                                     # real checkpoint directory
             shape = shape or LlamaShape.from_hf_dir(name)
+            check_weight_format(fmt, int8, shape)                       # (before any weight is read)
             weights = W.load_hf_safetensors(name, shape, device, torch.float16)
             if tokenizer is None:
                 from transformers import AutoTokenizer
@@ -169,11 +176,13 @@ class _LlamaFamily(LanguageModel):
                 raise FileNotFoundError(
                     f"no checkpoint directory {name!r} (there is no network here); pass random_init=True to use "
                     f"seeded N(0, {shape.initializer_range}) weights at the {shape.name} shape")
+            check_weight_format(fmt, int8, shape)                       # (before any weight is drawn)
             weights = W.random_weights_device(shape, device, torch.float16, seed)
         if tokenizer is None:
             tokenizer = StandInTokenizer(shape.vocab_size)
         # load_in_8bit (the reference's GPU configs, config/llm_config_*.json:5): weight-only int8 for the decoder linears
-        model = LlamaHIP(shape, weights, device=device, int8_weights=bool(_hf_kwargs.get("load_in_8bit", False)))
+        # weight_format="mxfp4" (or PC_WEIGHTS=mxfp4): MXFP4 decoder linears, 4-bit images for the <= 16-row projections
+        model = LlamaHIP(shape, weights, device=device, int8_weights=int8, weight_format=fmt)
         self.formatter = _llama_formatter()
         super().__init__(name, model, tokenizer, [tokenizer.eos_token_id], ["</s>"])
 
@@ -199,6 +208,9 @@ class Falcon(LanguageModel):
                  weights=None, tokenizer=None, random_init: bool = False, seed: int = 0, **_hf_kwargs):
         from .falcon_hip import FalconHIP
         from . import weights as W
+        from .llama_hip import check_weight_format
+
+        check_weight_format(_weight_format(_hf_kwargs), False, llama=False)      # (before any weight is read or drawn)
 
         name = name or self._default_name
         if weights is not None:
@@ -222,7 +234,8 @@ class Falcon(LanguageModel):
             weights = W.random_falcon_weights_device(shape, device, torch.float16, seed)
         if tokenizer is None:
             tokenizer = StandInTokenizer(shape.vocab_size)
-        model = FalconHIP(shape, weights, device=device, int8_weights=bool(_hf_kwargs.get("load_in_8bit", False)))
+        model = FalconHIP(shape, weights, device=device, int8_weights=bool(_hf_kwargs.get("load_in_8bit", False)),
+                          weight_format=_weight_format(_hf_kwargs))
         self.formatter = _falcon_formatter()
         super().__init__(name, model, tokenizer, list(range(12)), ["<|endoftext|>", "\nUser"])
 
@@ -246,6 +259,9 @@ class Mpt(LanguageModel):
                  weights=None, tokenizer=None, random_init: bool = False, seed: int = 0, **_hf_kwargs):
         from .mpt_hip import MptHIP
         from . import weights as W
+        from .llama_hip import check_weight_format
+
+        check_weight_format(_weight_format(_hf_kwargs), False, llama=False)      # (before any weight is read or drawn)
 
         name = name or self._default_name
         if weights is not None:
@@ -269,7 +285,8 @@ class Mpt(LanguageModel):
             weights = W.random_mpt_weights_device(shape, device, torch.float16, seed)
         if tokenizer is None:
             tokenizer = StandInTokenizer(shape.vocab_size)
-        model = MptHIP(shape, weights, device=device, int8_weights=bool(_hf_kwargs.get("load_in_8bit", False)))
+        model = MptHIP(shape, weights, device=device, int8_weights=bool(_hf_kwargs.get("load_in_8bit", False)),
+                       weight_format=_weight_format(_hf_kwargs))
         self.formatter = _mpt_formatter()
         super().__init__(name, model, tokenizer, [50278, 0], [])
 

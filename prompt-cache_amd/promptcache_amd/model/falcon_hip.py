@@ -23,7 +23,7 @@ import torch
 
 from .. import _native
 from .config import FalconShape
-from .llama_hip import LlamaHIP
+from .llama_hip import LlamaHIP, check_weight_format
 
 
 class FalconHIP(LlamaHIP):
@@ -32,7 +32,8 @@ class FalconHIP(LlamaHIP):
     supports_fused_gather = True    # (the weight-streaming loop hands pc_attn the row table: the first forward stages, as in LlamaHIP)
 
     def __init__(self, shape: FalconShape, weights: Dict[str, torch.Tensor], device="cuda:0", decode_headroom: int = 256,
-                 skinny: bool = True, int8_weights: bool = False):
+                 skinny: bool = True, int8_weights: bool = False, weight_format: str = "fp16"):
+        check_weight_format(weight_format, int8_weights, shape, llama=False)     # (MXFP4: the Llama family only)
         self._setup(shape, device, decode_headroom)
         c = shape
         self.H, self.Hkv, self.D, self.L = c.num_attention_heads, 1, c.head_dim, c.num_hidden_layers

@@ -945,6 +945,27 @@ class LookupSlotLoop(_SlotLoopHost):
             super().kill(j)
 
 
+WEIGHT_FORMATS = ("fp16", "mxfp4")
+
+
+def check_weight_format(weight_format: str, int8_weights: bool, shape=None, llama: bool = True) -> None:
+    """``ValueError`` for a weight format this model cannot load -- raised before anything is allocated."""
+    if weight_format not in WEIGHT_FORMATS:
+        raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, not {weight_format!r}")
+    if weight_format != "mxfp4":
+        return
+    if not llama:
+        raise ValueError("weight_format='mxfp4' is implemented for the Llama family only (not Falcon / MPT)")
+    if int8_weights:
+        raise ValueError("weight_format='mxfp4' and load_in_8bit / int8_weights exclude each other")
+    dims = (("hidden_size", shape.hidden_size), ("intermediate_size", shape.intermediate_size),
+            ("num_attention_heads * head_dim", shape.num_attention_heads * shape.head_dim))
+    for name, v in dims:
+        if v % 128:
+            raise ValueError(f"weight_format='mxfp4' needs {name} to be a multiple of 128 (a 16-byte lane load of the 4-bit "
+                             f"image is four 32-feature MX blocks); {name} = {v}")
+
+
 class LlamaHIP:
     """Weights live on one MI355X in fp16; ``wqkv`` and ``wgu`` are the row-concatenated q|k|v and
     gate|up projections so each is one GEMM."""
@@ -1042,6 +1063,7 @@ class LlamaHIP:
         self.supports_greedy_loop = True    # decode steps can run as a device-side loop (GreedyLoop)
         self._live_loop = None              # the device loop that owns the loop state words right now (one per model)
         self.llm_int8 = False
+        self.weight_format, self.w4, self.w4_stream = "fp16", False, False    # MXFP4 decoder weights (LlamaHIP.__init__)
         self._last_qt = None
         self.batch_invariant = True         # a row's result does not depend on the other rows of the forward (see llm_int8)
         self.tail_supported = True  # a subclass whose layer loops do not thread `_tail_for` through must switch this off
@@ -1068,11 +1090,17 @@ class LlamaHIP:
         return bool(self._shared_prefix_loop and self.precise_dense and not self.llm_int8)
 
     def __init__(self, shape: LlamaShape, weights: Dict[str, torch.Tensor], device="cuda:0",
-                 decode_headroom: int = 256, skinny: bool = True, int8_weights: bool = False):
+                 decode_headroom: int = 256, skinny: bool = True, int8_weights: bool = False, weight_format: str = "fp16"):
         """``int8_weights`` (the adapters' ``load_in_8bit=True``): the decoder-layer linears are quantised row-wise to
         int8 (``_native.quantize_rows_int8``); passes of <= 64 rows stream the int8 fragment images (half the bytes, exact
         arithmetic on the dequantised values); longer passes run hipBLASLt on the int8 codes held in fp16 (exact) and
-        scale the product per output feature (``_proj``)."""
+        scale the product per output feature (``_proj``).
+
+        ``weight_format="mxfp4"``: every decoder-layer linear is quantised at load to MXFP4 (``_native.quantize_mxfp4``) and the
+        model IS the fp16 model with the dequantised weights ``W'`` (exact in fp16): the layer keeps the fp16 images of ``W'``
+        for every path above 16 rows and, next to them, the two 4-bit images the <= 16-row projections stream (``pc_gemm_w4``:
+        the cached step, decode, the device loops).  ``PC_W4_STREAM=0`` runs the fp16 images of ``W'`` everywhere."""
+        check_weight_format(weight_format, int8_weights, shape)     # (before anything is allocated)
         self._setup(shape, device, decode_headroom)
         c = shape
         self.H, self.Hkv, self.D, self.L = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.num_hidden_layers
@@ -1129,11 +1157,30 @@ class LlamaHIP:
             self.batch_invariant = False                  # the fp16 outlier columns are chosen over ALL rows of a call
 
         prep = self._prep_linear
+        self.weight_format = weight_format
+        self.w4 = weight_format == "mxfp4"
+        # the <= 16-row projections on the 4-bit images.  They leave q|k|v as a plain fp32 store for pc_rope_append_ex (natural
+        # row order), which writes the residual tail as the fused epilogue does.  The forms that need fp16 fragment images
+        # inside their launch (pc_gemm_part, the in-launch K reduction, pc_gemm_chain) are off.
+        self.w4_stream = self.w4 and self.skinny and os.environ.get("PC_W4_STREAM", "1") != "0"
+        if self.w4_stream:
+            self.use_chain = False
+            self.defer_merge = False
+            self.ks_o = self.ks_down = None
 
         for i in range(self.L):
             wqkv = torch.cat([w(f"l{i}.wq"), w(f"l{i}.wk"), w(f"l{i}.wv")], dim=0).contiguous()
             wgu = torch.cat([w(f"l{i}.gate"), w(f"l{i}.up")], dim=0).contiguous()
             wo, wdown = w(f"l{i}.wo"), w(f"l{i}.down")
+            w4 = {}
+            if self.w4:
+                # W -> W' = dequant(quant(W)); the 4-bit images are in natural row order (q|k|v included)
+                def mx(wt, key):
+                    q = _native.quantize_mxfp4(wt)
+                    if self.w4_stream:
+                        w4[key + "_c4"], w4[key + "_e4"] = _native.to_weight_frags_w4(*q)
+                    return _native.dequantize_mxfp4(*q)
+                wqkv, wo, wgu, wdown = mx(wqkv, "wqkv"), mx(wo, "wo"), mx(wgu, "wgu"), mx(wdown, "wdown")
             if self.skinny and i == 0:
                 self._qkv_perm = _native.qkv_rope_row_perm(self.H + 2 * self.Hkv, self.D).to(dev)
             # q|k|v fragment image: rotary pairs share a 16-row tile (pc_gemm_qkv_rope)
@@ -1147,7 +1194,7 @@ class LlamaHIP:
                 for key, wt, tag in (("wqkv", wqkv, "qkv"), ("wo", wo, "o"), ("wgu", wgu, "gu"), ("wdown", wdown, "down")):
                     if tag not in self.dense_lo_skip and wt.shape[1] % 64 == 0:
                         q8[key + "_q8"], q8[key + "_q8s"] = _native.quantize_rows_int8(wt)
-            self.layers.append(dict(ln1=w(f"l{i}.ln1"), ln2=w(f"l{i}.ln2"), wqkv=wqkv, wo=wo, wgu=wgu, wdown=wdown, **q8,
+            self.layers.append(dict(ln1=w(f"l{i}.ln1"), ln2=w(f"l{i}.ln2"), wqkv=wqkv, wo=wo, wgu=wgu, wdown=wdown, **q8, **w4,
                                     wqkv_t8=t_qkv, wo_t8=t_o, wgu_t8=t_gu, wdown_t8=t_d,
                                     wqkv_f=wqkv_f, wo_f=wo_f, wgu_f=wgu_f, wdown_f=wdown_f,
                                     wqkv_s=wqkv_s[0], wo_s=wo_s[0], wgu_s=wgu_s[0], wdown_s=wdown_s[0],
@@ -1161,6 +1208,19 @@ class LlamaHIP:
             self._qkv_perm_i32 = self._qkv_perm.to(torch.int32).contiguous()
 
     # ------------------------------------------------------------------------------------------
+    def dequantized_weights(self) -> Dict[str, torch.Tensor]:
+        """name -> fp16 tensor of the weights this model computes with, under the names of the constructor's ``weights``: with
+        ``weight_format="mxfp4"`` the decoder linears are ``W' = dequant(quant(W))`` -- what an oracle of this model loads."""
+        if self.int8_weights:
+            raise ValueError("dequantized_weights: not kept in int8 mode")
+        HD, KD, inter = self.H * self.D, self.Hkv * self.D, self.config.intermediate_size
+        out = {"embed": self.embed, "norm": self.norm, "lm_head": self.lm_head}
+        for i, lw in enumerate(self.layers):
+            out.update({f"l{i}.ln1": lw["ln1"], f"l{i}.ln2": lw["ln2"], f"l{i}.wq": lw["wqkv"][:HD],
+                        f"l{i}.wk": lw["wqkv"][HD:HD + KD], f"l{i}.wv": lw["wqkv"][HD + KD:], f"l{i}.wo": lw["wo"],
+                        f"l{i}.gate": lw["wgu"][:inter], f"l{i}.up": lw["wgu"][inter:], f"l{i}.down": lw["wdown"]})
+        return out
+
     def new_arena(self, batch: int, cap: int) -> KVArena:
         return KVArena(batch, self.L, self.Hkv, cap, self.D, self.device, self.dtype)
 
@@ -1790,10 +1850,22 @@ class LlamaHIP:
         if chain and self._chain_sync is None:
             self._chain_sync = n.chain_sync_state(self.device)
         qkv_done = False
+        w4 = self.w4_stream and T <= 16               # the projections of this loop on the 4-bit images (pc_gemm_w4)
+        if w4:
+            W = (H + 2 * Hkv) * D
+            qkv = torch.empty((T, W), dtype=torch.float32, device=self.device)
         for li, lw in enumerate(layers):
             kp, vp = arena.k_plane(li), arena.v_plane(li)
             kvlo, lo_base = tail(li) if tail is not None else (None, -1)
-            if not qkv_done:
+            if w4:
+                # q|k|v as a plain store in natural row order, then RoPE + append (+ the residual rows: kvlo[4] is the row offset,
+                # -1 / -2 = read on the device like lo_base of the fused epilogue)
+                n.gemm_w4(lw["wqkv_c4"], lw["wqkv_e4"], T, W, hid, n.EPI_STORE, x=x, norm_weight=lw["ln1"], eps=eps, y=qkv, ldy=W,
+                          rows_dev=rows_dev)
+                n.rope_append(qkv, q_len * W, W, q16, q_len * H * D, H * D, qkv[:, H * D:], qkv[:, (H + Hkv) * D:], q_len * W, W,
+                              kp, vp, arena.batch_stride, arena.head_stride, cs, B, H, Hkv, D, q_len, past_len, arena.cap, True,
+                              past_len_dev=past_dev, q_out_lo=q16l, kv_lo=kvlo)
+            elif not qkv_done:
                 n.gemm_qkv_rope_norm(lw["wqkv_f"], x, lw["ln1"], eps, T, hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
                                      arena.head_stride, B, H, Hkv, D, q_len, past_len, arena.cap, past_dev,
                                      kv_lo=kvlo and kvlo[:4], wscale=lw["wqkv_s"], lo_base=lo_base, rows_dev=rows_dev)
@@ -1808,6 +1880,13 @@ class LlamaHIP:
                             q_lo=q16l, kv_lo=kvlo, counters=self._counters_for(B, H),
                             gather=None if self._gather is None else (self._gather, li * 2 * Hkv, (li * 2 + 1) * Hkv),
                             defer_merge=part_ok)
+            if w4:
+                n.gemm_w4(lw["wo_c4"], lw["wo_e4"], T, hid, H * D, n.EPI_ADD, xf_hi=ah, xf_lo=al, y=x, ldy=hid, rows_dev=rows_dev)
+                n.gemm_w4(lw["wgu_c4"], lw["wgu_e4"], T, 2 * inter, hid, n.EPI_SILU, x=x, norm_weight=lw["ln2"], eps=eps,
+                          of_hi=ch, of_lo=cl, rows_dev=rows_dev)
+                n.gemm_w4(lw["wdown_c4"], lw["wdown_e4"], T, hid, inter, n.EPI_ADD, xf_hi=ch, xf_lo=cl, y=x, ldy=hid,
+                          rows_dev=rows_dev)
+                continue
             if chain:
                 nxt = None
                 if li + 1 < len(layers):
@@ -2409,15 +2488,24 @@ class LlamaHIP:
         ah, al = planes(H * D)
         ch, cl = planes(inter)
         ks_down = self.ks_down and self.ks_min_rows <= S and inter >= 2 * hid
+        w4 = self.w4_stream and S <= 16               # the 4-bit images: q|k|v in natural row order (in_layout 0)
         for li, lw in enumerate(self.layers):
-            n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
-            n.rope_append_slots(qkv, W, 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D)
+            if w4:
+                n.gemm_w4(lw["wqkv_c4"], lw["wqkv_e4"], S, W, hid, n.EPI_STORE, x=x, norm_weight=lw["ln1"], eps=eps, y=qkv, ldy=W)
+            else:
+                n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+            n.rope_append_slots(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D)
             if nsplit_trunk:
                 n.attn_decode_slots_trunk(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], st["leader"],
                                           st["trunk"], S, li, H, Hkv, D, self.softmax_scale, nsplit, nsplit_trunk, ws, (ah, al))
             else:
                 n.attn_decode_slots(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
                                     self.softmax_scale, nsplit, ws, (ah, al))
+            if w4:
+                n.gemm_w4(lw["wo_c4"], lw["wo_e4"], S, hid, H * D, n.EPI_ADD, xf_hi=ah, xf_lo=al, y=x, ldy=hid)
+                n.gemm_w4(lw["wgu_c4"], lw["wgu_e4"], S, 2 * inter, hid, n.EPI_SILU, x=x, norm_weight=lw["ln2"], eps=eps, of_hi=ch, of_lo=cl)
+                n.gemm_w4(lw["wdown_c4"], lw["wdown_e4"], S, hid, inter, n.EPI_ADD, xf_hi=ch, xf_lo=cl, y=x, ldy=hid)
+                continue
             n.gemm_skinny(lw["wo_f"], ah, al, S, hid, H * D, n.EPI_ADD, y=x, ldy=hid)                  # x += attn @ Wo^T
             n.gemm_skinny_norm(lw["wgu_f"], x, lw["ln2"], eps, S, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
             if ks_down:
@@ -2562,8 +2650,10 @@ class LlamaHIP:
         ah, al = planes(H * D, True)
         ch, cl = planes(inter, True)
 
+        w4 = self.w4_stream and R <= 16               # the 4-bit images: q|k|v in natural row order (in_layout 0)
+
         def attend(li):
-            n.rope_append_slots_rows(qkv, W, 1, q16, q16l, H * D, cs, *slot, S, k, li, H, Hkv, D)
+            n.rope_append_slots_rows(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, *slot, S, k, li, H, Hkv, D)
             if nsplit_trunk:
                 n.attn_verify_slots_trunk(q16, q16l, H * D, *slot, st["leader"], st["trunk"], S, k, li, H, Hkv, D, self.softmax_scale,
                                           nsplit, nsplit_trunk, ws, (ah, al))
@@ -2573,6 +2663,13 @@ class LlamaHIP:
         if R <= 16:
             ks_down = self.ks_down and self.ks_min_rows <= R and inter >= 2 * hid
             for li, lw in enumerate(self.layers):
+                if w4:
+                    n.gemm_w4(lw["wqkv_c4"], lw["wqkv_e4"], R, W, hid, n.EPI_STORE, x=x, norm_weight=lw["ln1"], eps=eps, y=qkv, ldy=W)
+                    attend(li)
+                    n.gemm_w4(lw["wo_c4"], lw["wo_e4"], R, hid, H * D, n.EPI_ADD, xf_hi=ah, xf_lo=al, y=x, ldy=hid)
+                    n.gemm_w4(lw["wgu_c4"], lw["wgu_e4"], R, 2 * inter, hid, n.EPI_SILU, x=x, norm_weight=lw["ln2"], eps=eps, of_hi=ch, of_lo=cl)
+                    n.gemm_w4(lw["wdown_c4"], lw["wdown_e4"], R, hid, inter, n.EPI_ADD, xf_hi=ch, xf_lo=cl, y=x, ldy=hid)
+                    continue
                 n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
                 attend(li)
                 n.gemm_skinny(lw["wo_f"], ah, al, R, hid, H * D, n.EPI_ADD, y=x, ldy=hid)

@@ -21,7 +21,7 @@ import torch
 
 from .. import _native
 from .config import MptShape
-from .llama_hip import CausalLMOutput, LlamaHIP, prime_graph_capture
+from .llama_hip import CausalLMOutput, LlamaHIP, check_weight_format, prime_graph_capture
 
 _LOG2E = 1.4426950408889634
 
@@ -41,7 +41,8 @@ class MptHIP(LlamaHIP):
     supports_fused_gather = False   # (its layer loops read staged rows from the arena: PromptCache.update copies at once)
 
     def __init__(self, shape: MptShape, weights: Dict[str, torch.Tensor], device="cuda:0", decode_headroom: int = 256,
-                 skinny: bool = True, int8_weights: bool = False):
+                 skinny: bool = True, int8_weights: bool = False, weight_format: str = "fp16"):
+        check_weight_format(weight_format, int8_weights, shape, llama=False)     # (MXFP4: the Llama family only)
         self._setup(shape, device, decode_headroom)
         c = shape
         self.H = self.Hkv = c.num_attention_heads

@@ -1,0 +1,203 @@
+"""MXFP4 decoder weights against fp16 and int8, same process, same box: 7b shape (random init), the persona prompt bench.py
+times.  Four models, built one after another and measured INTERLEAVED (repetition r of every leg before repetition r + 1 of any, the order rotating by one leg per repetition):
+
+    (a) fp16                 weight_format="fp16"
+    (b) mxfp4                weight_format="mxfp4": the <= 16-row projections stream the 4-bit images (pc_gemm_w4)
+    (c) mxfp4_fp16_images    the same weights W' with PC_W4_STREAM=0: the parent's kernels on the fp16 images of W'
+    (d) int8_weight_only     load_in_8bit with PC_INT8_WEIGHT_ONLY=1
+
+Per leg: TTFT (CacheEngine.process + the first forward, 12 new rows over the staged modules) and its two parts, the GreedyLoop
+rate (generate, greedy; first Output to last, host clock) and the one-row decode step on the device's clock (--new GreedyLoop
+replays between two events), the SlotLoop rate at 4 / 8 / 16 slots (generate_batch; tokens summed over the
+sequences, prefills excluded; null where the model has no batched loop), resident weight bytes.  Medians of --repeats
+repetitions with the spread (min, max, and (max - min) / median).  The condition the mode is held to: (b) faster than (c) by
+more than (c)'s own spread on the 12-row cached step and on the one-row decode step.  Also max |dlogit| of the first forward's
+last row between the legs ((a)-(b): the format's accuracy on this model; (b)-(c): the same weights on two kernels).
+
+    python tools/w4_bench.py [--repeats 20] [--new 48] [--out profiles/w4_bench.json]
+    python tools/w4_bench.py --only mxfp4       # leg (b)'s step alone: the run to put under rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "prompt-cache_amd")]
+from promptcache_amd import CacheEngine, GenerationEngine, GenerationParameters, Prompt, synth  # noqa: E402
+from promptcache_amd.model import Llama2  # noqa: E402
+
+LEGS = {
+    "fp16": (dict(weight_format="fp16"), {}),
+    "mxfp4": (dict(weight_format="mxfp4"), {"PC_W4_STREAM": "1"}),
+    "mxfp4_fp16_images": (dict(weight_format="mxfp4"), {"PC_W4_STREAM": "0"}),
+    "int8_weight_only": (dict(weight_format="fp16", load_in_8bit=True), {"PC_INT8_WEIGHT_ONLY": "1"}),
+}
+SLOTS = (4, 8, 16)
+
+
+def weight_bytes(m) -> int:
+    """Bytes of every tensor the model keeps resident for its weights (each storage once)."""
+    seen, total = set(), 0
+    tensors = [m.embed, m.norm, m.lm_head, m.lm_head_f] + [v for lw in m.layers for v in lw.values()]
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.untyped_storage().data_ptr() not in seen:
+            seen.add(t.untyped_storage().data_ptr())
+            total += t.untyped_storage().nbytes()
+    return total
+
+
+class Leg:
+    def __init__(self, name):
+        kw, env = LEGS[name]
+        saved = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            self.lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0, **kw)
+        finally:
+            for k, v in saved.items():
+                os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+        self.name = name
+        self.eng = CacheEngine(4096, self.lm, slots=max(SLOTS))
+        fmt = self.lm.get_formatter()
+        sp, pp = synth.persona_like()
+        self.eng.add_schema(fmt(sp))
+        self.prompt = Prompt(pp, [fmt])
+        self.ge = GenerationEngine(self.lm)
+
+    def ttft(self):
+        """(process ms, first forward ms, last-row logits)"""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ids, pos, _, cache = self.eng.process(self.prompt)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        out = self.lm(input_ids=torch.tensor([ids], device="cuda:0"), position_ids=torch.tensor([pos], device="cuda:0"),
+                      past_key_values=cache, use_cache=True)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        return 1e3 * (t1 - t0), 1e3 * (t2 - t1), out.logits[0, -1].float().clone(), len(ids)
+
+    def greedy_rate(self, params):
+        ids, pos, _, cache = self.eng.process(self.prompt)
+        t0 = None
+        for _out in self.ge.generate(ids, pos, params, cache, stream_interval=10 ** 9):
+            if t0 is None:
+                t0 = time.perf_counter()
+        torch.cuda.synchronize()
+        return (params.max_new_tokens - 1) / (time.perf_counter() - t0)
+
+    def decode_step_ms(self, n):
+        """One-row decode step on the device's clock: n GreedyLoop replays behind the cached prefill, first replay's start event
+        to the last one's end event (None where the model has no device loop)."""
+        m = self.lm.hf_model
+        ids, pos, _, cache = self.eng.process(self.prompt)
+        out = self.lm(input_ids=torch.tensor([ids], device="cuda:0"), position_ids=torch.tensor([pos], device="cuda:0"),
+                      past_key_values=cache, use_cache=True)
+        past = out.past_key_values
+        if not m.can_loop(past):
+            return None
+        g = m.greedy_loop(past, int(torch.argmax(out.logits[0, -1])), max(pos) + 2, n)
+        if g is None:
+            return None
+        for _ in range(n):
+            g.enqueue()
+        torch.cuda.synchronize()
+        ms = g.events[0][0].elapsed_time(g.events[-1][1]) / n
+        g.close(n)
+        return ms
+
+    def slot_rate(self, params, B):
+        if not self.ge.batch_plan(B, params)[0]:
+            return None
+        reqs = [self.eng.process(self.prompt, slot=k) for k in range(B)]
+        firsts, t0 = 0, None
+        for _k, _out in self.ge.generate_batch([(r[0], r[1], r[3]) for r in reqs], params, stream_interval=10 ** 9):
+            firsts += 1
+            if firsts == B:
+                t0 = time.perf_counter()
+        torch.cuda.synchronize()
+        return B * (params.max_new_tokens - 1) / (time.perf_counter() - t0)
+
+
+def summary(vals, nd=3):
+    vals = [v for v in vals if v is not None]
+    if not vals:
+        return None
+    med = statistics.median(vals)
+    return {"median": round(med, nd), "min": round(min(vals), nd), "max": round(max(vals), nd),
+            "spread": round((max(vals) - min(vals)) / med, 4), "n": len(vals)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--new", type=int, default=48, help="greedy tokens per sequence")
+    ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--only", default=None, help="one leg's cached step and decode loop alone (warm + 3 repetitions), no JSON file")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "w4_bench.json"))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "w4_bench measures on the GPU"
+    params = GenerationParameters(temperature=0.0, max_new_tokens=args.new, stop_token_ids=[], stop_str=[])
+    if args.only:
+        leg = Leg(args.only)
+        for _ in range(4):
+            leg.ttft()
+            leg.greedy_rate(params)
+        print(json.dumps({"leg": args.only, "first_forward_ms": round(leg.ttft()[1], 3), "greedy_tok_s": round(leg.greedy_rate(params), 1)}))
+        return
+    legs = [Leg(n) for n in args.legs.split(",")]
+    for leg in legs:                                   # warm: graphs captured, code objects loaded
+        for _ in range(3):
+            leg.ttft()
+        leg.greedy_rate(params)
+        leg.decode_step_ms(args.new)
+        for B in SLOTS:
+            leg.slot_rate(params, B)
+    rec = {leg.name: {"process_ms": [], "first_forward_ms": [], "ttft_ms": [], "greedy_tok_s": [], "decode_step_ms": [],
+                      **{f"slot{B}_tok_s": [] for B in SLOTS}} for leg in legs}
+    logits, rows = {}, None
+    for rep in range(args.repeats):
+        for leg in legs[rep % len(legs):] + legs[:rep % len(legs)]:     # (the order rotates: no leg always runs behind the same one)
+            r = rec[leg.name]
+            p, f, lg, rows = leg.ttft()
+            r["process_ms"].append(p); r["first_forward_ms"].append(f); r["ttft_ms"].append(p + f)
+            logits[leg.name] = lg
+            r["greedy_tok_s"].append(leg.greedy_rate(params))
+            r["decode_step_ms"].append(leg.decode_step_ms(args.new))
+            for B in SLOTS:
+                r[f"slot{B}_tok_s"].append(leg.slot_rate(params, B))
+    result = {"shape": "llama2-7b (random init)", "prompt": f"persona schema, {rows} new rows over the staged modules",
+              "new_tokens": args.new, "how": f"{args.repeats} interleaved repetitions, leg order rotating; median, min, max, spread = (max - min) / median",
+              "legs": {}}
+    for leg in legs:
+        row = {k: summary(v, 1 if k.endswith("tok_s") else 3) for k, v in rec[leg.name].items()}
+        row["weight_bytes"] = weight_bytes(leg.lm.hf_model)
+        result["legs"][leg.name] = row
+
+    def dl(a, b):
+        return None if a not in logits or b not in logits else float((logits[a] - logits[b]).abs().max())
+    result["max_dlogit"] = {"fp16_vs_mxfp4": dl("fp16", "mxfp4"), "mxfp4_vs_mxfp4_fp16_images": dl("mxfp4", "mxfp4_fp16_images")}
+    if "mxfp4" in result["legs"] and "mxfp4_fp16_images" in result["legs"]:
+        b, c = result["legs"]["mxfp4"], result["legs"]["mxfp4_fp16_images"]
+        cond = {}
+        for key in ("first_forward_ms", "decode_step_ms"):
+            if b[key] is None or c[key] is None:
+                continue
+            gain = (c[key]["median"] - b[key]["median"]) / c[key]["median"]
+            cond[key] = {"b_median": b[key]["median"], "c_median": c[key]["median"], "gain": round(gain, 4),
+                         "c_spread": c[key]["spread"], "met": bool(gain > c[key]["spread"])}
+        result["condition_b_faster_than_c_by_more_than_c_spread"] = cond
+    line = json.dumps(result)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
