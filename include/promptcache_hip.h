@@ -419,6 +419,26 @@ typedef struct pc_gemm_w4_args {
     float* y; int64_t ldy; void* of_hi; void* of_lo;
 } pc_gemm_w4_args;
 int pc_gemm_w4(const pc_gemm_w4_args* args, void* stream);
+/* pc_gemm_w4_rows -- the same projections for 1 <= M <= 64 rows over the SAME two MXFP4 images (csrc/pc_gemm_w4_rows.hip): the
+ *   form of the 17..64-row steps (a cached step with a 17..64-token question, the slot-lookup verify step of S * (k + 1) rows).
+ *   y[m][n] = sum_k (hi + lo)[m][k] W'[n][k].  Needs K % 128 == 0, N % 16 == 0.
+ *   xf_hi, xf_lo   the split-precision activation planes [ceil(M/16)][K/32][64][8] (both; rows behind M are never read)
+ *   epilogue   PC_GEMM_EPI_STORE: y / ldy, fp32 row-major; K is cut into kslices (1..8) workgroup slices, slice s owns the quads
+ *              of k-steps [s * ceil(K/128 / kslices), ...) and writes slab y + s * M * ldy (the slabs pc_rmsnorm_frag folds in fixed
+ *              order; a slice that owns no quad writes zeros).  PC_GEMM_EPI_SILU (N = 2 * inter, N % 64 == 0, kslices = 1):
+ *              of_hi / of_lo fragment planes [ceil(M/16)][inter/32][64][8], as in pc_gemm_args
+ *   The summation order is fixed (a slice's quads split eight ways over the waves in ascending order as a function of (K, kslices)
+ *   alone, k-steps ascending inside a wave, waves added in order 0..7; no atomics).  A row's result depends neither on M, nor on
+ *   the other rows, nor on its row tile; at kslices = 1 it is bit-identical to pc_gemm_w4 on that row (planes source). */
+typedef struct pc_gemm_w4_rows_args {
+    uint32_t struct_bytes;
+    int32_t epilogue;
+    const void* codes; const void* scales;
+    const void* xf_hi; const void* xf_lo;
+    int32_t M, N, K, kslices;
+    float* y; int64_t ldy; void* of_hi; void* of_lo;
+} pc_gemm_w4_rows_args;
+int pc_gemm_w4_rows(const pc_gemm_w4_rows_args* args, void* stream);
 /* pc_rmsnorm_frag -- LlamaRMSNorm (llama2.py:103-108) on the fp32 residual stream, output as fragment planes;
  *   optional prologue x += slabs[0] + ... + slabs[nslabs-1] (each [rows][hidden], the residual adds of
  *   llama2.py:638 / :644 fed by a K-sliced pc_gemm), written back to x in place. */

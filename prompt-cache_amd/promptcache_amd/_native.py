@@ -146,11 +146,20 @@ class GemmW4Args(C.Structure):
                 ("y", _vp), ("ldy", _i64), ("of_hi", _vp), ("of_lo", _vp)]
 
 
-# name -> (restype, argtypes); mirrors include/promptcache_hip.h one to one
+class GemmW4RowsArgs(C.Structure):
+    """``pc_gemm_w4_rows_args`` of include/promptcache_hip.h (field for field)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("epilogue", _i32),
+                ("codes", _vp), ("scales", _vp), ("xf_hi", _vp), ("xf_lo", _vp),
+                ("M", _i32), ("N", _i32), ("K", _i32), ("kslices", _i32),
+                ("y", _vp), ("ldy", _i64), ("of_hi", _vp), ("of_lo", _vp)]
+
+
+# name ->(restype, argtypes); mirrors include/promptcache_hip.h one to one
 SIGNATURES = {
     "pc_attn": (C.c_int, [C.POINTER(AttnArgs), _vp]),
     "pc_gemm": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "pc_gemm_w4": (C.c_int, [C.POINTER(GemmW4Args), _vp]),
+    "pc_gemm_w4_rows": (C.c_int, [C.POINTER(GemmW4RowsArgs), _vp]),
     "pc_gemm_q8": (C.c_int, [C.POINTER(GemmQ8Args), _vp]),
     "pc_gemm_part": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pc_dev_gemm_trace": (C.c_int, [_vp]),
@@ -690,6 +699,21 @@ def gemm_w4(codes_img, scales_img, M: int, N: int, K: int, epilogue: int, xf_hi=
             setattr(a, k, v.data_ptr())
     rc = load().pc_gemm_w4(C.byref(a), current_stream() if stream is None else stream)
     check(rc, "pc_gemm_w4")
+
+
+def gemm_w4_rows(codes_img, scales_img, xf_hi, xf_lo, M: int, N: int, K: int, epilogue: int, y=None, ldy: int = 0, of_hi=None,
+                 of_lo=None, kslices: int = 1, stream: Optional[int] = None, struct_bytes: Optional[int] = None) -> None:
+    """One ``pc_gemm_w4_rows`` call (1 <= M <= 64) on the images of ``to_weight_frags_w4``: ``EPI_STORE`` into ``kslices`` slabs
+    ``y[s]`` of ``[M][ldy]``, or ``EPI_SILU`` into the planes ``of_hi`` / ``of_lo``."""
+    a = GemmW4RowsArgs()
+    a.struct_bytes = C.sizeof(GemmW4RowsArgs) if struct_bytes is None else struct_bytes
+    a.epilogue, a.M, a.N, a.K, a.kslices, a.ldy = epilogue, M, N, K, kslices, ldy
+    a.codes, a.scales = _ptr(codes_img) or None, _ptr(scales_img) or None
+    for k, v in (("xf_hi", xf_hi), ("xf_lo", xf_lo), ("y", y), ("of_hi", of_hi), ("of_lo", of_lo)):
+        if v is not None:
+            setattr(a, k, v.data_ptr())
+    rc = load().pc_gemm_w4_rows(C.byref(a), current_stream() if stream is None else stream)
+    check(rc, "pc_gemm_w4_rows")
 
 
 def to_act_frags(x):

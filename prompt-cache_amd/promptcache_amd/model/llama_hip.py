@@ -966,6 +966,11 @@ def check_weight_format(weight_format: str, int8_weights: bool, shape=None, llam
                              f"image is four 32-feature MX blocks); {name} = {v}")
 
 
+# weight_format="mxfp4": most rows of a step that streams the 4-bit images (PC_W4_MAX_ROWS, clamped to 16..64).  64: at 17, 32, 48
+# and 64 rows the 4-bit images beat the fp16 images of W' by more than the latter's own spread
+W4_MAX_ROWS_DEFAULT = "64"
+
+
 class LlamaHIP:
     """Weights live on one MI355X in fp16; ``wqkv`` and ``wgu`` are the row-concatenated q|k|v and
     gate|up projections so each is one GEMM."""
@@ -1064,6 +1069,7 @@ class LlamaHIP:
         self._live_loop = None              # the device loop that owns the loop state words right now (one per model)
         self.llm_int8 = False
         self.weight_format, self.w4, self.w4_stream = "fp16", False, False    # MXFP4 decoder weights (LlamaHIP.__init__)
+        self.w4_max_rows = 16
         self._last_qt = None
         self.batch_invariant = True         # a row's result does not depend on the other rows of the forward (see llm_int8)
         self.tail_supported = True  # a subclass whose layer loops do not thread `_tail_for` through must switch this off
@@ -1099,7 +1105,9 @@ class LlamaHIP:
         ``weight_format="mxfp4"``: every decoder-layer linear is quantised at load to MXFP4 (``_native.quantize_mxfp4``) and the
         model IS the fp16 model with the dequantised weights ``W'`` (exact in fp16): the layer keeps the fp16 images of ``W'``
         for every path above 16 rows and, next to them, the two 4-bit images the <= 16-row projections stream (``pc_gemm_w4``:
-        the cached step, decode, the device loops).  ``PC_W4_STREAM=0`` runs the fp16 images of ``W'`` everywhere."""
+        the cached step, decode, the device loops).  ``PC_W4_MAX_ROWS`` (16..64) extends the images to the steps of 17 rows up
+        to it (``pc_gemm_w4_rows``: a cached step with a longer question, the slot-lookup verify step).  ``PC_W4_STREAM=0`` runs
+        the fp16 images of ``W'`` everywhere."""
         check_weight_format(weight_format, int8_weights, shape)     # (before anything is allocated)
         self._setup(shape, device, decode_headroom)
         c = shape
@@ -1163,6 +1171,9 @@ class LlamaHIP:
         # row order), which writes the residual tail as the fused epilogue does.  The forms that need fp16 fragment images
         # inside their launch (pc_gemm_part, the in-launch K reduction, pc_gemm_chain) are off.
         self.w4_stream = self.w4 and self.skinny and os.environ.get("PC_W4_STREAM", "1") != "0"
+        # ... and the 17..w4_max_rows-row steps (the generic loop of _forward_skinny, the 17..64-row branch of the slot-lookup step)
+        # on the same images (pc_gemm_w4_rows); 16 = those steps stay on the fp16 images of W' (DESIGN 3.25 has the measurements)
+        self.w4_max_rows = min(max(int(os.environ.get("PC_W4_MAX_ROWS", W4_MAX_ROWS_DEFAULT)), 16), self.SKINNY_MAX_ROWS)
         if self.w4_stream:
             self.use_chain = False
             self.defer_merge = False
@@ -1850,7 +1861,9 @@ class LlamaHIP:
         if chain and self._chain_sync is None:
             self._chain_sync = n.chain_sync_state(self.device)
         qkv_done = False
-        w4 = self.w4_stream and T <= 16               # the projections of this loop on the 4-bit images (pc_gemm_w4)
+        # the projections of this loop on the 4-bit images (pc_gemm_w4).  (PC_NORM_FUSED_MAX=32 set by hand: 17..32 rows of this
+        # loop stay on the fp16 images -- pc_gemm_w4_rows has no norm-folded source and no ADD epilogue)
+        w4 = self.w4_stream and T <= 16
         if w4:
             W = (H + 2 * Hkv) * D
             qkv = torch.empty((T, W), dtype=torch.float32, device=self.device)
@@ -2622,7 +2635,8 @@ class LlamaHIP:
                               each: bool = False) -> None:
         """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
         k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
-        projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop.
+        projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop (on the 4-bit
+        images up to ``w4_max_rows`` rows).
         ``nsplit_trunk`` > 0: the attention with shared trunks (leader / trunk words of the state)."""
         n = _native
         dev, c = self.device, self.config
@@ -2650,7 +2664,8 @@ class LlamaHIP:
         ah, al = planes(H * D, True)
         ch, cl = planes(inter, True)
 
-        w4 = self.w4_stream and R <= 16               # the 4-bit images: q|k|v in natural row order (in_layout 0)
+        # the 4-bit images: q|k|v in natural row order (in_layout 0); 17..w4_max_rows rows run pc_gemm_w4_rows
+        w4 = self.w4_stream and R <= self.w4_max_rows
 
         def attend(li):
             n.rope_append_slots_rows(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, *slot, S, k, li, H, Hkv, D)
@@ -2687,13 +2702,21 @@ class LlamaHIP:
             pending = 0
             for li, lw in enumerate(self.layers):
                 n.rmsnorm_frag(x, lw["ln1"], xh, xl, R, hid, eps, slabs, pending)
+                pending = KQ
+                if w4:
+                    n.gemm_w4_rows(lw["wqkv_c4"], lw["wqkv_e4"], xh, xl, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+                    attend(li)
+                    n.gemm_w4_rows(lw["wo_c4"], lw["wo_e4"], ah, al, R, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                    n.rmsnorm_frag(x, lw["ln2"], xh, xl, R, hid, eps, slabs, KQ)
+                    n.gemm_w4_rows(lw["wgu_c4"], lw["wgu_e4"], xh, xl, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+                    n.gemm_w4_rows(lw["wdown_c4"], lw["wdown_e4"], ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                    continue
                 n.gemm_skinny(lw["wqkv_f"], xh, xl, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
                 attend(li)
                 n.gemm_skinny(lw["wo_f"], ah, al, R, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
                 n.rmsnorm_frag(x, lw["ln2"], xh, xl, R, hid, eps, slabs, KQ)
                 n.gemm_skinny(lw["wgu_f"], xh, xl, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
                 n.gemm_skinny(lw["wdown_f"], ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
-                pending = KQ
             n.rmsnorm_frag(x, self.norm, xh, xl, R, hid, eps, slabs, pending)
             n.gemm_skinny(self.lm_head_f, xh, xl, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
         if each:                      # the sampler on every row, per slot
@@ -2777,20 +2800,37 @@ class LlamaHIP:
         if T <= (16 if self.int8_weights else self.NORM_FUSED_MAX_ROWS) and self.fuse_norm:   # (int8 weight images: one row tile)
             return self._layers_norm_fused(x, cs, q16, q16l, ws, ah, al, ch, cl, arena, layers, B, q_len, past_len, past_dev,
                                            last_token_only, tail)
+        # 17..w4_max_rows rows of an MXFP4 model: the four projections on the 4-bit images (pc_gemm_w4_rows), q|k|v as a plain
+        # store in natural row order followed by pc_rope_append_ex, as the <= 16-row loop has it (_layers_norm_fused)
+        w4 = self.w4_stream and 16 < T <= self.w4_max_rows
+        qkv = torch.empty((T, W), dtype=torch.float32, device=dev) if w4 else None
         for li, lw in enumerate(layers):
             n.rmsnorm_frag(x, lw["ln1"], xh, xl, T, hid, eps, slabs, pending)
             kp, vp = arena.k_plane(li), arena.v_plane(li)
             kvlo, lo_base = tail(li)
-            # q|k|v projection + RoPE + in-place KV append in one weight-streaming launch
-            n.gemm_qkv_rope(lw["wqkv_f"], xh, xl, T, hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
-                            arena.head_stride, B, H, Hkv, D, q_len, past_len, arena.cap, past_dev, kv_lo=kvlo and kvlo[:4],
-                            wscale=lw["wqkv_s"], lo_base=lo_base, kslices=QS, scratch=qkv_slabs)
+            if w4:
+                n.gemm_w4_rows(lw["wqkv_c4"], lw["wqkv_e4"], xh, xl, T, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+                n.rope_append(qkv, q_len * W, W, q16, q_len * H * D, H * D, qkv[:, H * D:], qkv[:, (H + Hkv) * D:], q_len * W, W,
+                              kp, vp, arena.batch_stride, arena.head_stride, cs, B, H, Hkv, D, q_len, past_len, arena.cap, True,
+                              past_len_dev=past_dev, q_out_lo=q16l, kv_lo=kvlo)
+            else:
+                # q|k|v projection + RoPE + in-place KV append in one weight-streaming launch
+                n.gemm_qkv_rope(lw["wqkv_f"], xh, xl, T, hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
+                                arena.head_stride, B, H, Hkv, D, q_len, past_len, arena.cap, past_dev, kv_lo=kvlo and kvlo[:4],
+                                wscale=lw["wqkv_s"], lo_base=lo_base, kslices=QS, scratch=qkv_slabs)
             if self._kv_only and li == len(layers) - 1:
                 return None       # schema encode: the K / V of the last layer are written; nothing after them is used
             n.attn_fwd(q16, q_len * H * D, H * D, kp, vp, arena.batch_stride, arena.head_stride, None, 0, 0,
                        B, H, Hkv, D, q_len, past_len, self.softmax_scale, ws, past_len_dev=past_dev, out_frag=(ah, al),
                        q_lo=q16l, kv_lo=kvlo, counters=self._counters_for(B, H),
                        gather=None if self._gather is None else (self._gather, li * 2 * Hkv, (li * 2 + 1) * Hkv))
+            if w4:
+                n.gemm_w4_rows(lw["wo_c4"], lw["wo_e4"], ah, al, T, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                n.rmsnorm_frag(x, lw["ln2"], xh, xl, T, hid, eps, slabs, KQ)
+                n.gemm_w4_rows(lw["wgu_c4"], lw["wgu_e4"], xh, xl, T, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+                n.gemm_w4_rows(lw["wdown_c4"], lw["wdown_e4"], ch, cl, T, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                pending = KQ
+                continue
             mid_skip = self.mid_lo_skip if (T > self.SKINNY_MAX_ROWS and self._lo_mode != 3) else ()      # (precision audit: tools/plane_audit.py)
             n.gemm_skinny(lw["wo_f"], ah, None if "o" in mid_skip else al, T, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ,
                           wscale=lw["wo_s"])                                                    # attn @ Wo^T

@@ -110,9 +110,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--only-serve", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--weight-format", default="fp16", help="fp16 or mxfp4 (with PC_W4_STREAM / PC_W4_MAX_ROWS from the environment)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "serve_bench measures on the GPU"
-    lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0)
+    lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0, weight_format=args.weight_format)
     eng = CacheEngine(4096, lm, slots=args.slots)
     fmt = lm.get_formatter()
     sp, pp = synth.persona_like()

@@ -16,6 +16,15 @@ last row between the legs ((a)-(b): the format's accuracy on this model; (b)-(c)
 
     python tools/w4_bench.py [--repeats 20] [--new 48] [--out profiles/w4_bench.json]
     python tools/w4_bench.py --only mxfp4       # leg (b)'s step alone: the run to put under rocprofv3 --kernel-trace --stats
+
+``--rows``: the 17..64-row steps, legs (b) with PC_W4_MAX_ROWS=64 (pc_gemm_w4_rows) and (c), interleaved in the same
+rotating order: the cached step at 17 / 32 / 48 / 64 new rows (HIP events around the forward) and the LookupSlotLoop step at 8 slots
+with k = 3 and k = 7 (32 and 64 rows; an empty corpus, HIP events around one replay).  The default of PC_W4_MAX_ROWS the numbers
+imply: the largest of {16, 32, 48, 64} such that at it and at every smaller measured row count (b)'s median beats (c)'s by more
+than (c)'s own (max - min) / median.
+
+    python tools/w4_bench.py --rows [--repeats 10] [--out profiles/w4_rows_bench.json]
+    python tools/w4_bench.py --rows --only mxfp4     # leg (b)'s steps alone, for rocprofv3 --kernel-trace --stats
 """
 import argparse
 import json
@@ -38,6 +47,8 @@ LEGS = {
     "int8_weight_only": (dict(weight_format="fp16", load_in_8bit=True), {"PC_INT8_WEIGHT_ONLY": "1"}),
 }
 SLOTS = (4, 8, 16)
+ROW_COUNTS = (17, 32, 48, 64)
+LOOKUP_CASES = ((8, 3), (8, 7))
 
 
 def weight_bytes(m) -> int:
@@ -52,8 +63,9 @@ def weight_bytes(m) -> int:
 
 
 class Leg:
-    def __init__(self, name):
+    def __init__(self, name, extra_env=None):
         kw, env = LEGS[name]
+        env = dict(env, **(extra_env or {}))
         saved = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         try:
@@ -124,6 +136,109 @@ class Leg:
         return B * (params.max_new_tokens - 1) / (time.perf_counter() - t0)
 
 
+    # ---- the 17..64-row steps (--rows) ----
+    def question(self, rows):
+        """The persona prompt with a question that gives exactly ``rows`` new rows over the staged modules."""
+        fmt = self.lm.get_formatter()
+        for qlen in range(1, 2 * rows):
+            _, pp = synth.persona_like(question_len=qlen)
+            prompt = Prompt(pp, [fmt])
+            if len(self.eng.process(prompt)[0]) == rows:
+                return prompt
+        raise RuntimeError(f"no question length gives {rows} new rows")
+
+    def step_ms(self, prompt):
+        """The cached step between two HIP events (process excluded) -> (ms, last-row logits)."""
+        ids, pos, _, cache = self.eng.process(prompt)
+        ii, pp = torch.tensor([ids], device="cuda:0"), torch.tensor([pos], device="cuda:0")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        out = self.lm(input_ids=ii, position_ids=pp, past_key_values=cache, use_cache=True)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out.logits[0, -1].float().clone()
+
+    def lookup_step_ms(self, S, k, n_new):
+        """Median ms of one LookupSlotLoop replay at S slots (S * (k + 1) rows), an empty corpus: every step verifies k drafts
+        per slot only where the output repeats itself."""
+        pasts, firsts, p0s = [], [], []
+        for j in range(S):
+            ids, pos, _, cache = self.eng.process(self.prompt, slot=j)
+            out = self.lm(input_ids=torch.tensor([ids]), position_ids=torch.tensor([pos]), past_key_values=cache, use_cache=True)
+            pasts.append(out.past_key_values)
+            firsts.append(int(out.logits[0, -1].argmax()))
+            p0s.append(max(pos) + 2)
+        loop = self.lm.hf_model.lookup_slot_loop(pasts, firsts, p0s, n_new, k, [[]] * S)
+        assert loop is not None
+        got, i = [0] * S, 0
+        while min(got) < n_new:
+            if loop.n <= i:
+                loop.enqueue()
+            for j in range(S):
+                got[j] += len(loop.tokens(j, i))
+            i += 1
+        ms = [loop.elapsed_ms(j) for j in range(i)]
+        loop.close([n_new] * S)
+        return statistics.median(ms)
+
+
+def rows_mode(args):
+    names = [args.only] if args.only else ["mxfp4", "mxfp4_fp16_images"]
+    legs = [Leg(n, {"PC_W4_MAX_ROWS": "64"}) for n in names]
+    n_new = min(args.new, 24)
+    prompts = {leg.name: {r: leg.question(r) for r in ROW_COUNTS} for leg in legs}
+    keys = [f"step{r}_ms" for r in ROW_COUNTS] + [f"lookup_S{S}_k{k}_step_ms" for S, k in LOOKUP_CASES]
+
+    def once(leg, r, logits):
+        for rows in ROW_COUNTS:
+            ms, lg = leg.step_ms(prompts[leg.name][rows])
+            logits[(leg.name, rows)] = lg
+            if r is not None:
+                r[f"step{rows}_ms"].append(ms)
+        for S, k in LOOKUP_CASES:
+            ms = leg.lookup_step_ms(S, k, n_new)
+            if r is not None:
+                r[f"lookup_S{S}_k{k}_step_ms"].append(ms)
+    logits = {}
+    for leg in legs:                                   # warm: graphs captured, code objects loaded
+        for _ in range(2):
+            once(leg, None, logits)
+    repeats = 3 if args.only else args.repeats
+    rec = {leg.name: {k: [] for k in keys} for leg in legs}
+    for rep in range(repeats):
+        for leg in legs[rep % len(legs):] + legs[:rep % len(legs)]:
+            once(leg, rec[leg.name], logits)
+    result = {"shape": "llama2-7b (random init)", "prompt": "persona schema, questions of %s new rows; slot lookup at %s (slots, k), empty corpus"
+              % (list(ROW_COUNTS), list(LOOKUP_CASES)),
+              "how": f"{repeats} interleaved repetitions, leg order rotating; HIP events around the forward / one replay; median, min, "
+                     "max, spread = (max - min) / median; PC_W4_MAX_ROWS=64 in both legs",
+              "legs": {leg.name: {k: summary(v) for k, v in rec[leg.name].items()} for leg in legs}}
+    if len(legs) == 2:
+        b, c = result["legs"]["mxfp4"], result["legs"]["mxfp4_fp16_images"]
+        cond = {}
+        for key in keys:
+            gain = (c[key]["median"] - b[key]["median"]) / c[key]["median"]
+            cond[key] = {"b_median": b[key]["median"], "c_median": c[key]["median"], "gain": round(gain, 4),
+                         "c_spread": c[key]["spread"], "met": bool(gain > c[key]["spread"])}
+        result["condition_b_faster_than_c_by_more_than_c_spread"] = cond
+        rows_of = {f"step{r}_ms": r for r in ROW_COUNTS}
+        rows_of.update({f"lookup_S{S}_k{k}_step_ms": S * (k + 1) for S, k in LOOKUP_CASES})
+        default = 16
+        for cand in (32, 48, 64):
+            if all(cond[key]["met"] for key, r in rows_of.items() if r <= cand):
+                default = cand
+            else:
+                break
+        result["implied_default_PC_W4_MAX_ROWS"] = default
+        result["max_dlogit_b_vs_c"] = {str(r): float((logits[("mxfp4", r)] - logits[("mxfp4_fp16_images", r)]).abs().max()) for r in ROW_COUNTS}
+    line = json.dumps(result)
+    if args.out and not args.only:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def summary(vals, nd=3):
     vals = [v for v in vals if v is not None]
     if not vals:
@@ -139,9 +254,14 @@ def main():
     ap.add_argument("--new", type=int, default=48, help="greedy tokens per sequence")
     ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--only", default=None, help="one leg's cached step and decode loop alone (warm + 3 repetitions), no JSON file")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "w4_bench.json"))
+    ap.add_argument("--rows", action="store_true", help="the 17..64-row steps: legs (b) and (c) with PC_W4_MAX_ROWS=64")
+    ap.add_argument("--out", default=None, help="default profiles/w4_bench.json (--rows: profiles/w4_rows_bench.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "w4_rows_bench.json" if args.rows else "w4_bench.json")
     assert torch.cuda.is_available(), "w4_bench measures on the GPU"
+    if args.rows:
+        return rows_mode(args)
     params = GenerationParameters(temperature=0.0, max_new_tokens=args.new, stop_token_ids=[], stop_str=[])
     if args.only:
         leg = Leg(args.only)
