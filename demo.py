@@ -55,15 +55,19 @@ def main():
     ap.add_argument("--weights", choices=("fp16", "mxfp4"), default=None,
                     help="decoder weight format (default: PC_WEIGHTS, else fp16); mxfp4 = OCP MX 4-bit blocks, Llama family: the "
                          "cached step and decode stream 4.25 bits per weight")
+    ap.add_argument("--drop-fp16", action="store_true",
+                    help="with --weights mxfp4: keep only the 4-bit images of the decoder weights resident (keep_fp16=False; default: "
+                         "PC_W4_KEEP_FP16); passes above 64 rows expand each projection just in time")
     a = ap.parse_args()
+    wkw = dict(weight_format=a.weights, **(dict(keep_fp16=False) if a.drop_fp16 else {}))
 
     if os.path.isdir(a.model):
         import json
         arch = json.load(open(os.path.join(a.model, "config.json"))).get("model_type", "llama")
-        lm = {"falcon": Falcon, "mpt": Mpt}.get(arch, Llama2)(a.model, weight_format=a.weights)
+        lm = {"falcon": Falcon, "mpt": Mpt}.get(arch, Llama2)(a.model, **wkw)
     else:
         cls, shape = ADAPTERS[a.model]
-        lm = cls(shape, random_init=True, weight_format=a.weights)
+        lm = cls(shape, random_init=True, **wkw)
     preproc = [lm.get_formatter()]
     cache_engine = CacheEngine(a.max_ctx, lm, module_kv=a.module_kv, slots=max(1, a.batch))
     gen_engine = GenerationEngine(lm, lookup=a.lookup, lookup_sampled=a.lookup_sampled)

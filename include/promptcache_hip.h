@@ -439,6 +439,26 @@ typedef struct pc_gemm_w4_rows_args {
     float* y; int64_t ldy; void* of_hi; void* of_lo;
 } pc_gemm_w4_rows_args;
 int pc_gemm_w4_rows(const pc_gemm_w4_rows_args* args, void* stream);
+/* pc_w4_expand -- the fp16 weight W' from the two MXFP4 images of pc_gemm_w4 (csrc/pc_w4_expand.hip), exact: every grid value
+ *   times 2^(byte - 127) with the byte in [114, 140] is an fp16 normal or zero.  A scale byte outside 114..140 is OUT OF
+ *   CONTRACT (the quantiser never emits one; the result would round, overflow or go subnormal).  Needs N % 16 == 0, K % 128 == 0;
+ *   codes, scales and out 16-byte aligned.
+ *   layout     PC_W4_EXPAND_FRAG: out = the fragment image [N/16][K/32][64][8] of _native.to_weight_frags (what pc_gemm
+ *              streams); ld_out is ignored.  PC_W4_EXPAND_ROWMAJOR: out = [N][ld_out] fp16 with ld_out >= K, ld_out % 8 == 0
+ *              (what pc_gemm_dense reads); columns at and behind K are not written.
+ *   row_perm   optional device int32[N] (NULL = identity): output row r holds source row row_perm[r] (the q|k|v fragment image
+ *              is kept in qkv_rope_row_perm order).  An index outside [0, N) is out of contract. */
+#define PC_W4_EXPAND_FRAG 0
+#define PC_W4_EXPAND_ROWMAJOR 1
+typedef struct pc_w4_expand_args {
+    uint32_t struct_bytes;
+    int32_t layout;
+    int32_t N, K;
+    const void* codes; const void* scales;
+    const int32_t* row_perm;
+    void* out; int64_t ld_out;
+} pc_w4_expand_args;
+int pc_w4_expand(const pc_w4_expand_args* args, void* stream);
 /* pc_rmsnorm_frag -- LlamaRMSNorm (llama2.py:103-108) on the fp32 residual stream, output as fragment planes;
  *   optional prologue x += slabs[0] + ... + slabs[nslabs-1] (each [rows][hidden], the residual adds of
  *   llama2.py:638 / :644 fed by a K-sliced pc_gemm), written back to x in place. */

@@ -95,16 +95,16 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const void* __restrict__ x
 }
 
 // gate_up: [rows][2*inter] (gate columns first, then up), fp32 or fp16 -> out[rows][inter] = silu(gate) * up,
-// fp32 math, one fp16 rounding.
-template <bool F32>
+// fp32 math, one fp16 rounding.  The input type is a launch argument (one kernel for both: the branch around the loads is
+// uniform over the grid; the arithmetic and the stores do not depend on it).
 __global__ __launch_bounds__(256) void silu_mul_kernel(const void* __restrict__ gu, _Float16* __restrict__ out,
-                                                       int inter, const float* __restrict__ gu2 = nullptr,
+                                                       int inter, int in_f32, const float* __restrict__ gu2 = nullptr,
                                                        _Float16* __restrict__ out_lo = nullptr) {
     const int row = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i * 8 >= inter) return;
     float gt[8], up[8];
-    if (F32) {
+    if (in_f32) {
         const float* g = (const float*)gu + (int64_t)row * 2 * inter + i * 8;
         const f4 a = *(const f4*)g, b = *(const f4*)(g + 4), c = *(const f4*)(g + inter), d = *(const f4*)(g + inter + 4);
 #pragma unroll
@@ -330,8 +330,8 @@ PC_EXPORT int pc_silu_mul_split(const float* gate_up, const float* gate_up2, voi
     if (rows == 0) return PC_OK;
     PC_REQUIRE(gate_up && out_hi && out_lo, PC_ERR_ARG, "pc_silu_mul_split: null pointer");
     dim3 grid(pc_ceil_div(inter / 8, 256), rows);
-    hipLaunchKernelGGL(silu_mul_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const void*)gate_up, (_Float16*)out_hi,
-                       inter, gate_up2, (_Float16*)out_lo);
+    hipLaunchKernelGGL(silu_mul_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const void*)gate_up, (_Float16*)out_hi,
+                       inter, 1, gate_up2, (_Float16*)out_lo);
     return pc_check_launch("silu_mul_kernel");
 }
 
@@ -349,10 +349,8 @@ PC_EXPORT int pc_silu_mul(const void* gate_up, void* out, int32_t rows, int32_t 
     if (rows == 0) return PC_OK;
     PC_REQUIRE(gate_up && out, PC_ERR_ARG, "pc_silu_mul: null pointer");
     dim3 grid(pc_ceil_div(inter / 8, 256), rows);
-    if (in_is_f32)
-        hipLaunchKernelGGL(silu_mul_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, gate_up, (_Float16*)out, inter);
-    else
-        hipLaunchKernelGGL(silu_mul_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, gate_up, (_Float16*)out, inter);
+    hipLaunchKernelGGL(silu_mul_kernel, grid, dim3(256), 0, (hipStream_t)stream, gate_up, (_Float16*)out, inter,
+                       in_is_f32 ? 1 : 0, (const float*)nullptr, (_Float16*)nullptr);
     return pc_check_launch("silu_mul_kernel");
 }
 

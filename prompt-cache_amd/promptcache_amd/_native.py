@@ -154,12 +154,21 @@ class GemmW4RowsArgs(C.Structure):
                 ("y", _vp), ("ldy", _i64), ("of_hi", _vp), ("of_lo", _vp)]
 
 
+class W4ExpandArgs(C.Structure):
+    """``pc_w4_expand_args`` of include/promptcache_hip.h (field for field)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("layout", _i32), ("N", _i32), ("K", _i32),
+                ("codes", _vp), ("scales", _vp), ("row_perm", _vp), ("out", _vp), ("ld_out", _i64)]
+
+
+W4_EXPAND_FRAG, W4_EXPAND_ROWMAJOR = 0, 1
+
 # name ->(restype, argtypes); mirrors include/promptcache_hip.h one to one
 SIGNATURES = {
     "pc_attn": (C.c_int, [C.POINTER(AttnArgs), _vp]),
     "pc_gemm": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "pc_gemm_w4": (C.c_int, [C.POINTER(GemmW4Args), _vp]),
     "pc_gemm_w4_rows": (C.c_int, [C.POINTER(GemmW4RowsArgs), _vp]),
+    "pc_w4_expand": (C.c_int, [C.POINTER(W4ExpandArgs), _vp]),
     "pc_gemm_q8": (C.c_int, [C.POINTER(GemmQ8Args), _vp]),
     "pc_gemm_part": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pc_dev_gemm_trace": (C.c_int, [_vp]),
@@ -714,6 +723,21 @@ def gemm_w4_rows(codes_img, scales_img, xf_hi, xf_lo, M: int, N: int, K: int, ep
             setattr(a, k, v.data_ptr())
     rc = load().pc_gemm_w4_rows(C.byref(a), current_stream() if stream is None else stream)
     check(rc, "pc_gemm_w4_rows")
+
+
+def w4_expand(codes_img, scales_img, out, N: int, K: int, layout: int = W4_EXPAND_FRAG, ld_out: int = 0, row_perm=None,
+              stream: Optional[int] = None, struct_bytes: Optional[int] = None) -> None:
+    """One ``pc_w4_expand`` call: the fp16 weight ``W'`` of the images of ``to_weight_frags_w4`` into ``out``, as the fragment
+    image of ``to_weight_frags`` or row-major ``[N][ld_out]``; ``row_perm`` (device int32 ``[N]``): output row r = source row
+    ``row_perm[r]``.  Tensors or raw addresses (ints) are taken for the four pointers."""
+    a = W4ExpandArgs()
+    a.struct_bytes = C.sizeof(W4ExpandArgs) if struct_bytes is None else struct_bytes
+    a.layout, a.N, a.K, a.ld_out = layout, N, K, ld_out
+    for k, v in (("codes", codes_img), ("scales", scales_img), ("row_perm", row_perm), ("out", out)):
+        if v is not None:
+            setattr(a, k, (v if isinstance(v, int) else v.data_ptr()) or None)
+    rc = load().pc_w4_expand(C.byref(a), current_stream() if stream is None else stream)
+    check(rc, "pc_w4_expand")
 
 
 def to_act_frags(x):

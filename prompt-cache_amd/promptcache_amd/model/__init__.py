@@ -152,10 +152,12 @@ class _LlamaFamily(LanguageModel):
 
     def __init__(self, name: Optional[str] = None, device: str = "cuda:0", shape: Optional[LlamaShape] = None,
                  weights=None, tokenizer=None, random_init: bool = False, seed: int = 0, **_hf_kwargs):
-        from .llama_hip import LlamaHIP, check_weight_format
+        from .llama_hip import LlamaHIP, check_keep_fp16, check_weight_format
         from . import weights as W
 
         fmt, int8 = _weight_format(_hf_kwargs), bool(_hf_kwargs.get("load_in_8bit", False))
+        # keep_fp16=False (or PC_W4_KEEP_FP16=0): an MXFP4 model that keeps only the 4-bit images of its decoder linears
+        keep = check_keep_fp16(_hf_kwargs.get("keep_fp16"), fmt)       # (before any weight is read or drawn)
         name = name or self._default_name
         if weights is not None:                                       # caller-supplied tensors (tests)
             assert shape is not None, "pass shape= together with weights="
@@ -182,7 +184,7 @@ class _LlamaFamily(LanguageModel):
             tokenizer = StandInTokenizer(shape.vocab_size)
         # load_in_8bit (the reference's GPU configs, config/llm_config_*.json:5): weight-only int8 for the decoder linears
         # weight_format="mxfp4" (or PC_WEIGHTS=mxfp4): MXFP4 decoder linears, 4-bit images for the <= 16-row projections
-        model = LlamaHIP(shape, weights, device=device, int8_weights=int8, weight_format=fmt)
+        model = LlamaHIP(shape, weights, device=device, int8_weights=int8, weight_format=fmt, keep_fp16=keep)
         self.formatter = _llama_formatter()
         super().__init__(name, model, tokenizer, [tokenizer.eos_token_id], ["</s>"])
 

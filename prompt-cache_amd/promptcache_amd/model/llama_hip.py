@@ -966,6 +966,35 @@ def check_weight_format(weight_format: str, int8_weights: bool, shape=None, llam
                              f"image is four 32-feature MX blocks); {name} = {v}")
 
 
+def parse_keep_fp16(value) -> bool:
+    """``PC_W4_KEEP_FP16``: unset, empty or ``1`` keeps the fp16 images of an MXFP4 model's decoder linears, ``0`` drops them."""
+    if value is None or value in ("", "1"):
+        return True
+    if value == "0":
+        return False
+    raise ValueError(f"PC_W4_KEEP_FP16 must be 0 or 1, not {value!r}")
+
+
+def check_keep_fp16(keep_fp16, weight_format: str, env=None) -> bool:
+    """The ``keep_fp16`` a model runs with: the argument, else ``PC_W4_KEEP_FP16`` for an MXFP4 model, else True.  ``ValueError``
+    for a combination in which dropping the fp16 images leaves a path without weights -- raised before anything is allocated."""
+    env = os.environ if env is None else env
+    if keep_fp16 is None:
+        keep_fp16 = parse_keep_fp16(env.get("PC_W4_KEEP_FP16")) if weight_format == "mxfp4" else True
+    if keep_fp16:
+        return True
+    if weight_format != "mxfp4":
+        raise ValueError(f"keep_fp16=False needs weight_format='mxfp4' (the fp16 images are all a weight_format={weight_format!r} "
+                         "model has)")
+    if env.get("PC_W4_STREAM", "1") == "0":
+        raise ValueError("keep_fp16=False and PC_W4_STREAM=0 exclude each other: PC_W4_STREAM=0 builds no 4-bit images, so nothing "
+                         "would be left to expand")
+    if env.get("PC_DENSE_LO8", "0") == "1":
+        raise ValueError("keep_fp16=False and PC_DENSE_LO8=1 exclude each other: the int8 residual-plane GEMM keeps int8 images of the "
+                         "fp16 weights")
+    return False
+
+
 # weight_format="mxfp4": most rows of a step that streams the 4-bit images (PC_W4_MAX_ROWS, clamped to 16..64).  64: at 17, 32, 48
 # and 64 rows the 4-bit images beat the fp16 images of W' by more than the latter's own spread (DESIGN 3.25)
 W4_MAX_ROWS_DEFAULT = "64"
@@ -1070,6 +1099,7 @@ class LlamaHIP:
         self.llm_int8 = False
         self.weight_format, self.w4, self.w4_stream = "fp16", False, False    # MXFP4 decoder weights (LlamaHIP.__init__)
         self.w4_max_rows = 16
+        self.keep_fp16, self._w16_scratch = True, None                       # MXFP4 without fp16 images (LlamaHIP.__init__, _w16)
         self._last_qt = None
         self.batch_invariant = True         # a row's result does not depend on the other rows of the forward (see llm_int8)
         self.tail_supported = True  # a subclass whose layer loops do not thread `_tail_for` through must switch this off
@@ -1096,7 +1126,8 @@ class LlamaHIP:
         return bool(self._shared_prefix_loop and self.precise_dense and not self.llm_int8)
 
     def __init__(self, shape: LlamaShape, weights: Dict[str, torch.Tensor], device="cuda:0",
-                 decode_headroom: int = 256, skinny: bool = True, int8_weights: bool = False, weight_format: str = "fp16"):
+                 decode_headroom: int = 256, skinny: bool = True, int8_weights: bool = False, weight_format: str = "fp16",
+                 keep_fp16: Optional[bool] = None):
         """``int8_weights`` (the adapters' ``load_in_8bit=True``): the decoder-layer linears are quantised row-wise to
         int8 (``_native.quantize_rows_int8``); passes of <= 64 rows stream the int8 fragment images (half the bytes, exact
         arithmetic on the dequantised values); longer passes run hipBLASLt on the int8 codes held in fp16 (exact) and
@@ -1107,8 +1138,14 @@ class LlamaHIP:
         for every path above 16 rows and, next to them, the two 4-bit images the <= 16-row projections stream (``pc_gemm_w4``:
         the cached step, decode, the device loops).  ``PC_W4_MAX_ROWS`` (16..64) extends the images to the steps of 17 rows up
         to it (``pc_gemm_w4_rows``: a cached step with a longer question, the slot-lookup verify step).  ``PC_W4_STREAM=0`` runs
-        the fp16 images of ``W'`` everywhere."""
+        the fp16 images of ``W'`` everywhere.
+
+        ``keep_fp16=False`` (``None``: ``PC_W4_KEEP_FP16=0``; MXFP4 only): the layers keep the two 4-bit images and NO fp16 image of
+        ``W'``.  Steps of at most ``PC_W4_MAX_ROWS`` rows never needed one; every other projection launch is preceded by a
+        ``pc_w4_expand`` of its weight into the model's one scratch buffer (``_w16``) -- exact, so every forward is bit-identical
+        to the ``keep_fp16=True`` model's.  The embeddings, the norms and both lm_head images stay fp16."""
         check_weight_format(weight_format, int8_weights, shape)     # (before anything is allocated)
+        keep_fp16 = check_keep_fp16(keep_fp16, weight_format)
         self._setup(shape, device, decode_headroom)
         c = shape
         self.H, self.Hkv, self.D, self.L = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.num_hidden_layers
@@ -1178,6 +1215,17 @@ class LlamaHIP:
             self.use_chain = False
             self.defer_merge = False
             self.ks_o = self.ks_down = None
+        self.keep_fp16 = keep_fp16
+        if not keep_fp16:
+            if not self.w4_stream:
+                raise ValueError("keep_fp16=False needs the 4-bit images, which this shape does not tile (hidden, intermediate "
+                                 "% 32, vocab % 16): there would be nothing left to expand")
+            # ONE scratch for the expanded image of whichever projection runs next, sized for the largest (gate|up).  Allocated
+            # here, before any capture, and never resized: the captured 65..512-row graphs keep its address.  One buffer is
+            # enough because every forward of this class issues its launches on one stream, in order: a projection has read
+            # the scratch before the next expand overwrites it.
+            self._w16_scratch = torch.empty(max(2 * c.intermediate_size * c.hidden_size, (self.H + 2 * self.Hkv) * self.D * c.hidden_size,
+                                                c.hidden_size * self.H * self.D), dtype=self.dtype, device=dev)
 
         for i in range(self.L):
             wqkv = torch.cat([w(f"l{i}.wq"), w(f"l{i}.wk"), w(f"l{i}.wv")], dim=0).contiguous()
@@ -1194,6 +1242,13 @@ class LlamaHIP:
                 wqkv, wo, wgu, wdown = mx(wqkv, "wqkv"), mx(wo, "wo"), mx(wgu, "wgu"), mx(wdown, "wdown")
             if self.skinny and i == 0:
                 self._qkv_perm = _native.qkv_rope_row_perm(self.H + 2 * self.Hkv, self.D).to(dev)
+            if not keep_fp16:
+                # W' goes: the layer is its norms and the 4-bit images (every wX / wX_f / scale entry None)
+                del wqkv, wo, wgu, wdown
+                self.layers.append(dict(ln1=w(f"l{i}.ln1"), ln2=w(f"l{i}.ln2"), **w4,
+                                        **{key + sfx: None for key in ("wqkv", "wo", "wgu", "wdown")
+                                           for sfx in ("", "_f", "_s", "_ds", "_t8")}))
+                continue
             # q|k|v fragment image: rotary pairs share a 16-row tile (pc_gemm_qkv_rope)
             wqkv, wqkv_f, wqkv_s = prep(wqkv, self._qkv_perm if self.skinny else None); t_qkv = self._last_qt
             wo, wo_f, wo_s = prep(wo); t_o = self._last_qt
@@ -1221,16 +1276,33 @@ class LlamaHIP:
     # ------------------------------------------------------------------------------------------
     def dequantized_weights(self) -> Dict[str, torch.Tensor]:
         """name -> fp16 tensor of the weights this model computes with, under the names of the constructor's ``weights``: with
-        ``weight_format="mxfp4"`` the decoder linears are ``W' = dequant(quant(W))`` -- what an oracle of this model loads."""
+        ``weight_format="mxfp4"`` the decoder linears are ``W' = dequant(quant(W))`` -- what an oracle of this model loads
+        (``keep_fp16=False``: rebuilt here from the 4-bit images)."""
         if self.int8_weights:
             raise ValueError("dequantized_weights: not kept in int8 mode")
         HD, KD, inter = self.H * self.D, self.Hkv * self.D, self.config.intermediate_size
         out = {"embed": self.embed, "norm": self.norm, "lm_head": self.lm_head}
         for i, lw in enumerate(self.layers):
+            if not self.keep_fp16:
+                lw = dict(lw, **{key: _native.dequantize_mxfp4(*_native.from_weight_frags_w4(lw[key + "_c4"], lw[key + "_e4"]))
+                                 for key in ("wqkv", "wo", "wgu", "wdown")})
             out.update({f"l{i}.ln1": lw["ln1"], f"l{i}.ln2": lw["ln2"], f"l{i}.wq": lw["wqkv"][:HD],
                         f"l{i}.wk": lw["wqkv"][HD:HD + KD], f"l{i}.wv": lw["wqkv"][HD + KD:], f"l{i}.wo": lw["wo"],
                         f"l{i}.gate": lw["wgu"][:inter], f"l{i}.up": lw["wgu"][inter:], f"l{i}.down": lw["wdown"]})
         return out
+
+    def resident_tensors(self):
+        """The tensors this model holds, one per distinct storage: the attributes and every layer entry (weights and images, the
+        expand scratch, state words and whatever workspace a forward has left; not the captured graphs' private pools)."""
+        seen, out = set(), []
+        for t in list(vars(self).values()) + [v for lw in self.layers for v in lw.values()]:
+            if isinstance(t, torch.Tensor) and t.device.type == self.device.type and t.untyped_storage().data_ptr() not in seen:
+                seen.add(t.untyped_storage().data_ptr())
+                out.append(t)
+        return out
+
+    def resident_bytes(self) -> int:
+        return sum(t.untyped_storage().nbytes() for t in self.resident_tensors())
 
     def new_arena(self, batch: int, cap: int) -> KVArena:
         return KVArena(batch, self.L, self.Hkv, cap, self.D, self.device, self.dtype)
@@ -1450,6 +1522,22 @@ class LlamaHIP:
             return max(1, min(8 if T <= 128 else 6, 256 // (blocks * -(-N // 128))))
         return self.kslices
 
+    def _w16(self, lw: dict, key: str, frag: bool):
+        """The fp16 image of the decoder linear ``key`` of layer ``lw`` for the launch that follows: the fragment image of the
+        weight-streaming kernels (``frag``; q|k|v in ``_qkv_perm`` order) or the row-major one of pc_gemm_dense.  The resident
+        tensor when the model keeps one; ``keep_fp16=False``: ``pc_w4_expand`` of the 4-bit images into the model's scratch, on
+        the current stream -- so it is captured with a graph's launches -- and a view of the scratch, valid until the next call."""
+        if self.keep_fp16 or key + "_c4" not in lw:          # (lm_head goes through _proj with a dict of its own: always resident)
+            return lw[key + "_f" if frag else key]
+        ci, si = lw[key + "_c4"], lw[key + "_e4"]
+        N, K = 16 * ci.shape[0], 128 * ci.shape[1]
+        out = self._w16_scratch[:N * K]
+        if frag:
+            _native.w4_expand(ci, si, out, N, K, _native.W4_EXPAND_FRAG, row_perm=self._qkv_perm_i32 if key == "wqkv" else None)
+            return out.view(N // 16, K // 32, 4, 16, 8)
+        _native.w4_expand(ci, si, out, N, K, _native.W4_EXPAND_ROWMAJOR, ld_out=K)
+        return out.view(N, K)
+
     def _proj(self, a_hi, a_lo, lw: dict, key: str, M: int, N: int, K: int, epi: int, **out) -> None:
         """One many-row projection on the hand-written MFMA kernel (pc_gemm_dense.hip): ``(a_hi + a_lo) @ W^T`` with the
         epilogue fused.  int8 mode: ``lw[key]`` holds the int8 codes as fp16 (exact) and the per-output scales
@@ -1468,7 +1556,7 @@ class LlamaHIP:
             codes, sc = self._lo8_codes(a_lo, M, K)
             _native.gemm_dense_lo8(a_hi, codes, sc, lw[key], w8, lw[key + "_q8s"], M, N, K, epi, workspace=ws, **out)
             return
-        _native.gemm_dense(a_hi, a_lo, lw[key], M, N, K, epi, wscale=lw.get(key + "_ds"), workspace=ws, **out)
+        _native.gemm_dense(a_hi, a_lo, self._w16(lw, key, False), M, N, K, epi, wscale=lw.get(key + "_ds"), workspace=ws, **out)
 
     def _lo8_codes(self, a_lo, M: int, K: int):
         """Row-wise absmax int8 codes + scales of a residual activation plane (pc_quant_rows_i8)."""
@@ -1543,7 +1631,7 @@ class LlamaHIP:
                 if xlo is not None and self.dense_lo8 and lw.get("wqkv_q8") is not None:
                     codes, sc = self._lo8_codes(xlo, T, hid)
                     xlo, lo8 = None, (codes, sc, lw["wqkv_q8"], lw["wqkv_q8s"])
-                n.gemm_dense_qkv_rope(h2[0], xlo, lw["wqkv"], hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
+                n.gemm_dense_qkv_rope(h2[0], xlo, self._w16(lw, "wqkv", False), hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
                                       arena.head_stride, B, H, Hkv, D, q_len, past_len, arena.cap, kv_lo=kv_lo,
                                       past_lens=self._past_lens, lo8=lo8)
             else:
@@ -1879,7 +1967,7 @@ class LlamaHIP:
                               kp, vp, arena.batch_stride, arena.head_stride, cs, B, H, Hkv, D, q_len, past_len, arena.cap, True,
                               past_len_dev=past_dev, q_out_lo=q16l, kv_lo=kvlo)
             elif not qkv_done:
-                n.gemm_qkv_rope_norm(lw["wqkv_f"], x, lw["ln1"], eps, T, hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
+                n.gemm_qkv_rope_norm(self._w16(lw, "wqkv", True), x, lw["ln1"], eps, T, hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
                                      arena.head_stride, B, H, Hkv, D, q_len, past_len, arena.cap, past_dev,
                                      kv_lo=kvlo and kvlo[:4], wscale=lw["wqkv_s"], lo_base=lo_base, rows_dev=rows_dev)
             qkv_done = False
@@ -1917,19 +2005,19 @@ class LlamaHIP:
                 except RuntimeError:
                     chain = self.use_chain = False       # no instantiation for this shape: nothing was launched
             if ns > 1:
-                n.gemm_part(lw["wo_f"], ws, ws[H * ns * D:], ns, H, D, hid, x)
+                n.gemm_part(self._w16(lw, "wo", True), ws, ws[H * ns * D:], ns, H, D, hid, x)
             elif self.ks_o and lw["wo_s"] is None and self.ks_min_rows <= T <= 32 and (T <= 16 or (self.ks_o[1] <= 4 and self.ks_o[0] in (1, 2, 4))):   # (in-launch K reduction)
                 sc, ctr = self._ks_buffers(hid)
-                n.gemm_skinny_ks(lw["wo_f"], ah, al, T, hid, H * D, x, hid, self.ks_o[1], self.ks_o[0], sc, ctr, rows_dev=rows_dev)
+                n.gemm_skinny_ks(self._w16(lw, "wo", True), ah, al, T, hid, H * D, x, hid, self.ks_o[1], self.ks_o[0], sc, ctr, rows_dev=rows_dev)
             else:
-                n.gemm_skinny(lw["wo_f"], ah, al, T, hid, H * D, n.EPI_ADD, y=x, ldy=hid, wscale=lw["wo_s"], rows_dev=rows_dev)  # x += attn @ Wo^T
-            n.gemm_skinny_norm(lw["wgu_f"], x, lw["ln2"], eps, T, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl,
+                n.gemm_skinny(self._w16(lw, "wo", True), ah, al, T, hid, H * D, n.EPI_ADD, y=x, ldy=hid, wscale=lw["wo_s"], rows_dev=rows_dev)  # x += attn @ Wo^T
+            n.gemm_skinny_norm(self._w16(lw, "wgu", True), x, lw["ln2"], eps, T, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl,
                                wscale=lw["wgu_s"], rows_dev=rows_dev)
             if self.ks_down and lw["wdown_s"] is None and self.ks_min_rows <= T <= 32 and (T <= 16 or (self.ks_down[1] <= 4 and self.ks_down[0] in (1, 2, 4))) and inter >= 2 * hid:
                 sc, ctr = self._ks_buffers(hid)
-                n.gemm_skinny_ks(lw["wdown_f"], ch, cl, T, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr, rows_dev=rows_dev)
+                n.gemm_skinny_ks(self._w16(lw, "wdown", True), ch, cl, T, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr, rows_dev=rows_dev)
             else:
-                n.gemm_skinny(lw["wdown_f"], ch, cl, T, hid, inter, n.EPI_ADD, y=x, ldy=hid, wscale=lw["wdown_s"], rows_dev=rows_dev)  # x += act @ Wd^T
+                n.gemm_skinny(self._w16(lw, "wdown", True), ch, cl, T, hid, inter, n.EPI_ADD, y=x, ldy=hid, wscale=lw["wdown_s"], rows_dev=rows_dev)  # x += act @ Wd^T
         if last_token_only:
             xs = x.view(B, q_len, hid)[:, -1, :].contiguous()
             logits = torch.empty((B, V), dtype=torch.float32, device=self.device)
@@ -2506,7 +2594,7 @@ class LlamaHIP:
             if w4:
                 n.gemm_w4(lw["wqkv_c4"], lw["wqkv_e4"], S, W, hid, n.EPI_STORE, x=x, norm_weight=lw["ln1"], eps=eps, y=qkv, ldy=W)
             else:
-                n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+                n.gemm_skinny_norm(self._w16(lw, "wqkv", True), x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
             n.rope_append_slots(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D)
             if nsplit_trunk:
                 n.attn_decode_slots_trunk(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], st["leader"],
@@ -2519,13 +2607,13 @@ class LlamaHIP:
                 n.gemm_w4(lw["wgu_c4"], lw["wgu_e4"], S, 2 * inter, hid, n.EPI_SILU, x=x, norm_weight=lw["ln2"], eps=eps, of_hi=ch, of_lo=cl)
                 n.gemm_w4(lw["wdown_c4"], lw["wdown_e4"], S, hid, inter, n.EPI_ADD, xf_hi=ch, xf_lo=cl, y=x, ldy=hid)
                 continue
-            n.gemm_skinny(lw["wo_f"], ah, al, S, hid, H * D, n.EPI_ADD, y=x, ldy=hid)                  # x += attn @ Wo^T
-            n.gemm_skinny_norm(lw["wgu_f"], x, lw["ln2"], eps, S, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+            n.gemm_skinny(self._w16(lw, "wo", True), ah, al, S, hid, H * D, n.EPI_ADD, y=x, ldy=hid)                  # x += attn @ Wo^T
+            n.gemm_skinny_norm(self._w16(lw, "wgu", True), x, lw["ln2"], eps, S, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
             if ks_down:
                 sc, ctr = self._ks_buffers(hid)
-                n.gemm_skinny_ks(lw["wdown_f"], ch, cl, S, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr)
+                n.gemm_skinny_ks(self._w16(lw, "wdown", True), ch, cl, S, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr)
             else:
-                n.gemm_skinny(lw["wdown_f"], ch, cl, S, hid, inter, n.EPI_ADD, y=x, ldy=hid)           # x += act @ Wd^T
+                n.gemm_skinny(self._w16(lw, "wdown", True), ch, cl, S, hid, inter, n.EPI_ADD, y=x, ldy=hid)           # x += act @ Wd^T
         n.gemm_skinny_norm(self.lm_head_f, x, self.norm, eps, S, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
         if each:
             n.sample_advance_slots_each(st["logits"], V, V, st["params_each"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
@@ -2685,15 +2773,15 @@ class LlamaHIP:
                     n.gemm_w4(lw["wgu_c4"], lw["wgu_e4"], R, 2 * inter, hid, n.EPI_SILU, x=x, norm_weight=lw["ln2"], eps=eps, of_hi=ch, of_lo=cl)
                     n.gemm_w4(lw["wdown_c4"], lw["wdown_e4"], R, hid, inter, n.EPI_ADD, xf_hi=ch, xf_lo=cl, y=x, ldy=hid)
                     continue
-                n.gemm_skinny_norm(lw["wqkv_f"], x, lw["ln1"], eps, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+                n.gemm_skinny_norm(self._w16(lw, "wqkv", True), x, lw["ln1"], eps, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
                 attend(li)
-                n.gemm_skinny(lw["wo_f"], ah, al, R, hid, H * D, n.EPI_ADD, y=x, ldy=hid)
-                n.gemm_skinny_norm(lw["wgu_f"], x, lw["ln2"], eps, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+                n.gemm_skinny(self._w16(lw, "wo", True), ah, al, R, hid, H * D, n.EPI_ADD, y=x, ldy=hid)
+                n.gemm_skinny_norm(self._w16(lw, "wgu", True), x, lw["ln2"], eps, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
                 if ks_down:
                     sc, ctr = self._ks_buffers(hid)
-                    n.gemm_skinny_ks(lw["wdown_f"], ch, cl, R, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr)
+                    n.gemm_skinny_ks(self._w16(lw, "wdown", True), ch, cl, R, hid, inter, x, hid, self.ks_down[1], self.ks_down[0], sc, ctr)
                 else:
-                    n.gemm_skinny(lw["wdown_f"], ch, cl, R, hid, inter, n.EPI_ADD, y=x, ldy=hid)
+                    n.gemm_skinny(self._w16(lw, "wdown", True), ch, cl, R, hid, inter, n.EPI_ADD, y=x, ldy=hid)
             n.gemm_skinny_norm(self.lm_head_f, x, self.norm, eps, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
         else:
             xh, xl = planes(hid)
@@ -2711,12 +2799,12 @@ class LlamaHIP:
                     n.gemm_w4_rows(lw["wgu_c4"], lw["wgu_e4"], xh, xl, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
                     n.gemm_w4_rows(lw["wdown_c4"], lw["wdown_e4"], ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
                     continue
-                n.gemm_skinny(lw["wqkv_f"], xh, xl, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
+                n.gemm_skinny(self._w16(lw, "wqkv", True), xh, xl, R, W, hid, n.EPI_STORE, y=qkv, ldy=W)
                 attend(li)
-                n.gemm_skinny(lw["wo_f"], ah, al, R, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                n.gemm_skinny(self._w16(lw, "wo", True), ah, al, R, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
                 n.rmsnorm_frag(x, lw["ln2"], xh, xl, R, hid, eps, slabs, KQ)
-                n.gemm_skinny(lw["wgu_f"], xh, xl, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
-                n.gemm_skinny(lw["wdown_f"], ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
+                n.gemm_skinny(self._w16(lw, "wgu", True), xh, xl, R, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl)
+                n.gemm_skinny(self._w16(lw, "wdown", True), ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
             n.rmsnorm_frag(x, self.norm, xh, xl, R, hid, eps, slabs, pending)
             n.gemm_skinny(self.lm_head_f, xh, xl, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
         if each:                      # the sampler on every row, per slot
@@ -2815,7 +2903,7 @@ class LlamaHIP:
                               past_len_dev=past_dev, q_out_lo=q16l, kv_lo=kvlo)
             else:
                 # q|k|v projection + RoPE + in-place KV append in one weight-streaming launch
-                n.gemm_qkv_rope(lw["wqkv_f"], xh, xl, T, hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
+                n.gemm_qkv_rope(self._w16(lw, "wqkv", True), xh, xl, T, hid, cs, q16, q16l, H * D, kp, vp, arena.batch_stride,
                                 arena.head_stride, B, H, Hkv, D, q_len, past_len, arena.cap, past_dev, kv_lo=kvlo and kvlo[:4],
                                 wscale=lw["wqkv_s"], lo_base=lo_base, kslices=QS, scratch=qkv_slabs)
             if self._kv_only and li == len(layers) - 1:
@@ -2832,15 +2920,15 @@ class LlamaHIP:
                 pending = KQ
                 continue
             mid_skip = self.mid_lo_skip if (T > self.SKINNY_MAX_ROWS and self._lo_mode != 3) else ()      # (precision audit: tools/plane_audit.py)
-            n.gemm_skinny(lw["wo_f"], ah, None if "o" in mid_skip else al, T, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ,
+            n.gemm_skinny(self._w16(lw, "wo", True), ah, None if "o" in mid_skip else al, T, hid, H * D, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ,
                           wscale=lw["wo_s"])                                                    # attn @ Wo^T
             n.rmsnorm_frag(x, lw["ln2"], xh, xl, T, hid, eps, slabs, KQ)                       # x += ...; norm
             # (an encode pass on this stack follows the many-row stack's plane policy: dense_lo_skip; PC_MID_LO_SKIP=gu extends it to
             # the long-question forward)
             gu_lo = None if (T > self.SKINNY_MAX_ROWS and ((self._lo_mode == 3 and "gu" in self.dense_lo_skip) or
                                                            (self._lo_mode != 3 and "gu" in self.mid_lo_skip))) else xl
-            n.gemm_skinny(lw["wgu_f"], xh, gu_lo, T, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl, wscale=lw["wgu_s"])  # silu(g)*u
-            n.gemm_skinny(lw["wdown_f"], ch, None if "down" in mid_skip else cl, T, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ,
+            n.gemm_skinny(self._w16(lw, "wgu", True), xh, gu_lo, T, 2 * inter, hid, n.EPI_SILU, of_hi=ch, of_lo=cl, wscale=lw["wgu_s"])  # silu(g)*u
+            n.gemm_skinny(self._w16(lw, "wdown", True), ch, None if "down" in mid_skip else cl, T, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ,
                           wscale=lw["wdown_s"])                                                 # act @ Wd^T
             pending = KQ
         V = c.vocab_size

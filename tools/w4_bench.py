@@ -25,6 +25,15 @@ than (c)'s own (max - min) / median.
 
     python tools/w4_bench.py --rows [--repeats 10] [--out profiles/w4_rows_bench.json]
     python tools/w4_bench.py --rows --only mxfp4     # leg (b)'s steps alone, for rocprofv3 --kernel-trace --stats
+
+``--resident``: keep_fp16=False against keep_fp16=True, two MXFP4 models in one process, the order of the two
+alternating between repetitions, every time from HIP events, median [min .. max]: resident bytes of both legs; pc_w4_expand alone
+on the four 7b projections in both layouts (us, read + written bytes/s) with kv_copy_kernel's rate from the same run next to it;
+the cached step at 12 / 40 / 64 rows and the one-row decode step (the dropped leg launches nothing new there: its median has to lie
+inside the kept leg's min .. max); the cached step at 130 / 258 rows, the no-cache persona prefill and the persona schema encode
+(the price of the mode, as a ratio to the kept leg).
+
+    python tools/w4_bench.py --resident [--repeats 10] [--out profiles/w4_resident_bench.json]
 """
 import argparse
 import json
@@ -45,7 +54,10 @@ LEGS = {
     "mxfp4": (dict(weight_format="mxfp4"), {"PC_W4_STREAM": "1"}),
     "mxfp4_fp16_images": (dict(weight_format="mxfp4"), {"PC_W4_STREAM": "0"}),
     "int8_weight_only": (dict(weight_format="fp16", load_in_8bit=True), {"PC_INT8_WEIGHT_ONLY": "1"}),
+    "mxfp4_keep_fp16": (dict(weight_format="mxfp4", keep_fp16=True), {"PC_W4_STREAM": "1"}),          # --resident
+    "mxfp4_drop_fp16": (dict(weight_format="mxfp4", keep_fp16=False), {"PC_W4_STREAM": "1"}),
 }
+RESIDENT_SMALL, RESIDENT_LARGE = (12, 40, 64), (130, 258)
 SLOTS = (4, 8, 16)
 ROW_COUNTS = (17, 32, 48, 64)
 LOOKUP_CASES = ((8, 3), (8, 7))
@@ -70,6 +82,7 @@ class Leg:
         os.environ.update(env)
         try:
             self.lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0, **kw)
+            self.resident_bytes = self.lm.hf_model.resident_bytes()        # (before any forward leaves a workspace behind)
         finally:
             for k, v in saved.items():
                 os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
@@ -77,7 +90,8 @@ class Leg:
         self.eng = CacheEngine(4096, self.lm, slots=max(SLOTS))
         fmt = self.lm.get_formatter()
         sp, pp = synth.persona_like()
-        self.eng.add_schema(fmt(sp))
+        self.schema_text = fmt(sp)
+        self.eng.add_schema(self.schema_text)
         self.prompt = Prompt(pp, [fmt])
         self.ge = GenerationEngine(self.lm)
 
@@ -183,6 +197,134 @@ class Leg:
         return statistics.median(ms)
 
 
+    # ---- keep_fp16=False against keep_fp16=True (--resident) ----
+    def nocache_ms(self):
+        """The persona prompt without the cache, between two HIP events -> (ms, rows)."""
+        ids, pos, _, cache = self.eng.process(self.prompt, no_cache=True)
+        ii, pp = torch.tensor([ids], device="cuda:0"), torch.tensor([pos], device="cuda:0")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        self.lm(input_ids=ii, position_ids=pp, past_key_values=cache, use_cache=True)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), len(ids)
+
+    def encode_tok_s(self):
+        """The persona schema encoded again (its module KV dropped first): module tokens stored per second between two HIP events."""
+        name = next(iter(self.eng.schemas))
+        self.eng.remove_schema(name)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        self.eng.add_schema(self.schema_text)
+        e1.record()
+        torch.cuda.synchronize()
+        toks = sum(len(c) for c in self.eng.schemas[name].cache_l1.values())
+        return toks / (1e-3 * e0.elapsed_time(e1))
+
+
+def _events_us(fn, inner):
+    """``inner`` back-to-back launches of ``fn`` between two HIP events -> us per launch."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(inner):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / inner
+
+
+def expand_micro(m, repeats, inner=10):
+    """pc_w4_expand alone on layer 0's four projections, both layouts, and kv_copy_kernel (pc_kv_gather of one 512-row segment
+    of the 7b geometry: 268 MB read, 268 MB written) in the same rotation."""
+    from promptcache_amd import _native as n
+    lw = m.layers[0]
+    cases = {}
+    for key in ("wqkv", "wo", "wgu", "wdown"):
+        ci, si = lw[key + "_c4"], lw[key + "_e4"]
+        N, K = 16 * ci.shape[0], 128 * ci.shape[1]
+        nbytes = N * K // 2 + N * K // 32 + 2 * N * K
+        out = m._w16_scratch
+        perm = m._qkv_perm_i32 if key == "wqkv" else None
+        cases[f"{key}_{N}x{K}_frag"] = (nbytes, lambda ci=ci, si=si, N=N, K=K, perm=perm: n.w4_expand(ci, si, out, N, K, n.W4_EXPAND_FRAG, row_perm=perm))
+        cases[f"{key}_{N}x{K}_rowmajor"] = (nbytes, lambda ci=ci, si=si, N=N, K=K: n.w4_expand(ci, si, out, N, K, n.W4_EXPAND_ROWMAJOR, ld_out=K))
+    L, Hkv, D, rows = m.L, m.Hkv, m.D, 512
+    src = torch.randn((L, 2, Hkv, rows, D), device="cuda:0").half()
+    dst = torch.empty((L, 2, Hkv, rows, D), dtype=torch.float16, device="cuda:0")
+    cases["kv_copy_kernel"] = (2 * src.numel() * 2, lambda: n.kv_gather([src.data_ptr()], [rows], [0], dst, L, Hkv, D, rows))
+    rec = {k: [] for k in cases}
+    for k, (_, fn) in cases.items():
+        _events_us(fn, 3)
+    names = list(cases)
+    for rep in range(repeats):
+        for k in names[rep % len(names):] + names[:rep % len(names)]:
+            rec[k].append(_events_us(cases[k][1], inner))
+    res = {}
+    for k, v in rec.items():
+        sm = summary(v)
+        sm["bytes"] = cases[k][0]
+        sm["GB_s"] = {"at_" + q: round(cases[k][0] / (1e-6 * sm[q]) / 1e9, 1) for q in ("median", "min", "max")}   # (of the TIME)
+        res[k] = sm
+    return res
+
+
+def resident_mode(args):
+    legs = []
+    names = ("mxfp4_keep_fp16", "mxfp4_drop_fp16")
+    for name in (names[::-1] if args.drop_first else names):       # (--drop-first: the models allocated in the other order)
+        legs.append(Leg(name, {"PC_W4_MAX_ROWS": "64"}))
+        print(f"[w4_bench] {name}: {legs[-1].resident_bytes / 1e9:.2f} GB resident", file=sys.stderr, flush=True)
+    legs.sort(key=lambda leg: names.index(leg.name))
+    prompts = {leg.name: {r: leg.question(r) for r in RESIDENT_SMALL + RESIDENT_LARGE} for leg in legs}
+    keys = [f"step{r}_ms" for r in RESIDENT_SMALL + RESIDENT_LARGE] + ["decode_step_ms", "nocache_prefill_ms", "encode_tok_s"]
+    info = {}
+
+    def once(leg, r):
+        for rows in RESIDENT_SMALL + RESIDENT_LARGE:
+            ms, lg = leg.step_ms(prompts[leg.name][rows])
+            info[(leg.name, rows)] = lg
+            if r is not None:
+                r[f"step{rows}_ms"].append(ms)
+        dm = leg.decode_step_ms(args.new)
+        ms, info["nocache_rows"] = leg.nocache_ms()
+        ts = leg.encode_tok_s()
+        if r is not None:
+            r["decode_step_ms"].append(dm); r["nocache_prefill_ms"].append(ms); r["encode_tok_s"].append(ts)
+    for leg in legs:                                   # warm: graphs captured, code objects loaded
+        for _ in range(2):
+            once(leg, None)
+    rec = {leg.name: {k: [] for k in keys} for leg in legs}
+    for rep in range(args.repeats):
+        for leg in (legs if rep % 2 == 0 else legs[::-1]):
+            once(leg, rec[leg.name])
+        print(f"[w4_bench] repetition {rep + 1} / {args.repeats}", file=sys.stderr, flush=True)
+    kept, drop = legs
+    result = {"shape": "llama2-7b (random init)",
+              "prompt": "persona schema; cached steps of %s new rows; no-cache prefill of %d rows" % (list(RESIDENT_SMALL + RESIDENT_LARGE), info["nocache_rows"]),
+              "built_first": "mxfp4_drop_fp16" if args.drop_first else "mxfp4_keep_fp16",
+              "how": f"{args.repeats} repetitions, the order of the two legs alternating; HIP events around every timed region; median, min, "
+                     "max, spread = (max - min) / median; PC_W4_MAX_ROWS=64 in both legs; encode_tok_s = module tokens stored / time of add_schema",
+              "legs": {leg.name: dict({k: summary(v, 1 if k.endswith("tok_s") else 3) for k, v in rec[leg.name].items()},
+                                      resident_bytes=leg.resident_bytes, weight_bytes=weight_bytes(leg.lm.hf_model)) for leg in legs},
+              "pc_w4_expand": expand_micro(drop.lm.hf_model, args.repeats)}
+    a, b = result["legs"][kept.name], result["legs"][drop.name]
+    result["resident_bytes_ratio_drop_over_keep"] = round(drop.resident_bytes / kept.resident_bytes, 4)
+    result["bit_equal_last_row_logits"] = {str(r): bool(torch.equal(info[(kept.name, r)], info[(drop.name, r)])) for r in RESIDENT_SMALL + RESIDENT_LARGE}
+    result["no_new_launch_steps_drop_median_inside_keep_min_max"] = {
+        k: {"drop_median": b[k]["median"], "keep_min": a[k]["min"], "keep_max": a[k]["max"],
+            "inside": bool(a[k]["min"] <= b[k]["median"] <= a[k]["max"])}
+        for k in [f"step{r}_ms" for r in RESIDENT_SMALL] + ["decode_step_ms"]}
+    result["cost_ratio_drop_over_keep"] = {k: round(b[k]["median"] / a[k]["median"], 4)
+                                           for k in [f"step{r}_ms" for r in RESIDENT_LARGE] + ["nocache_prefill_ms", "encode_tok_s"]}
+    line = json.dumps(result)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def rows_mode(args):
     names = [args.only] if args.only else ["mxfp4", "mxfp4_fp16_images"]
     legs = [Leg(n, {"PC_W4_MAX_ROWS": "64"}) for n in names]
@@ -252,14 +394,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--new", type=int, default=48, help="greedy tokens per sequence")
-    ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--legs", default=",".join(list(LEGS)[:4]))
     ap.add_argument("--only", default=None, help="one leg's cached step and decode loop alone (warm + 3 repetitions), no JSON file")
     ap.add_argument("--rows", action="store_true", help="the 17..64-row steps: legs (b) and (c) with PC_W4_MAX_ROWS=64")
-    ap.add_argument("--out", default=None, help="default profiles/w4_bench.json (--rows: profiles/w4_rows_bench.json)")
+    ap.add_argument("--resident", action="store_true", help="keep_fp16=False against keep_fp16=True (DESIGN 3.26)")
+    ap.add_argument("--drop-first", action="store_true", help="--resident: build the keep_fp16=False model first")
+    ap.add_argument("--out", default=None, help="default profiles/w4_bench.json (--rows: profiles/w4_rows_bench.json, "
+                                                "--resident: profiles/w4_resident_bench.json)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "w4_rows_bench.json" if args.rows else "w4_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "w4_resident_bench.json" if args.resident else
+                                "w4_rows_bench.json" if args.rows else "w4_bench.json")
     assert torch.cuda.is_available(), "w4_bench measures on the GPU"
+    if args.resident:
+        return resident_mode(args)
     if args.rows:
         return rows_mode(args)
     params = GenerationParameters(temperature=0.0, max_new_tokens=args.new, stop_token_ids=[], stop_str=[])
