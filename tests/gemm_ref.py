@@ -180,14 +180,21 @@ def split_floor(x, w):
     return ref, floor16
 
 
-def lost_lo_step(x, w, mode=np.median):
-    """max |error| when the lo plane of ONE k-step of ONE row is lost, reduced over all (row, k-step) choices by ``mode``."""
+def lost_lo_step(x, w, mode=np.median, depth=32):
+    """max |error| when the lo plane of ONE k-step of ONE row is lost, reduced over all (row, k-step) choices by ``mode``.
+    ``depth``: features per k-step (32: a k-step of the weight-streaming kernels; 16: one slab of the 32x32x16 MFMA of
+    pc_gemm_dense, where a K that is no multiple of it ends in a shorter slab -- zero-filled here as in the kernel)."""
     _, lo = split_planes(x)
     M, K = x.shape
-    lo3 = lo.astype(np.float64).reshape(M, K // 32, 32)
-    w3 = w.astype(np.float64).reshape(w.shape[0], K // 32, 32)
-    worst = np.empty((M, K // 32))
-    for s in range(K // 32):
+    steps = (K + depth - 1) // depth
+    lo3 = np.zeros((M, steps * depth))
+    lo3[:, :K] = lo
+    lo3 = lo3.reshape(M, steps, depth)
+    w3 = np.zeros((w.shape[0], steps * depth))
+    w3[:, :K] = w
+    w3 = w3.reshape(w.shape[0], steps, depth)
+    worst = np.empty((M, steps))
+    for s in range(steps):
         worst[:, s] = np.abs(lo3[:, s] @ w3[:, s].T).max(axis=1)
     return float(mode(worst))
 
