@@ -41,6 +41,10 @@ def main():
     ap.add_argument("--share-trunk", action="store_true",
                     help="with --batch: read the module rows the N prompts have in common once per step for all of them "
                          "(with --lookup K as well: once for all K + 1 draft rows of all of them)")
+    ap.add_argument("--slot-kv", choices=("fp16", "int8"), default=None,
+                    help="with --batch / --serve: what the batched loop's attention reads (default: PC_SLOT_KV, else fp16); int8 = "
+                         "int8 images of the slots' K/V rows, about half the bytes per step, the format's accuracy, and 0.516 of a "
+                         "slot buffer MORE memory per slot (the fp16 buffers stay); not with --share-trunk or --lookup")
     ap.add_argument("--serve", type=int, default=0,
                     help="serve N prompts with mixed max_new_tokens through --batch slots (continuous batching: a finished "
                          "sequence's slot takes the next prompt while the others keep decoding)")
@@ -103,18 +107,18 @@ def main():
             pk = Prompt(prompt_text[:cut] + f"<user>{synth.words(4 + k % 5, 4000 + k)}</user>" + prompt_text[cut:], preproc)
             ids, pos, _, cache = cache_engine.process(pk, return_full_position_ids=lm.use_full_position_ids, slot=k)
             reqs.append((ids, pos, cache))
-        batched, why = gen_engine.batch_plan(len(reqs), params)
+        batched, why = gen_engine.batch_plan(len(reqs), params, slot_kv=a.slot_kv)
         for _pass in ("warm", "timed"):              # (the first pass captures the batched step)
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2, share_trunk=a.share_trunk,
-                                                     lookup=a.lookup):
+                                                     lookup=a.lookup, slot_kv=a.slot_kv):
                 lasts[k] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
         n_tok = a.batch * a.max_new_tokens               # (fewer where a stop token or stop string ended a sequence early)
-        print(f"batch of {a.batch} ({'one device loop' if batched else 'one after another: ' + why}): up to {n_tok} tokens in "
+        print(f"batch of {a.batch} ({'one device loop' + (', int8 K/V images' if 'int8' in why else '') if batched else 'one after another: ' + why}): up to {n_tok} tokens in "
               f"{dt * 1e3:8.2f} ms, prefills included: {n_tok / dt:8.1f} tokens/s aggregate")
         print("Assistant[0]:", lasts[0].new_text[:120] + " ...")
     if a.serve:
@@ -127,12 +131,13 @@ def main():
             for r in range(a.serve):
                 pr = Prompt(prompt_text[:cut] + f"<user>{synth.words(4 + r % 5, 5000 + r)}</user>" + prompt_text[cut:], preproc)
                 yield pr, dataclasses.replace(params, max_new_tokens=budgets[r % len(budgets)])
-        batched, why = gen_engine.serve_plan(a.lookup or 0, cache_engine.slots)
+        batched, why = gen_engine.serve_plan(a.lookup or 0, cache_engine.slots, slot_kv=a.slot_kv)
         for _pass in ("warm", "timed"):
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk, lookup=a.lookup):
+            for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk, lookup=a.lookup,
+                                              slot_kv=a.slot_kv):
                 lasts[r] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

@@ -103,6 +103,13 @@ int pc_kv_slice_store(const void* src, int32_t src_cap, const int32_t* seg_src_o
  * pc_kv_quant_q8 -- what SchemaCache._process keeps of a stored slice, cache_engine.py:283-296 (there: fp16 tensors moved to
  *   the CPU): the fp16 segment store [n_planes][n_rows][head_dim] (pc_kv_slice_store's seg_dst) -> its image.
  *
+ * pc_kv_quant_q8_rows -- the same rows, cache_engine.py:283-296, out of a buffer whose planes lie further apart than the rows
+ *   that are kept: rows [0, n_rows) of every plane of src [n_planes][src_plane_rows][head_dim] (a staged batch-1 arena:
+ *   src_plane_rows = its capacity) -> rows [0, n_rows) of every plane of an image of dst_plane_rows rows per plane (codes
+ *   [n_planes][dst_plane_rows][head_dim], scales at byte n_planes*dst_plane_rows*head_dim).  Image rows at and behind n_rows are
+ *   not written.  The same kernel and the same bits as pc_kv_quant_q8, which is the case of both strides = n_rows.
+ *   n_rows > src_plane_rows or > dst_plane_rows, dst_plane_rows < 1 -> PC_ERR_ARG.
+ *
  * pc_kv_gather_q8 -- replaces PromptCache.update's copy loop, cache_engine.py:135-151, as pc_kv_gather does, for segments held
  *   as images: ONE launch over a segment table that writes dequantised fp16 rows into the staged buffer
  *   [n_layers][2][n_kv_heads][max_ctx][head_dim].
@@ -111,6 +118,8 @@ int pc_kv_slice_store(const void* src, int32_t src_cap, const int32_t* seg_src_o
  *   A segment with dst_row + len > max_ctx -> PC_ERR_BOUNDS (nothing is launched).
  * ------------------------------------------------------------------------------------------- */
 int pc_kv_quant_q8(const void* src, int32_t n_rows, int32_t n_planes, int32_t head_dim, void* dst_image, void* stream);
+int pc_kv_quant_q8_rows(const void* src, int32_t src_plane_rows, int32_t n_rows, int32_t n_planes, int32_t head_dim,
+                        void* dst_image, int32_t dst_plane_rows, void* stream);
 int pc_kv_gather_q8(const pc_kv_seg* segs, int32_t nseg, void* dst, int32_t n_layers, int32_t n_kv_heads, int32_t head_dim,
                     int32_t max_ctx, void* stream);
 
@@ -758,7 +767,22 @@ int pc_lookup_verify_sample(const float* logits, int64_t ldl, int32_t vocab, int
  * query rows = members x the kv head's query heads; `nsplit_trunk` shares of the trunk), an own launch does pc_attn_decode_slots'
  * arithmetic over the remaining keys in `nsplit_own` shares, and the merge takes nsplit_trunk + nsplit_own partials per (slot,
  * head) in key order.  A row's result depends on its own q, its keys, trunk and the two split counts only.  With leader = -1
- * everywhere the planes are bit-identical to pc_attn_decode_slots at nsplit = nsplit_own. */
+ * everywhere the planes are bit-identical to pc_attn_decode_slots at nsplit = nsplit_own.
+ *
+ * pc_attn_decode_slots_q8 -- llama2.py:366-400 as pc_attn_decode_slots replaces it, with the keys of a slot read from an int8
+ * image instead of its fp16 arena.  kvq_base (device, uint64[S]): per slot the 16-byte aligned address of ONE image in the
+ * pc_kv_quant_q8 layout at qcap rows per plane and P = n_layers * 2 * Hkv planes in the arena's plane order (codes
+ * [P][qcap][128], fp32 scales [P][qcap] at byte P*qcap*128 -- which is why the entry takes n_layers).  For a live slot, keys
+ * [0, len[b]) are image rows, an element being (float) code * scale in fp32 with no fp16 rounding; key len[b], the row
+ * pc_rope_append_slots just wrote, is read from the fp16 arena, exact.  The key axis is cut as pc_attn_decode_slots cuts it, the
+ * workspace (pc_attn_decode_slots_workspace_bytes), the partial records, the merge launch and the fragment planes are that
+ * entry's.  The workgroup that takes key len[b] also quantises that row (K and V of its kv head, the arithmetic of
+ * pc_kv_quant_q8, bit for bit) into image row len[b]; no other image row is written, and none of the launch reads that one.
+ * A slot's result depends on its own q, keys and nsplit only.  head_dim 128 only; a kv head with H / Hkv query heads is read
+ * once per query head.  Host contract: qcap >= cap[b] for every slot (a slot with len[b] >= qcap is left alone: neither its
+ * image nor its partials are touched and its output rows are undefined).  PC_ERR_ARG with nothing launched: head_dim != 128,
+ * H % Hkv != 0, a null pointer, S outside 1..16, qcap < 1, layer outside [0, n_layers), nsplit outside 1..32, a workspace that
+ * is too small. */
 int pc_rope_append_slots(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
                          const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live,
                          int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, void* stream);
@@ -767,6 +791,10 @@ int pc_attn_decode_slots(const void* q_hi, const void* q_lo, int64_t q_token_str
                          const int32_t* len, const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
                          float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
                          void* out_frag_lo, void* stream);
+int pc_attn_decode_slots_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base, const int32_t* cap,
+                            const int32_t* len, const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                            float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
+                            void* out_frag_lo, const uint64_t* kvq_base, int32_t qcap, int32_t n_layers, void* stream);
 int64_t pc_attn_decode_slots_trunk_workspace_bytes(int32_t S, int32_t H, int32_t D, int32_t nsplit_own, int32_t nsplit_trunk);
 int pc_attn_decode_slots_trunk(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
                                const int32_t* cap, const int32_t* len, const int32_t* live, const int32_t* leader,

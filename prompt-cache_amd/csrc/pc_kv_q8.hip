@@ -3,7 +3,9 @@
 //
 // Replaces  PromptCache.update      promptcache/cache_engine.py:135-151  (pc_kv_gather_q8: the copy loop, with the module KV
 //                                                                         held at 0.516 of its fp16 bytes)
-//           SchemaCache._process    promptcache/cache_engine.py:283-296  (pc_kv_quant_q8: what is kept of a stored slice)
+//           SchemaCache._process    promptcache/cache_engine.py:283-296  (pc_kv_quant_q8: what is kept of a stored slice;
+//                                                                         pc_kv_quant_q8_rows: the same rows out of an arena
+//                                                                         whose planes are `cap` rows apart)
 //
 // Image of one segment of n rows, P = n_layers * 2 * n_kv_heads planes, head dim D -- ONE contiguous byte run:
 //   int8  codes [P][n][D]      plane p = (layer * 2 + k|v) * n_kv_heads + head      (the fp16 store's plane order)
@@ -32,6 +34,7 @@
 // the lines in L2 (kv_copy_kernel measured non-temporal stores slower inside the real step for the same reason).  The 1-token
 // segments between PML tags cost nothing special: their 2048 flat rows are four workgroups.
 #include "pc_common.h"
+#include "pc_kv_q8_quant.h"
 
 namespace {
 
@@ -119,18 +122,27 @@ __global__ __launch_bounds__(kQ8Threads) void kv_gather_q8_kernel(const Q8Gather
 }
 
 // ---- quantiser: one lane per 16 values (two 16-byte loads, one 16-byte code store), a row's D/16 lanes reduce its maximum with
-// cross-lane swaps; rows are numbered over the whole segment (plane-major on both sides, so the kernel never sees planes)
+// cross-lane swaps (pcq::quant_row16); rows are numbered plane-major over the n_rows quantised rows of every plane, g = p * n_rows
+// + r.  Source planes lie src_plane_rows rows apart and image planes dst_plane_rows (pc_kv_quant_q8_rows: an arena of `cap` rows
+// into an image of `qcap`); with both equal to n_rows (pc_kv_quant_q8) row g is row g on both sides and nothing is divided.
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-__global__ __launch_bounds__(kQ8Threads) void kv_quant_q8_kernel(const _Float16* __restrict__ src, int64_t total_rows, int head_dim,
+__global__ __launch_bounds__(kQ8Threads) void kv_quant_q8_kernel(const _Float16* __restrict__ src, int64_t total_rows, int n_rows,
+                                                                 int64_t src_plane_rows, int64_t dst_plane_rows, int head_dim,
                                                                  int lg_cpr, int8_t* __restrict__ codes, float* __restrict__ scale) {
     const int lg = lg_cpr;
     const int64_t row = ((int64_t)blockIdx.x * kQ8Threads + threadIdx.x) >> lg;
     const int j = threadIdx.x & ((1 << lg) - 1);
     const bool live = row < total_rows;                     // (whole rows drop out together: a row's lanes share one wave)
+    int64_t srow = row, drow = row;
+    if (src_plane_rows != n_rows || dst_plane_rows != n_rows) {   // (uniform over the grid)
+        const int64_t p = row / n_rows, r = row - p * n_rows;
+        srow = p * src_plane_rows + r;
+        drow = p * dst_plane_rows + r;
+    }
     float x[16];
     if (live) {
-        const h8* p = (const h8*)(src + row * head_dim + j * 16);
+        const h8* p = (const h8*)(src + srow * head_dim + j * 16);
         const h8 a0 = p[0], a1 = p[1];
 #pragma unroll
         for (int i = 0; i < 8; ++i) { x[i] = (float)a0[i]; x[8 + i] = (float)a1[i]; }
@@ -138,35 +150,12 @@ __global__ __launch_bounds__(kQ8Threads) void kv_quant_q8_kernel(const _Float16*
 #pragma unroll
         for (int i = 0; i < 16; ++i) x[i] = 0.0f;
     }
-    float s = 0.0f;
-    bool bad = false;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float ax = __builtin_fabsf(x[i]);
-        bad |= !(ax <= 65504.0f);                           // NaN or infinity (every finite fp16 is <= 65504)
-        s = (ax > s) ? ax : s;
-    }
-    for (int m = 1; m < (1 << lg); m <<= 1) {
-        const float o = __shfl_xor(s, m);
-        const int ob = __shfl_xor((int)bad, m);
-        s = (o > s) ? o : s;
-        bad |= ob != 0;
-    }
-    const float inv = (s > 0.0f && !bad) ? __fdiv_rn(127.0f, s) : 0.0f;
     uint32_t w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const float t = bad ? 0.0f : __builtin_rintf(__fmul_rn(x[q * 4 + b], inv));
-            acc |= ((uint32_t)(int)t & 0xffu) << (8 * b);
-        }
-        w[q] = acc;
-    }
+    float sc;
+    pcq::quant_row16(x, lg, w, sc);
     if (!live) return;
-    *(u32x4*)(codes + row * head_dim + j * 16) = u32x4{w[0], w[1], w[2], w[3]};
-    if (j == 0) scale[row] = bad ? __builtin_nanf("") : __fdiv_rn(s, 127.0f);
+    *(u32x4*)(codes + drow * head_dim + j * 16) = u32x4{w[0], w[1], w[2], w[3]};
+    if (j == 0) scale[drow] = sc;
 }
 
 int lg_lanes_per_row(int head_dim) {
@@ -177,6 +166,27 @@ int lg_lanes_per_row(int head_dim) {
 }
 
 }  // namespace
+
+PC_EXPORT int pc_kv_quant_q8_rows(const void* src, int32_t src_plane_rows, int32_t n_rows, int32_t n_planes, int32_t head_dim,
+                                  void* dst_image, int32_t dst_plane_rows, void* stream) {
+    PC_REQUIRE(n_rows >= 0 && n_planes > 0 && src_plane_rows >= n_rows && dst_plane_rows >= n_rows && dst_plane_rows >= 1, PC_ERR_ARG,
+               "pc_kv_quant_q8_rows: bad sizes (0 <= n_rows <= src_plane_rows, dst_plane_rows; dst_plane_rows >= 1)");
+    const int lg = lg_lanes_per_row(head_dim);
+    PC_REQUIRE(lg >= 0, PC_ERR_ARG, "pc_kv_quant_q8_rows: head_dim must be 32, 64 or 128");
+    if (n_rows == 0) return PC_OK;
+    PC_REQUIRE(src && dst_image, PC_ERR_ARG, "pc_kv_quant_q8_rows: null pointer");
+    PC_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst_image & 15) == 0, PC_ERR_ARG,
+               "pc_kv_quant_q8_rows: pointers must be 16-byte aligned");
+    const int64_t rows = (int64_t)n_planes * n_rows;
+    const int64_t lanes = rows << lg;
+    const int64_t blocks = (lanes + kQ8Threads - 1) / kQ8Threads;
+    PC_REQUIRE(blocks < (1ll << 31), PC_ERR_ARG, "pc_kv_quant_q8_rows: segment too long");
+    int8_t* codes = (int8_t*)dst_image;
+    float* scale = (float*)(codes + (int64_t)n_planes * dst_plane_rows * head_dim);
+    hipLaunchKernelGGL(kv_quant_q8_kernel, dim3((unsigned)blocks), dim3(kQ8Threads), 0, (hipStream_t)stream, (const _Float16*)src,
+                       rows, n_rows, (int64_t)src_plane_rows, (int64_t)dst_plane_rows, head_dim, lg, codes, scale);
+    return pc_check_launch("kv_quant_q8_kernel");
+}
 
 PC_EXPORT int pc_kv_quant_q8(const void* src, int32_t n_rows, int32_t n_planes, int32_t head_dim, void* dst_image, void* stream) {
     PC_REQUIRE(n_rows >= 0 && n_planes > 0, PC_ERR_ARG, "pc_kv_quant_q8: bad sizes");
@@ -192,7 +202,7 @@ PC_EXPORT int pc_kv_quant_q8(const void* src, int32_t n_rows, int32_t n_planes, 
     int8_t* codes = (int8_t*)dst_image;
     float* scale = (float*)(codes + rows * head_dim);
     hipLaunchKernelGGL(kv_quant_q8_kernel, dim3((unsigned)blocks), dim3(kQ8Threads), 0, (hipStream_t)stream, (const _Float16*)src,
-                       rows, head_dim, lg, codes, scale);
+                       rows, n_rows, (int64_t)n_rows, (int64_t)n_rows, head_dim, lg, codes, scale);   // both strides = n_rows
     return pc_check_launch("kv_quant_q8_kernel");
 }
 

@@ -38,10 +38,10 @@ __device__ __forceinline__ float wave_sum(float v) {
 // One workgroup (256 threads) per row; 8 elements (16 B of fp16 / 32 B of fp32) per lane per pass.
 // fp32 statistics and fp32 gain multiply, ONE fp16 rounding at the end.  (The reference casts the normalised
 // value back to the input dtype before the gain, llama2.py:108 -- a no-op on its fp32 CPU path, which is the
-// parity target, so rounding there would only add error.)
-template <bool XF32>
+// parity target, so rounding there would only add error.)  The input type is a launch argument, as silu_mul_kernel's: the
+// branches around the loads are uniform over the grid, and each type keeps its own expressions and stores.
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const void* __restrict__ xin, const _Float16* __restrict__ w,
-                                                      _Float16* __restrict__ out, int hidden, float eps,
+                                                      _Float16* __restrict__ out, int hidden, float eps, int XF32,
                                                       _Float16* __restrict__ out_lo = nullptr) {
     __shared__ float red[4];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -305,12 +305,8 @@ PC_EXPORT int pc_rmsnorm(const void* x, const void* weight, void* out, int32_t r
     PC_REQUIRE(rows >= 0 && hidden > 0 && hidden % 8 == 0, PC_ERR_ARG, "pc_rmsnorm: hidden must be a multiple of 8");
     if (rows == 0) return PC_OK;
     PC_REQUIRE(x && weight && out, PC_ERR_ARG, "pc_rmsnorm: null pointer");
-    if (x_is_f32)
-        hipLaunchKernelGGL(rmsnorm_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)stream, x,
-                           (const _Float16*)weight, (_Float16*)out, hidden, eps);
-    else
-        hipLaunchKernelGGL(rmsnorm_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, x,
-                           (const _Float16*)weight, (_Float16*)out, hidden, eps);
+    hipLaunchKernelGGL(rmsnorm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, (const _Float16*)weight, (_Float16*)out,
+                       hidden, eps, x_is_f32 ? 1 : 0);
     return pc_check_launch("rmsnorm_kernel");
 }
 
@@ -319,8 +315,8 @@ PC_EXPORT int pc_rmsnorm_split(const float* x, const void* weight, void* out_hi,
     PC_REQUIRE(rows >= 0 && hidden > 0 && hidden % 8 == 0, PC_ERR_ARG, "pc_rmsnorm_split: hidden must be a multiple of 8");
     if (rows == 0) return PC_OK;
     PC_REQUIRE(x && weight && out_hi && out_lo, PC_ERR_ARG, "pc_rmsnorm_split: null pointer");
-    hipLaunchKernelGGL(rmsnorm_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const void*)x,
-                       (const _Float16*)weight, (_Float16*)out_hi, hidden, eps, (_Float16*)out_lo);
+    hipLaunchKernelGGL(rmsnorm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const void*)x,
+                       (const _Float16*)weight, (_Float16*)out_hi, hidden, eps, 1, (_Float16*)out_lo);
     return pc_check_launch("rmsnorm_kernel");
 }
 

@@ -1,0 +1,237 @@
+// Batched decode over slots with int8 K / V images: the one-row slot attention of pc_slots.hip reading, per slot, an image of the
+// sequence's rows in the format of pc_kv_q8.hip -- 0.516 of the fp16 bytes -- instead of the fp16 arena.
+//
+// Replaces, for S sequences at once, with the keys held as int8 codes and one fp32 scale per row and plane:
+//           softmax(q k^T / sqrt(d)) v over the sequence's keys  promptcache/model/llama2.py:366-400
+//
+// Image of one slot, qcap rows per plane, P = n_layers * 2 * n_kv_heads planes in the arena's plane order -- ONE contiguous run,
+// the layout of pc_kv_q8.hip at n = qcap:
+//   int8  codes [P][qcap][D]
+//   fp32  scale [P][qcap]      starts at byte P*qcap*D
+//
+// A live slot b (live[b] != 0, 0 <= len[b] < cap[b]) attends over len + 1 keys.  Keys [0, len) come from the image, an element's
+// value is (float)code * scale in fp32 (no fp16 rounding of the product; the scale is applied to the reduced dot on the K side
+// and folded into p on the V side).  Key len is the row pc_rope_append_slots has just written: it is read from the fp16 arena,
+// exact.  The key axis is split as pc_attn_decode_slots splits it (chunk = ceil((len + 1) / nsplit), host-fixed nsplit); the
+// partial records and the merge are that entry's (pcr::launch_attn_merge_slots).
+//
+// Staging while reading: the workgroup whose key slice holds key len also quantises that fp16 row -- K and V of its kv head -- with
+// the pinned arithmetic (pcq::quant_row16) and stores codes and scale at image row len; of the G = H / Hkv passes over a kv head
+// only the first does.  No workgroup of the launch reads image row len (the image keys end at len - 1), so nothing is handed
+// from one workgroup to another; no other image row is written.
+//
+// Order of summation, all a function of the slot's own length and of nsplit: a lane group (8 lanes, 16 head dims each) keeps an
+// online softmax over keys k0 + grp, k0 + grp + 32, ..., four at a time; the group that takes the exact row (group 0 of wave 0)
+// adds it last; the eight groups of a wave are merged through lane exchanges, the four waves through LDS, in index order.  A
+// slot's bits depend on nothing another slot holds, nor on its index.
+//
+// One instantiation (head_dim 128, one query head per workgroup pass): a kv head with G query heads is read G times.
+#include <hip/hip_fp16.h>
+#include <math.h>
+
+#include "pc_attn_rows.h"
+#include "pc_kv_q8_quant.h"
+
+namespace {
+
+using pca::kNegBig;
+using pca::kThreads;
+using pcr::h8;
+using pcr::SlotAttnArgs;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kD = 128;
+constexpr int kLPK = kD / 16;        // lanes per key row: 16 codes (one 16-byte load) each
+constexpr int kGPW = 64 / kLPK;      // key groups per wave: a wave instruction reads 8 consecutive rows, 1 KiB
+constexpr int kNG = 4 * kGPW;        // key groups per workgroup
+constexpr int kU = 4;                // keys in flight per group
+
+__device__ __forceinline__ float code_f32(uint32_t w, int b) { return (float)(int)(int8_t)(w >> (8 * b)); }
+
+// grid (split, query head, slot)
+__global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
+    const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo, int64_t q_ts, const uint64_t* __restrict__ kv_base,
+    const uint64_t* __restrict__ kvq_base, const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
+    const int32_t* __restrict__ live, int layer, int n_layers, int H, int Hkv, int qcap, float scale_log2, int nsplit,
+    float* __restrict__ part_o, float* __restrict__ part_ml) {
+    __shared__ float sm[4][kD + 2];
+
+    const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    if (live[b] == 0) return;
+    const int past = len[b], c = cap[b];
+    if (past < 0 || past >= c) return;
+    if (past >= qcap) return;                     // out of contract (the host sizes qcap >= every cap): nothing leaves the image
+    const int G = H / Hkv, kvh = h / G;
+    const int n = past + 1;                       // keys of this slot: image rows [0, past) and the row just appended
+    const int chunk = (n + nsplit - 1) / nsplit;
+    const int k0 = split * chunk, k1 = min(n, k0 + chunk);
+    const int kq = min(k1, past);                 // image keys of this slice: [k0, kq)
+    const bool has_new = k0 <= past && past < k1; // (uniform over the workgroup)
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sub = lane % kLPK, grp = wave * kGPW + lane / kLPK;
+    // image planes of this kv head (rows [0, past] of them are all the kernel touches, and past < qcap)
+    const int64_t kplane = (int64_t)(layer * 2) * Hkv + kvh, vplane = kplane + Hkv;
+    const char* img = (const char*)(uintptr_t)kvq_base[b];
+    const float* sbase = (const float*)(img + (int64_t)n_layers * 2 * Hkv * qcap * kD);
+    const char* kc = img + kplane * qcap * kD + sub * 16;
+    const char* vc = img + vplane * qcap * kD + sub * 16;
+    const float* ks = sbase + kplane * qcap;
+    const float* vs = sbase + vplane * qcap;
+
+    float q[16], acc[16], m = kNegBig, l = 0.0f;
+    {
+        const int64_t qo = (int64_t)b * q_ts + (int64_t)h * kD + sub * 16;
+        const h8 a0 = *(const h8*)(q_hi + qo), a1 = *(const h8*)(q_hi + qo + 8);
+        const h8 r0 = *(const h8*)(q_lo + qo), r1 = *(const h8*)(q_lo + qo + 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            q[e] = ((float)a0[e] + (float)r0[e]) * scale_log2;
+            q[8 + e] = ((float)a1[e] + (float)r1[e]) * scale_log2;
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+    }
+
+    for (int base = k0; base < kq; base += kNG * kU) {
+        u32x4 kk[kU], vv[kU];
+        float sk[kU], sv[kU];
+        bool ok[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int key = base + u * kNG + grp;
+            ok[u] = key < kq;
+            const int row = min(key, kq - 1);     // (a key past the slice re-reads its last row and is masked below)
+            kk[u] = *(const u32x4*)(kc + (int64_t)row * kD);
+            vv[u] = *(const u32x4*)(vc + (int64_t)row * kD);
+            sk[u] = ks[row];
+            sv[u] = vs[row];
+        }
+        float s[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            float d = 0.0f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) d = fmaf(q[e], code_f32(kk[u][e >> 2], e & 3), d);
+#pragma unroll
+            for (int o = 1; o < kLPK; o <<= 1) d += __shfl_xor(d, o);
+            s[u] = ok[u] ? d * sk[u] : -INFINITY;
+        }
+        float mn = m;
+#pragma unroll
+        for (int u = 0; u < kU; ++u) mn = fmaxf(mn, s[u]);
+        const float sc = exp2f(m - mn);
+        l *= sc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] *= sc;
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const float p = exp2f(s[u] - mn);
+            l += p;
+            const float pv = ok[u] ? p * sv[u] : 0.0f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = fmaf(pv, code_f32(vv[u][e >> 2], e & 3), acc[e]);
+        }
+        m = mn;
+    }
+
+    // the row just appended: exact from the fp16 arena, the last key of group 0 of wave 0; staged into the image on the way
+    if (has_new && wave == 0) {                   // (wave-uniform; every lane group of the wave loads the same row)
+        const _Float16* kp = (const _Float16*)(uintptr_t)kv_base[b] + (kplane * c + past) * kD + sub * 16;
+        const _Float16* vp = (const _Float16*)(uintptr_t)kv_base[b] + (vplane * c + past) * kD + sub * 16;
+        const h8 k0v = *(const h8*)kp, k1v = *(const h8*)(kp + 8), v0v = *(const h8*)vp, v1v = *(const h8*)(vp + 8);
+        float kx[16], vx[16];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            kx[e] = (float)k0v[e]; kx[8 + e] = (float)k1v[e];
+            vx[e] = (float)v0v[e]; vx[8 + e] = (float)v1v[e];
+        }
+        float d = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) d = fmaf(q[e], kx[e], d);
+#pragma unroll
+        for (int o = 1; o < kLPK; o <<= 1) d += __shfl_xor(d, o);
+        if (grp == 0) {
+            const float mn = fmaxf(m, d);
+            const float sc = exp2f(m - mn), p = exp2f(d - mn);
+            l = l * sc + p;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = fmaf(p, vx[e], acc[e] * sc);
+            m = mn;
+        }
+        if (h == kvh * G) {                       // the first pass over this kv head stages the row (wave-uniform)
+            uint32_t wk[4], wv[4];
+            float qsk, qsv;
+            pcq::quant_row16(kx, 3, wk, qsk);
+            pcq::quant_row16(vx, 3, wv, qsv);
+            if (grp == 0) {
+                char* wimg = (char*)(uintptr_t)kvq_base[b];
+                float* wsb = (float*)(wimg + (int64_t)n_layers * 2 * Hkv * qcap * kD);
+                *(u32x4*)(wimg + (kplane * qcap + past) * kD + sub * 16) = u32x4{wk[0], wk[1], wk[2], wk[3]};
+                *(u32x4*)(wimg + (vplane * qcap + past) * kD + sub * 16) = u32x4{wv[0], wv[1], wv[2], wv[3]};
+                if (sub == 0) {
+                    wsb[kplane * qcap + past] = qsk;
+                    wsb[vplane * qcap + past] = qsv;
+                }
+            }
+        }
+    }
+
+    // the key groups of a wave -> its first group
+#pragma unroll
+    for (int o = kLPK; o < 64; o <<= 1) {
+        const float mo = __shfl_xor(m, o), lo = __shfl_xor(l, o);
+        const float mn = fmaxf(m, mo);
+        const float wa = exp2f(m - mn), wb = exp2f(mo - mn);
+        l = l * wa + lo * wb;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = acc[e] * wa + __shfl_xor(acc[e], o) * wb;
+        m = mn;
+    }
+    if (lane < kLPK) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) sm[wave][sub * 16 + e] = acc[e];
+        if (sub == 0) { sm[wave][kD] = m; sm[wave][kD + 1] = l; }
+    }
+    __syncthreads();
+    // the four waves -> this split's partial (unnormalised sum, maximum, denominator)
+    if (tid < kD) {
+        const int d = tid;
+        float ms = sm[0][kD];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) ms = fmaxf(ms, sm[w][kD]);
+        float num = 0.0f, den = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float wt = exp2f(sm[w][kD] - ms);
+            den = fmaf(wt, sm[w][kD + 1], den);
+            num = fmaf(wt, sm[w][d], num);
+        }
+        const int64_t rec = ((int64_t)b * H + h) * nsplit + split;
+        part_o[rec * kD + d] = num;
+        if (d == 0) { part_ml[rec * 2] = ms; part_ml[rec * 2 + 1] = den; }
+    }
+}
+
+}  // namespace
+
+PC_EXPORT int pc_attn_decode_slots_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                                      const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t layer,
+                                      int32_t H, int32_t Hkv, int32_t D, float softmax_scale, int32_t nsplit, void* workspace,
+                                      int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base,
+                                      int32_t qcap, int32_t n_layers, void* stream) {
+    PC_REQUIRE(D == kD, PC_ERR_ARG, "pc_attn_decode_slots_q8: head_dim must be 128");
+    PC_REQUIRE(kvq_base != nullptr, PC_ERR_ARG, "pc_attn_decode_slots_q8: null pointer");
+    PC_REQUIRE(qcap >= 1 && n_layers >= 1 && layer < n_layers, PC_ERR_ARG,
+               "pc_attn_decode_slots_q8: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)");
+    SlotAttnArgs a = {(const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len, live, nullptr, nullptr,
+                      S, 0, layer, H, Hkv, 0.f, nsplit, 0, nullptr, nullptr, (_Float16*)out_frag_hi, (_Float16*)out_frag_lo};
+    if (const int rc = pcr::slot_attn_prepare("pc_attn_decode_slots_q8", false, false, 8, a, D, softmax_scale, workspace, workspace_bytes))
+        return rc;
+    hipLaunchKernelGGL(attn_decode_slots_q8_kernel, dim3(a.ns_own, a.H, a.S), dim3(kThreads), 0, (hipStream_t)stream, a.q_hi, a.q_lo,
+                       a.q_ts, a.kv_base, kvq_base, a.cap, a.len, a.live, a.layer, n_layers, a.H, a.Hkv, qcap, a.scale_log2, a.ns_own,
+                       a.part_o, a.part_ml);
+    pcr::launch_attn_merge_slots(a, D, false, (hipStream_t)stream);
+    return pc_check_launch("attn_decode_slots_q8_kernel");
+}

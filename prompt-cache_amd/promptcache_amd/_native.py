@@ -179,6 +179,7 @@ SIGNATURES = {
     "pc_kv_gather": (C.c_int, [C.POINTER(_vp), _pi32, _pi32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pc_kv_slice_store": (C.c_int, [_vp, _i32, _pi32, _pi32, C.POINTER(_vp), _i32, _i32, _i32, _i32, _vp]),
     "pc_kv_quant_q8": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "pc_kv_quant_q8_rows": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "pc_kv_gather_q8": (C.c_int, [C.POINTER(KvSeg), _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pc_kv_row_table": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "pc_attn_gather_ok": (C.c_int, [C.POINTER(AttnArgs)]),
@@ -226,6 +227,8 @@ SIGNATURES = {
     "pc_attn_decode_slots_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
     "pc_attn_decode_slots": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
                                        _vp, _vp]),
+    "pc_attn_decode_slots_q8": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
+                                          _vp, _vp, _i32, _i32, _vp]),
     "pc_attn_decode_slots_trunk_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "pc_attn_decode_slots_trunk": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
                                              _vp, _i64, _vp, _vp, _vp]),
@@ -354,6 +357,18 @@ def kv_quant_q8(src, n_rows: int, n_planes: int, head_dim: int, dst_image, strea
     rc = load().pc_kv_quant_q8(src.data_ptr(), n_rows, n_planes, head_dim, dst_image.data_ptr(),
                                current_stream() if stream is None else stream)
     check(rc, "pc_kv_quant_q8")
+
+
+def kv_quant_q8_rows(src, src_plane_rows: int, n_rows: int, n_planes: int, head_dim: int, dst_image, dst_plane_rows: int,
+                     stream: Optional[int] = None) -> None:
+    """Rows ``[0, n_rows)`` of every plane of ``src`` (fp16, planes ``src_plane_rows`` rows apart: a batch-1 arena) -> the same rows
+    of an int8 image with ``dst_plane_rows`` rows per plane (``dst_image``: uint8, kv_q8_image_bytes(dst_plane_rows, ...) long);
+    pc_kv_quant_q8_rows."""
+    if dst_image.numel() * dst_image.element_size() < kv_q8_image_bytes(max(dst_plane_rows, 0), n_planes, head_dim):
+        raise ValueError("kv_quant_q8_rows: the image tensor is too small")
+    rc = load().pc_kv_quant_q8_rows(src.data_ptr(), src_plane_rows, n_rows, n_planes, head_dim, dst_image.data_ptr(), dst_plane_rows,
+                                    current_stream() if stream is None else stream)
+    check(rc, "pc_kv_quant_q8_rows")
 
 
 def kv_gather_q8(seg_ptrs: Sequence[int], seg_lens: Sequence[int], seg_dst_rows: Sequence[int], dst,
@@ -987,6 +1002,19 @@ def attn_decode_slots(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int,
                                      workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
                                      current_stream() if stream is None else stream)
     check(rc, "pc_attn_decode_slots")
+
+
+def attn_decode_slots_q8(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int, layer: int, H: int, Hkv: int, D: int,
+                         softmax_scale: float, nsplit: int, workspace, out_frag, kvq_base, qcap: int, n_layers: int,
+                         stream: Optional[int] = None) -> None:
+    """``attn_decode_slots`` with keys ``[0, len)`` of every slot read from its int8 image (``kvq_base``: int64[S] image addresses,
+    ``qcap`` rows per plane, ``n_layers * 2 * Hkv`` planes) and the row just appended from the fp16 arena, which the launch also
+    quantises into image row ``len`` (pc_attn_decode_slots_q8) -> fragment planes (hi, lo)."""
+    rc = load().pc_attn_decode_slots_q8(q_hi.data_ptr(), q_lo.data_ptr(), q_ts, kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(),
+                                        live.data_ptr(), S, layer, H, Hkv, D, softmax_scale, nsplit, workspace.data_ptr(),
+                                        workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
+                                        kvq_base.data_ptr(), qcap, n_layers, current_stream() if stream is None else stream)
+    check(rc, "pc_attn_decode_slots_q8")
 
 
 def attn_decode_slots_trunk_workspace_bytes(S: int, H: int, D: int, nsplit_own: int, nsplit_trunk: int) -> int:

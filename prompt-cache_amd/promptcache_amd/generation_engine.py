@@ -382,9 +382,27 @@ class GenerationEngine:
             return "PC_DEVICE_SAMPLE=0"
         return None
 
-    def batch_plan(self, n_requests: int, params: GenerationParameters) -> Tuple[bool, str]:
+    def _slot_kv(self, slot_kv: Optional[str], share_trunk: bool, lookup: int, batched: bool, why: str) -> str:
+        """The K/V mode a batched loop runs with: the argument, else ``PC_SLOT_KV``, else "fp16".  "int8" where the loop cannot
+        run it -- ``check_slot_kv`` (model/llama_hip.py) -- raises ValueError, before anything is asked of the model."""
+        kv = os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv
+        if kv != "fp16":
+            from .model.llama_hip import check_slot_kv
+            hf = getattr(self.lm, "hf_model", None)
+            check_slot_kv(kv, share_trunk=bool(share_trunk), lookup=int(lookup), head_dim=getattr(hf, "D", None),
+                          no_loop=self._no_batched_loop(False, False), not_batched=None if batched else why)
+        return kv
+
+    def batch_plan(self, n_requests: int, params: GenerationParameters, slot_kv: Optional[str] = None) -> Tuple[bool, str]:
         """``(batched, reason)``: whether ``generate_batch`` decodes ``n_requests`` sequences together in one device loop
-        (``model/llama_hip.py`` SlotLoop) or runs them one after another through ``generate``, and why.  Host logic only."""
+        (``model/llama_hip.py`` SlotLoop) or runs them one after another through ``generate``, and why.  Host logic only.
+        ``slot_kv`` (None: ``PC_SLOT_KV``): with "int8" the reason of a batched plan says that the loop reads int8 K/V images."""
+        batched, why = self._batch_plan(n_requests, params)
+        if batched and (os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv) == "int8":
+            why += ", K/V read from int8 images (slot_kv='int8')"
+        return batched, why
+
+    def _batch_plan(self, n_requests: int, params: GenerationParameters) -> Tuple[bool, str]:
         if n_requests < 1:
             return False, "no requests"
         if n_requests > self.MAX_BATCH:
@@ -400,7 +418,7 @@ class GenerationEngine:
 
     @torch.inference_mode()
     def generate_batch(self, requests, params: GenerationParameters, stream_interval: int = 2,
-                       share_trunk: Optional[bool] = None, lookup: Optional[int] = None
+                       share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None
                        ) -> Generator[Tuple[int, Output], None, None]:
         """Generate for several prompts at once: ``requests = [(token_ids, position_ids, cache), ...]``, each as
         ``CacheEngine.process(prompt, slot=k)`` returned it (every cache in a staged buffer of its own).  Yields ``(index,
@@ -422,13 +440,26 @@ class GenerationEngine:
         (``LlamaHIP.lookup_slot_loop(share_trunk=True)``) where the model has that step
         (``lookup_trunk_available``) and ``batch_plan`` decodes the batch in a device loop; a refused lookup loop falls back to
         ``slot_loop(share_trunk=True)``.  Anywhere else the combination raises ValueError, as it did before that step existed,
-        before anything is asked of the model."""
+        before anything is asked of the model.
+        ``slot_kv`` (None: ``PC_SLOT_KV``, default "fp16"): "int8" decodes over int8 images of the slots' K/V rows
+        (``LlamaHIP.slot_loop(kv="int8")``) -- about half the attention's bytes, the format's accuracy, and 0.516 of
+        an arena MORE memory per slot.  ValueError with ``share_trunk``, ``lookup`` > 0, head_dim other than 128, a model without
+        the slot loop or a batch that is not decoded in the device loop."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         lookup = int(os.environ.get("PC_SLOT_LOOKUP", "0")) if lookup is None else int(lookup)
         requests = [(list(t), list(p), c) for t, p, c in requests]
         hf = getattr(self.lm, "hf_model", None)
-        batched, why = self.batch_plan(len(requests), params)
+        batched, why = self._batch_plan(len(requests), params)
+        if batched:
+            arenas = [getattr(c, "arena", None) for _, _, c in requests]
+            if not (all(a is not None and a.B == 1 for a in arenas) and len(set(map(id, arenas))) == len(arenas)):
+                kv_batched, kv_why = False, "a cache is not a staged batch-1 arena of its own"
+            else:
+                kv_batched, kv_why = True, why
+        else:
+            kv_batched, kv_why = False, why
+        slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, kv_batched, kv_why)
         if lookup > 0 and share_trunk:
             offered = getattr(hf, "lookup_trunk_available", None)
             if offered is None or not offered():
@@ -468,7 +499,8 @@ class GenerationEngine:
                                                stop_ids=params.stop_token_ids, share_trunk=bool(share_trunk))
                 if loop is None:
                     loop = hf.slot_loop(*first, None if plain_greedy else params, [st.seed for st in members],
-                                        [st.output_ids for st in members], params.stop_token_ids, share_trunk=bool(share_trunk))
+                                        [st.output_ids for st in members], params.stop_token_ids, share_trunk=bool(share_trunk),
+                                        **({"kv": slot_kv} if slot_kv != "fp16" else {}))
                 if loop is None:
                     raise RuntimeError("generate_batch: the model refused a batched decode loop over these caches")
                 yield from self._pump_slots(loop, members)
@@ -480,7 +512,15 @@ class GenerationEngine:
             gc.collect()
 
     # -- a stream of requests: continuous batching ------------------------------------------------
-    def serve_plan(self, lookup: int = 0, slots: Optional[int] = None) -> Tuple[bool, str]:
+    def serve_plan(self, lookup: int = 0, slots: Optional[int] = None, slot_kv: Optional[str] = None) -> Tuple[bool, str]:
+        """``_serve_plan``; ``slot_kv`` (None: ``PC_SLOT_KV``): with "int8" the reason of a batched plan says that the loop reads
+        int8 K/V images."""
+        batched, why = self._serve_plan(lookup, slots)
+        if batched and (os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv) == "int8":
+            why += ", K/V read from int8 images (slot_kv='int8')"
+        return batched, why
+
+    def _serve_plan(self, lookup: int = 0, slots: Optional[int] = None) -> Tuple[bool, str]:
         """``(batched, reason)``: whether ``serve`` runs its requests through one device loop that admits new prompts as slots free
         up (``model/llama_hip.py`` SlotLoop, ``each=True``), or one after another through ``generate``, and why.  Host logic only.
         Requests carry their own parameters, so both device loops must be on.  ``lookup`` = k > 0 (``serve(lookup=k)`` over
@@ -513,7 +553,8 @@ class GenerationEngine:
 
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
-              share_trunk: Optional[bool] = None, lookup: Optional[int] = None) -> Generator[Tuple[int, Output], None, None]:
+              share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None
+              ) -> Generator[Tuple[int, Output], None, None]:
         """Continuous batching over ``cache_engine.slots`` slots.  ``requests``: any iterable -- it may be lazy -- of ``Prompt`` or
         ``(Prompt, GenerationParameters)``; ``params`` is the default for bare prompts.  Requests are numbered in the order they
         are pulled; yields ``(index, Output)``.  A request is pulled when a slot is free: ``cache_engine.process(prompt, slot=k)``,
@@ -534,17 +575,20 @@ class GenerationEngine:
         (``LlamaHIP.lookup_slot_loop(each=True)``): on identical logits the tokens are the one-token loop's, sampled
         ones included.  Where the model has no lookup step or ``slots * (k + 1) > 64`` (``serve_plan(lookup, slots)``) today's
         loop runs.  With ``share_trunk`` the step reads a group's shared rows once for all draft rows of the group.  In the
-        lookup form ``last_serve_stats`` gains ``tokens`` (decoded in the loop) and ``steps`` (replays)."""
+        lookup form ``last_serve_stats`` gains ``tokens`` (decoded in the loop) and ``steps`` (replays).
+        ``slot_kv`` (None: ``PC_SLOT_KV``, default "fp16"): ``generate_batch``'s -- "int8" serves over int8 images of the slots' rows,
+        sized from ``cache_engine.max_ctx_length``; ValueError with ``share_trunk``, ``lookup`` > 0 or where ``serve_plan`` says no."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         lookup = min(int(os.environ.get("PC_SERVE_LOOKUP", "0")) if lookup is None else int(lookup), 15)
+        slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, *self._serve_plan())
 
         def unpack(req):
             if isinstance(req, (tuple, list)):
                 return req[0], (req[1] if req[1] is not None else params)
             return req, params
 
-        batched, _ = self.serve_plan()
+        batched, _ = self._serve_plan()
         if not batched:
             full = bool(getattr(self.lm, "use_full_position_ids", False))
             for r, req in enumerate(requests):
@@ -621,7 +665,8 @@ class GenerationEngine:
                                                hist_cap=2 * cache_engine.max_ctx_length)
                 if loop is None:
                     loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
-                                        max_keys=cache_engine.max_ctx_length, trunks=trunks)
+                                        max_keys=cache_engine.max_ctx_length, trunks=trunks,
+                                        **({"kv": slot_kv} if slot_kv != "fp16" else {}))
                 if loop is None:
                     raise RuntimeError("serve: the model refused a batched decode loop over these caches")
                 for k, st in enumerate(pending):

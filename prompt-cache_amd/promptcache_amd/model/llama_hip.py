@@ -466,6 +466,7 @@ class _SlotLoopHost:
     MAX_SLOTS = 16
     MAX_ROWS = 64                    # rows of one step, S * (k + 1): what the weight-streaming projections take
     k = 0                            # draft rows per slot
+    kv = "fp16"                      # what the step's attention reads: the fp16 arenas, or int8 images of them (SlotLoop(kv="int8"))
     ctr0 = 0                         # the device step counter at replay 0 (step i's record lands in ring row (ctr0 + i) % RING)
 
     def _build(self, model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each,
@@ -499,6 +500,8 @@ class _SlotLoopHost:
                     _trunk_verify(arenas[j], arenas[l], T, f"sequence {j}", f"sequence {l}")
         self._split_counts([a.length for a in arenas], max_news, trunks, max_keys)
         st = self.st = self._make_state(tokens, corpora, hist_cap)
+        if self.kv == "int8":             # one int8 image per slot index, owned by the loop state and allocated before any capture
+            self.qcap, self.kvq = model._slot_kvq(st, S, max([a.cap for a in arenas] + [int(max_keys or 0)]))
         model._live_loop = self
         self.logits = st["logits"]
         self.host = torch.zeros((self.RING, S) + self._record, dtype=torch.int32, pin_memory=True)
@@ -518,6 +521,7 @@ class _SlotLoopHost:
             return
         for s, a, trunk in zip(idx, arenas, trunks):
             self._enter(s, a, trunk, max_new, stop_ids)
+            self._quantise_entry(s, a)
 
         def col(vals, dtype, fill=0):
             t = torch.full((S,), fill, dtype=dtype)
@@ -542,6 +546,17 @@ class _SlotLoopHost:
             a = a.grown(max(need, 2 * a.cap))
         self.m._tail_done(a, 0, 1, a.length)
         return a
+
+    def _quantise_entry(self, s: int, a) -> None:
+        """kv="int8": rows [0, length) of the arena a sequence enters with -> the image of slot ``s`` (``pc_kv_quant_q8_rows``), on
+        the loop's stream behind ``materialize()`` and in front of the arm launch or the first replay."""
+        if self.kv != "int8":
+            return
+        if a.cap > self.qcap:
+            raise RuntimeError(f"{type(self).__name__}: the arena of slot {s} holds {a.cap} rows, the loop's int8 images {self.qcap} "
+                               "(build the loop with max_keys >= the largest arena capacity)")
+        m = self.m
+        _native.kv_quant_q8_rows(a.buf, a.cap, a.length, m.L * 2 * m.Hkv, m.D, self.kvq[s], self.qcap)
 
     def _enter(self, s: int, a, trunk, max_new: int, stop_ids) -> int:
         """Sequence number ``len(arenas)`` sits in slot ``s`` from replay ``n`` on: one more row of every per-sequence table."""
@@ -594,6 +609,7 @@ class _SlotLoopHost:
         fields = dict(slot=s, cap=a.cap, kv_base=a.buf.data_ptr(), len=a.length, pos=int(position), id=int(token), leader=leader,
                       trunk=T, budget=int(max_new), counter=self.ctr0 + self.n, **extra)
         off = _fill_arm_block(arr, self._arm_header, fields, seed, params, stop_ids, history, m.config.vocab_size)
+        self._quantise_entry(s, a)
         self._arm(ent[0], arr, off, hist)
         ent[1].record()
         ent[2] = True
@@ -712,7 +728,7 @@ class SlotLoop(_SlotLoopHost):
         return self.m._slot_state(self.S)
 
     def _graph(self):
-        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each)
+        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap if self.kv == "int8" else 0)
 
     def _fill_state(self, col, tokens, positions, max_new, params, seeds, histories, stop_ids) -> None:
         """The state words of the loop over ``pc_sample_advance_slots``: one parameter block and one stop list for all slots."""
@@ -804,6 +820,15 @@ class SlotLoop(_SlotLoopHost):
         if i > self._last[k] or i < self._start[k]:
             return None
         return int(self.host[(self.ctr0 + i) % self.RING][self.idx[k]])
+
+
+class SlotLoopQ8(SlotLoop):
+    """``SlotLoop`` whose attention reads int8 images of the slots' K / V rows (``LlamaHIP.slot_loop(kv="int8")``):
+    the loop state also holds one image per slot index (``kvq``, ``qcap`` rows per plane) and their addresses (``kvq_base``);
+    a sequence that enters has its arena rows quantised into its slot's image, and every step stages the row it appends.  The
+    fp16 arenas stay complete, so ``close`` / ``retire`` and whatever reads an arena afterwards behave as ``SlotLoop``'s."""
+
+    kv = "int8"
 
 
 class LookupSlotLoop(_SlotLoopHost):
@@ -964,6 +989,33 @@ def check_weight_format(weight_format: str, int8_weights: bool, shape=None, llam
         if v % 128:
             raise ValueError(f"weight_format='mxfp4' needs {name} to be a multiple of 128 (a 16-byte lane load of the 4-bit "
                              f"image is four 32-feature MX blocks); {name} = {v}")
+
+
+SLOT_KV = ("fp16", "int8")
+
+
+def check_slot_kv(kv: str, share_trunk: bool = False, lookup: int = 0, head_dim: Optional[int] = None, no_loop: Optional[str] = None,
+                  not_batched: Optional[str] = None) -> None:
+    """``ValueError`` naming the conflict for a ``slot_kv`` / ``kv`` mode the batched decode loop cannot run -- raised before
+    anything is allocated.  Pure.  ``no_loop``: why the model has no slot loop (Falcon / MPT, ``load_in_8bit``,
+    ``PC_DECODE_TAIL=1``), ``not_batched``: why ``batch_plan`` / ``serve_plan`` would not decode this batch in the device loop
+    (None: they would)."""
+    if kv not in SLOT_KV:
+        raise ValueError(f"slot_kv must be one of {SLOT_KV}, not {kv!r}")
+    if kv != "int8":
+        return
+    if share_trunk:
+        raise ValueError("slot_kv='int8' and share_trunk exclude each other (the shared-trunk attention reads the leader's fp16 "
+                         "arena; int8 images under share_trunk are not implemented)")
+    if int(lookup) > 0:
+        raise ValueError("slot_kv='int8' and lookup > 0 exclude each other (the k + 1 row verify step reads the fp16 arenas; "
+                         "int8 images under lookup are not implemented)")
+    if no_loop is not None:
+        raise ValueError(f"slot_kv='int8' needs the batched decode loop, which this model does not have: {no_loop}")
+    if head_dim is not None and head_dim != 128:
+        raise ValueError(f"slot_kv='int8' is implemented for head_dim 128 only (pc_attn_decode_slots_q8); head_dim = {head_dim}")
+    if not_batched is not None:
+        raise ValueError(f"slot_kv='int8' needs a batch decoded in the device loop, and this one is not: {not_batched}")
 
 
 def parse_keep_fp16(value) -> bool:
@@ -2464,7 +2516,7 @@ class LlamaHIP:
     def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
                   slots: Optional[int] = None, slot_index=None, share_trunk: bool = False,
                   min_trunk: Optional[int] = None, each: bool = False, max_keys: Optional[int] = None,
-                  trunks=None) -> Optional["SlotLoop"]:
+                  trunks=None, kv: str = "fp16") -> Optional["SlotLoop"]:
         """A batched device-side decode loop over the arenas behind ``pasts`` (one ``past_key_values`` per sequence, each a
         batch-1 arena of its own): sequence k feeds ``tokens[k]`` at position ``positions[k]`` next.  ``params`` None or plain
         greedy: argmax; otherwise the sampled chain with ``seeds[k]`` (the stream continues at step 1) and ``histories[k]``.
@@ -2478,13 +2530,19 @@ class LlamaHIP:
         with one entry per sequence, and ``SlotLoop.admit`` puts new sequences into slots whose sequence is over.
         ``max_keys``: the upper bound of keys the split counts of the attention are taken from (default: from this batch).  A
         serving loop passes the capacity of the slot buffers, once: a sequence's bits must not depend on who joins later, and the
-        attention's summation order depends on the split counts."""
+        attention's summation order depends on the split counts.
+        ``kv="int8"``: the loop keeps an int8 image (the format of ``pc_kv_quant_q8``) of every slot's rows and the
+        attention reads that instead of the fp16 arena -- about half the bytes; accuracy is the format's.  The arenas stay
+        complete (every decoded row is still appended), so memory GROWS by 0.516 of an arena per slot.  ``max_keys`` then also
+        sizes the images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError."""
+        check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, head_dim=self.D,
+                      no_loop=None if self.slot_loop_available() else "the model has no batched decode loop")
         front = self._slot_loop_front(pasts, stop_ids, each, share_trunk, min_trunk, trunks)
         if front is None:
             return None
         arenas, trunks = front
-        return SlotLoop(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks,
-                        each, max_keys)
+        cls = SlotLoopQ8 if kv == "int8" else SlotLoop
+        return cls(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each, max_keys)
 
     def _slot_loop_front(self, pasts, stop_ids, each: bool, share_trunk: bool, min_trunk, trunks):
         """What ``slot_loop`` and ``lookup_slot_loop`` do before they build their loop -> (arenas, trunks), or None where there is
@@ -2536,13 +2594,31 @@ class LlamaHIP:
             sts[S] = st
         return st
 
-    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False):
+    def _slot_kvq(self, st: dict, S: int, need: int):
+        """The int8 images of the S-slot step with ``kv="int8"``: one per slot index, ``qcap >= need`` rows per plane, and their
+        addresses in ``st["kvq_base"]`` (int64[S], device data of the captured step).  Kept with the slot state and reused by
+        later loops; they only grow.  -> (qcap, images)."""
+        if st.get("kvq_cap", 0) < need:
+            st["kvq"] = None                   # (the smaller images go first)
+            nbytes = _native.kv_q8_image_bytes(int(need), self.L * 2 * self.Hkv, self.D)
+            st["kvq"] = [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(S)]
+            st["kvq_cap"] = int(need)
+            if "kvq_base" not in st:
+                st["kvq_base"] = torch.zeros(S, dtype=torch.int64, device=self.device)
+            st["kvq_base"].copy_(torch.tensor([t.data_ptr() for t in st["kvq"]], dtype=torch.int64))
+        return st["kvq_cap"], st["kvq"]
+
+    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0):
         """The captured S-slot decode step.  Everything that changes from step to step or from batch to batch -- arena
         addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch.
-        ``nsplit_trunk`` > 0: the step with shared trunks; which slots share what is device data as well (leader / trunk)."""
+        ``nsplit_trunk`` > 0: the step with shared trunks; which slots share what is device data as well (leader / trunk).
+        ``qcap`` > 0: the step over int8 images (``kv="int8"``); the image addresses are device data too, the key gains "q8" and
+        the images' rows per plane, which is an argument of the launch."""
         key = ("slots", S, nsplit, "trunk", nsplit_trunk) if nsplit_trunk else ("slots", S, nsplit)
         if each:
             key += ("each",)
+        if qcap:
+            key += ("q8", qcap)
         g = self._graphs.pop(key, None)
         if g is not None:
             self._graphs[key] = g
@@ -2554,19 +2630,20 @@ class LlamaHIP:
         # advances nothing, the live words are put back behind it
         live = st["live"].clone()
         st["live"].zero_()
-        self._forward_slots(st, S, nsplit, nsplit_trunk, each)
+        self._forward_slots(st, S, nsplit, nsplit_trunk, each, qcap)
         torch.cuda.synchronize()
         prime_graph_capture(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._forward_slots(st, S, nsplit, nsplit_trunk, each)
+            self._forward_slots(st, S, nsplit, nsplit_trunk, each, qcap)
         st["live"].copy_(live)
         self._graphs[key] = g
         return g
 
-    def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False) -> None:
+    def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0) -> None:
         """One decode step over S slots: the <= 16-row projections of ``_layers_norm_fused`` around per-slot RoPE + append
-        and attention; logits to ``st["logits"]``, then the advance launch."""
+        and attention; logits to ``st["logits"]``, then the advance launch.  ``qcap`` > 0: the attention reads the slots' int8
+        images (``pc_attn_decode_slots_q8``) and stages the appended row into them; the arenas are appended to as always."""
         n = _native
         dev, c = self.device, self.config
         H, Hkv, D, hid, inter = self.H, self.Hkv, self.D, c.hidden_size, c.intermediate_size
@@ -2596,7 +2673,10 @@ class LlamaHIP:
             else:
                 n.gemm_skinny_norm(self._w16(lw, "wqkv", True), x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
             n.rope_append_slots(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D)
-            if nsplit_trunk:
+            if qcap:
+                n.attn_decode_slots_q8(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
+                                       self.softmax_scale, nsplit, ws, (ah, al), st["kvq_base"], qcap, self.L)
+            elif nsplit_trunk:
                 n.attn_decode_slots_trunk(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], st["leader"],
                                           st["trunk"], S, li, H, Hkv, D, self.softmax_scale, nsplit, nsplit_trunk, ws, (ah, al))
             else:

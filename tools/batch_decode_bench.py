@@ -9,6 +9,12 @@ B (W + K) / (W + B K) from the weight bytes W a decode step streams and the K/V 
     python tools/batch_decode_bench.py --share-trunk [--out profiles/r10_trunk_decode.json]
         # (c) as well: generate_batch(share_trunk=True), interleaved with (a) and (b) in the same process, next to the extended
         # byte model B (W + K) / (W + K_t + B K_o) (K_t: the shared staged rows, read once; K_o: a sequence's own rows)
+    python tools/batch_decode_bench.py --slot-kv int8 [--weight-format mxfp4] [--out profiles/slot_kv_q8_bench.json]
+        # the slot loop over int8 K/V images (slot_loop(kv="int8")) beside the fp16 slot loop: same process, same
+        # model, same prefilled slots, S = 4 / 8 / 16; the two legs interleaved with the order rotating; step time from the HIP
+        # events around one replay, median [min .. max]; plus the accuracy record of sequence 0: max |logit_int8 - logit_fp16|
+        # of the first loop step and how many of 32 greedy tokens agree.  --out merges the run into the file under its
+        # weight format, so the fp16 and the MXFP4 run share one JSON.
 """
 import argparse
 import json
@@ -53,6 +59,90 @@ def batch_rate(ge, eng, prompt, params, B, share=False):
     return B * (params.max_new_tokens - 1) / (time.perf_counter() - t0)
 
 
+def slot_kv_bench(args):
+    """--slot-kv int8: fp16 leg and int8 leg of the slot loop, stepped by hand (SlotLoop.enqueue / elapsed_ms)."""
+    steps, warm = max(args.new, 40), 8
+    fmt_w = args.weight_format
+    lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0, **({"weight_format": fmt_w} if fmt_w != "fp16" else {}))
+    m = lm.hf_model
+    sizes = [int(b) for b in args.batches.split(",")] if args.batches != "1,2,4,8,16" else [4, 8, 16]
+    eng = CacheEngine(4096, lm, slots=max(sizes))
+    fmt = lm.get_formatter()
+    sp, pp = synth.persona_like()
+    eng.add_schema(fmt(sp))
+    prompt = Prompt(pp, [fmt])
+    pre = []                                                                   # per slot: (past, rows after the prefill, token, position)
+    for k in range(max(sizes)):
+        ids, pos, _, cache = eng.process(prompt, slot=k)
+        out = lm(input_ids=torch.tensor([ids], device="cuda:0"), position_ids=torch.tensor([pos], device="cuda:0"),
+                 past_key_values=cache, use_cache=True)
+        past = out.past_key_values
+        pre.append((past, past.arena.length, int(torch.argmax(out.logits[0, -1])), max(pos) + 2))
+    keys = pre[0][1]
+    result = {"shape": "llama2-7b (random init)", "weight_format": fmt_w, "prompt": f"persona schema, {keys} keys per slot after the prefill",
+              "steps": steps, "warm_steps_dropped": warm, "repeats": args.repeats,
+              "how": "SlotLoop stepped by hand, greedy; ms per replay from the HIP events around it (SlotLoop.elapsed_ms), steps "
+                     f"{warm}..{steps - 1} of every repetition; legs interleaved, order rotating; median [min .. max]", "rows": {}}
+
+    def leg(S, kv):
+        pasts = []
+        for past, n0, _, _ in pre[:S]:
+            past.arena.length = n0                                             # (rows behind it are dead: the loop rewrites them)
+            pasts.append(past)
+        loop = m.slot_loop(pasts, [t for _, _, t, _ in pre[:S]], [p for _, _, _, p in pre[:S]], steps + 1, kv=kv)
+        try:
+            loop.enqueue()
+            torch.cuda.synchronize()
+            first = loop.logits[0].clone()
+            for _ in range(steps - 1):
+                loop.enqueue()
+            toks = [loop.token(0, i) for i in range(steps)]
+            ms = [loop.elapsed_ms(i) for i in range(warm, steps)]
+        finally:
+            loop.close([0] * S)
+        return ms, first, toks
+
+    for S in sizes:
+        times = {"fp16": [], "int8": []}
+        acc = None
+        for r in range(args.repeats + 1):                                       # (repetition 0 captures the graphs: dropped)
+            order = ["fp16", "int8"] if r % 2 == 0 else ["int8", "fp16"]
+            got = {kv: leg(S, kv) for kv in order}
+            if r == 0:
+                d = float((got["int8"][1] - got["fp16"][1]).abs().max())
+                agree = sum(int(a == b) for a, b in zip(got["int8"][2][:32], got["fp16"][2][:32]))
+                first_diff = next((i for i, (a, b) in enumerate(zip(got["int8"][2][:32], got["fp16"][2][:32])) if a != b), None)
+                acc = {"max_abs_dlogit_first_step": d, "greedy_tokens_agree_of_32": agree, "first_disagreement": first_diff,
+                       "max_abs_logit_fp16_first_step": float(got["fp16"][1].abs().max())}
+                continue
+            for kv in order:
+                times[kv] += got[kv][0]
+        row = {}
+        for kv in ("fp16", "int8"):
+            row[kv + "_ms"] = {"median": round(statistics.median(times[kv]), 4), "min": round(min(times[kv]), 4),
+                               "max": round(max(times[kv]), 4), "n": len(times[kv])}
+        f, q = row["fp16_ms"], row["int8_ms"]
+        row["gain_ms"] = round(f["median"] - q["median"], 4)
+        row["gain_us_per_layer"] = round((f["median"] - q["median"]) * 1e3 / m.L, 2)
+        row["fp16_spread_ms"] = round(f["max"] - f["min"], 4)
+        row["int8_median_below_fp16_min"] = q["median"] < f["min"]
+        row["gain_exceeds_fp16_spread"] = (f["median"] - q["median"]) > (f["max"] - f["min"])
+        row["accuracy_sequence_0"] = acc
+        row["kv_bytes_fp16_per_step"] = S * m.L * 2 * m.Hkv * keys * m.D * 2
+        row["kv_bytes_int8_per_step"] = S * m.L * 2 * m.Hkv * keys * (m.D + 4)
+        result["rows"][str(S)] = row
+        print(json.dumps({str(S): row}), file=sys.stderr, flush=True)
+    if args.out:
+        merged = {}
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                merged = json.loads(fh.read() or "{}")
+        merged["weights_" + fmt_w] = result
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(merged, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--new", type=int, default=64, help="greedy tokens per sequence")
@@ -60,9 +150,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--only-batch", type=int, default=0, help="run (b) at this B alone, twice (warm + one), and print its rate")
     ap.add_argument("--share-trunk", action="store_true", help="add leg (c): generate_batch(share_trunk=True)")
+    ap.add_argument("--slot-kv", choices=("fp16", "int8"), default="fp16",
+                    help="int8: measure the slot loop over int8 K/V images beside the fp16 slot loop (S = 4 / 8 / 16, or --batches)")
+    ap.add_argument("--weight-format", choices=("fp16", "mxfp4"), default="fp16", help="with --slot-kv int8: the decoder weights")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "batch_decode_bench measures on the GPU"
+    if args.slot_kv == "int8":
+        return slot_kv_bench(args)
     batches = [int(b) for b in args.batches.split(",")]
     lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0)
     eng = CacheEngine(4096, lm, slots=max(batches + [args.only_batch]))
