@@ -45,6 +45,9 @@ def main():
                     help="with --batch / --serve: what the batched loop's attention reads (default: PC_SLOT_KV, else fp16); int8 = "
                          "int8 images of the slots' K/V rows, about half the bytes per step, the format's accuracy, and 0.516 of a "
                          "slot buffer MORE memory per slot (the fp16 buffers stay); not with --share-trunk or --lookup")
+    ap.add_argument("--slot-drop-fp16", action="store_true",
+                    help="with --serve and --slot-kv int8: no slot keeps an fp16 buffer (keep_arenas=False; default: "
+                         "PC_SLOT_KEEP_ARENAS): every prompt is prefilled in one shared buffer and lives on as its int8 image")
     ap.add_argument("--serve", type=int, default=0,
                     help="serve N prompts with mixed max_new_tokens through --batch slots (continuous batching: a finished "
                          "sequence's slot takes the next prompt while the others keep decoding)")
@@ -63,6 +66,7 @@ def main():
                     help="with --weights mxfp4: keep only the 4-bit images of the decoder weights resident (keep_fp16=False; default: "
                          "PC_W4_KEEP_FP16); passes above 64 rows expand each projection just in time")
     a = ap.parse_args()
+    skw = dict(keep_arenas=False) if a.slot_drop_fp16 else {}
     wkw = dict(weight_format=a.weights, **(dict(keep_fp16=False) if a.drop_fp16 else {}))
 
     if os.path.isdir(a.model):
@@ -131,13 +135,13 @@ def main():
             for r in range(a.serve):
                 pr = Prompt(prompt_text[:cut] + f"<user>{synth.words(4 + r % 5, 5000 + r)}</user>" + prompt_text[cut:], preproc)
                 yield pr, dataclasses.replace(params, max_new_tokens=budgets[r % len(budgets)])
-        batched, why = gen_engine.serve_plan(a.lookup or 0, cache_engine.slots, slot_kv=a.slot_kv)
+        batched, why = gen_engine.serve_plan(a.lookup or 0, cache_engine.slots, slot_kv=a.slot_kv, **skw)
         for _pass in ("warm", "timed"):
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk, lookup=a.lookup,
-                                              slot_kv=a.slot_kv):
+                                              slot_kv=a.slot_kv, **skw):
                 lasts[r] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

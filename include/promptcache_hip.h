@@ -782,7 +782,29 @@ int pc_lookup_verify_sample(const float* logits, int64_t ldl, int32_t vocab, int
  * once per query head.  Host contract: qcap >= cap[b] for every slot (a slot with len[b] >= qcap is left alone: neither its
  * image nor its partials are touched and its output rows are undefined).  PC_ERR_ARG with nothing launched: head_dim != 128,
  * H % Hkv != 0, a null pointer, S outside 1..16, qcap < 1, layer outside [0, n_layers), nsplit outside 1..32, a workspace that
- * is too small. */
+ * is too small.
+ *
+ * Int8-only residency (no fp16 arena per slot).  kv_base[b] is then the slot's FRESH-ROW buffer: fp16 [P][128], plane stride
+ * head_dim, 16-byte aligned, holding the K / V row of the current step only; cap[b] keeps its meaning as the bound on len[b].
+ * pc_rope_append_slots_q8: pc_rope_append_slots' arguments with kv_base read that way, plus kvq_base / qcap / n_layers as above.
+ * For a live slot with 0 <= len[b] < cap[b] and len[b] < qcap: q_hi / q_lo are pc_rope_append_slots' bits (both in_layout
+ * values); the rotated K row and the V row, rounded to fp16 as there, go to planes (layer*2)*Hkv + h and + Hkv of the fresh-row
+ * buffer, and -- quantised with the arithmetic of pc_kv_quant_q8, bit for bit -- to image row len[b] (codes and scale).  Any
+ * other slot is left alone: nothing is written anywhere.  PC_ERR_ARG with nothing launched: what pc_rope_append_slots refuses,
+ * head_dim != 128, a null kvq_base, qcap < 1, layer outside [0, n_layers).
+ * pc_attn_decode_slots_q8_fresh: pc_attn_decode_slots_q8 behind pc_rope_append_slots_q8 -- the exact row is read from the
+ * fresh-row buffer (kv_base[b] + plane * 128) and nothing is staged: the launch writes no image byte.  Slices, order of
+ * summation, records, merge and argument checks are pc_attn_decode_slots_q8's; on equal image rows [0, len) and an equal
+ * exact row the planes are bit-equal to that entry's. */
+int pc_rope_append_slots_q8(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
+                            const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live,
+                            int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, const uint64_t* kvq_base, int32_t qcap,
+                            int32_t n_layers, void* stream);
+int pc_attn_decode_slots_q8_fresh(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                                  const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t layer, int32_t H,
+                                  int32_t Hkv, int32_t D, float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes,
+                                  void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base, int32_t qcap, int32_t n_layers,
+                                  void* stream);
 int pc_rope_append_slots(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
                          const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live,
                          int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, void* stream);

@@ -30,7 +30,7 @@ int slot_attn_prepare(const char* name, bool rows, bool trunk, int ws_align, Slo
                       void* workspace, int64_t workspace_bytes);
 // attn_verify_trunk_slots_kernel<D, RT>: the shared rows of every group, once for all rows of all members
 void launch_attn_trunk_slots(const SlotAttnArgs& a, int D, int RT, hipStream_t st);
-// attn_merge_slots_kernel<D, TRUNK>
+// attn_merge_slots_kernel<D> (trunk: the launch passes the leader / trunk words, otherwise null)
 void launch_attn_merge_slots(const SlotAttnArgs& a, int D, bool trunk, hipStream_t st);
 // rope_append_slots_rows_kernel, grid (k + 1, S)
 void launch_rope_append_slots_rows(const float* qkv, int64_t ld, int layout, _Float16* q_hi, _Float16* q_lo, int64_t q_ts,
@@ -42,6 +42,23 @@ __device__ __forceinline__ void load8(const float* p, float (&x)[8]) {
     const f4 a = *(const f4*)p, b = *(const f4*)(p + 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) { x[e] = a[e]; x[e + 4] = b[e]; }
+}
+
+// RoPE on the 8 rotary pairs (lo[e], hi[e]) of one work item of rope_append_kernel<float> (pc_rope.hip) with the table entries
+// w8[e] = (cos, sin): the rotated pair as split-precision halves, (olo, rlo) = hi / lo of the first member, (ohi, rhi) of the second.
+// Once for the kernels that append a slot's row (rope_append_slots_rows_kernel, rope_append_slots_q8_kernel).
+__device__ __forceinline__ void rope_pairs8(const float (&lo)[8], const float (&hi)[8], const float2* __restrict__ w8, h8& olo, h8& ohi,
+                                            h8& rlo, h8& rhi) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float2 w = w8[e];
+        const float a = lo[e] * w.x - hi[e] * w.y, b2 = hi[e] * w.x + lo[e] * w.y;
+        _Float16 t0, t1, t2, t3;
+        pc_split(a, t0, t1);
+        pc_split(b2, t2, t3);
+        olo[e] = t0; rlo[e] = t1;
+        ohi[e] = t2; rhi[e] = t3;
+    }
 }
 
 // LDS of a kernel that calls attn_rows_tiles: four wave-private V tiles, reused for the four waves' partials
@@ -223,9 +240,10 @@ __device__ __forceinline__ void attn_rows_tiles(const _Float16* __restrict__ q_h
 }
 
 // Merge of the records of a (row, head) in index (= key) order, one workgroup per (head, row), one thread per head dim; k + 1
-// rows per slot, nrec records per (row, head).  TRUNK: the first nsplit_t records are the trunk launch's, and a row of a slot on
-// its own (slot_trunk_rows 0) has none: its merge starts at record nsplit_t.  den > 0: every row sees its own key.
-template <int D, bool TRUNK>
+// rows per slot, nrec records per (row, head).  leader != nullptr (the entries with shared trunks; uniform over the launch): the
+// first nsplit_t records are the trunk launch's, and a row of a slot on its own (slot_trunk_rows 0) has none: its merge starts at
+// record nsplit_t.  den > 0: every row sees its own key.
+template <int D>
 __global__ __launch_bounds__(D) void attn_merge_slots_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                              const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
                                                              const int32_t* __restrict__ live, const int32_t* __restrict__ leader,
@@ -237,7 +255,7 @@ __global__ __launch_bounds__(D) void attn_merge_slots_kernel(const float* __rest
     if (!lookup_slot_runs(cap, len, live, b, k)) return;
     const int64_t base = ((int64_t)r * H + h) * nrec;
     int s0 = 0;
-    if constexpr (TRUNK) s0 = slot_trunk_rows(b, S, kv_base, cap, len, leader, trunk) > 0 ? 0 : nsplit_t;
+    if (leader != nullptr) s0 = slot_trunk_rows(b, S, kv_base, cap, len, leader, trunk) > 0 ? 0 : nsplit_t;
     float ms = pca::kNegBig;
     for (int s = s0; s < nrec; ++s) ms = fmaxf(ms, part_ml[(base + s) * 2]);
     float num = 0.0f, den = 0.0f;

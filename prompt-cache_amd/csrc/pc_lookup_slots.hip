@@ -59,16 +59,7 @@ __global__ __launch_bounds__(kThreads) void rope_append_slots_rows_kernel(
             load8(src + (layout ? ch * 16 : ch * 8), lo);
             load8(src + (layout ? ch * 16 + 8 : half + ch * 8), hi);
             h8 olo, ohi, rlo, rhi;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float2 w = csr[ch * 8 + e];
-                const float a = lo[e] * w.x - hi[e] * w.y, b2 = hi[e] * w.x + lo[e] * w.y;
-                _Float16 t0, t1, t2, t3;
-                pc_split(a, t0, t1);
-                pc_split(b2, t2, t3);
-                olo[e] = t0; rlo[e] = t1;
-                ohi[e] = t2; rhi[e] = t3;
-            }
+            pcr::rope_pairs8(lo, hi, csr + ch * 8, olo, ohi, rlo, rhi);
             *(h8*)(dst + ch * 8) = olo;
             *(h8*)(dst + half + ch * 8) = ohi;
             if (is_q) {
@@ -231,10 +222,11 @@ void launch_trunk(const SlotAttnArgs& a, hipStream_t st) {
                        a.ns_trunk, a.ns_trunk + a.ns_own, a.part_o, a.part_ml);
 }
 
-template <int D, bool TRUNK>
-void launch_merge(const SlotAttnArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL((pcr::attn_merge_slots_kernel<D, TRUNK>), dim3(a.H, a.S * (a.k + 1)), dim3(D), 0, st, a.part_o, a.part_ml, a.cap,
-                       a.len, a.live, a.leader, a.trunk, a.kv_base, a.S, a.k, a.H, a.ns_trunk, a.ns_trunk + a.ns_own, a.of_hi, a.of_lo);
+// (trunk: whether the merge skips the trunk records of a slot on its own -- said by the leader words, null without)
+template <int D>
+void launch_merge(const SlotAttnArgs& a, bool trunk, hipStream_t st) {
+    hipLaunchKernelGGL((pcr::attn_merge_slots_kernel<D>), dim3(a.H, a.S * (a.k + 1)), dim3(D), 0, st, a.part_o, a.part_ml, a.cap,
+                       a.len, a.live, trunk ? a.leader : nullptr, a.trunk, a.kv_base, a.S, a.k, a.H, a.ns_trunk, a.ns_trunk + a.ns_own, a.of_hi, a.of_lo);
 }
 
 bool rows_shape_ok(int S, int k) { return S >= 1 && S <= 16 && k >= 0 && k <= 15 && S * (k + 1) <= kMaxRows; }
@@ -269,8 +261,8 @@ void launch_attn_trunk_slots(const SlotAttnArgs& a, int D, int RT, hipStream_t s
 }
 
 void launch_attn_merge_slots(const SlotAttnArgs& a, int D, bool trunk, hipStream_t st) {
-    if (D == 128) trunk ? launch_merge<128, true>(a, st) : launch_merge<128, false>(a, st);
-    else trunk ? launch_merge<64, true>(a, st) : launch_merge<64, false>(a, st);
+    if (D == 128) launch_merge<128>(a, trunk, st);
+    else launch_merge<64>(a, trunk, st);
 }
 
 void launch_rope_append_slots_rows(const float* qkv, int64_t ld, int layout, _Float16* q_hi, _Float16* q_lo, int64_t q_ts,

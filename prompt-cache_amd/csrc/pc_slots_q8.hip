@@ -26,6 +26,11 @@
 // slot's bits depend on nothing another slot holds, nor on its index.
 //
 // One instantiation (head_dim 128, one query head per workgroup pass): a kv head with G query heads is read G times.
+//
+// Int8-only residency (pc_rope_append_slots_q8 / pc_attn_decode_slots_q8_fresh): a slot keeps no fp16 arena.  kv_base[b] is then the
+// slot's FRESH-ROW buffer, fp16 [P][D] (plane stride D): the append launch writes the step's K / V row there AND quantises it into
+// image row len (rope_append_slots_q8_kernel), and the attention -- the kernel above with `fresh` set -- reads the exact row from
+// kv_base[b] + plane * D and stages nothing.  cap[b] is still the bound on len.
 #include <hip/hip_fp16.h>
 #include <math.h>
 
@@ -37,6 +42,7 @@ namespace {
 using pca::kNegBig;
 using pca::kThreads;
 using pcr::h8;
+using pcr::load8;
 using pcr::SlotAttnArgs;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -47,6 +53,87 @@ constexpr int kGPW = 64 / kLPK;      // key groups per wave: a wave instruction 
 constexpr int kNG = 4 * kGPW;        // key groups per workgroup
 constexpr int kU = 4;                // keys in flight per group
 
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// ---- RoPE + append without an arena, one workgroup per slot -------------------------------------------------------------------
+// q: the work items and the arithmetic of rope_append_slots_rows_kernel at k = 0 (pcr::rope_pairs8), bit for bit.  K / V: a row of
+// a kv head is held by 8 consecutive lanes, lane `sub` with features [8 sub, 8 sub + 8) and [64 + 8 sub, 64 + 8 sub + 8) -- K as
+// that kernel's rotary work item has them, V loaded the same way --, rounded to fp16 as that kernel rounds what it stores.  The
+// fp16 row goes to plane (layer * 2) * Hkv + h (K) / + Hkv (V) of the fresh-row buffer kv_base[b] (plane stride D), and through
+// pcq::quant_row16 -- the row maximum is an exchange among the 8 lanes; a code depends on its value and that maximum only -- into
+// image row len: this lane's first two code dwords are bytes [8 sub, 8 sub + 8) of the row, the other two bytes [64 + 8 sub, ..).
+__global__ __launch_bounds__(kThreads) void rope_append_slots_q8_kernel(
+    const float* __restrict__ qkv, int64_t ld, int layout, _Float16* __restrict__ q_hi, _Float16* __restrict__ q_lo, int64_t q_ts,
+    const float2* __restrict__ cs, const uint64_t* __restrict__ kv_base, const uint64_t* __restrict__ kvq_base,
+    const int32_t* __restrict__ cap, const int32_t* __restrict__ len, const int32_t* __restrict__ live, int layer, int n_layers, int H,
+    int Hkv, int qcap) {
+    const int b = blockIdx.x;
+    if (live[b] == 0) return;
+    const int past = len[b];
+    if (past < 0 || past >= cap[b] || past >= qcap) return;     // (nothing of this slot is written anywhere)
+    constexpr int half = kD / 2;
+    const float2* csr = cs + (int64_t)b * half;
+    const float* row = qkv + (int64_t)b * ld;
+    for (int it = threadIdx.x; it < H * kLPK; it += kThreads) {
+        const int h = it / kLPK, ch = it - h * kLPK;
+        const float* src = row + (int64_t)h * kD;
+        float lo[8], hi[8];
+        load8(src + (layout ? ch * 16 : ch * 8), lo);
+        load8(src + (layout ? ch * 16 + 8 : half + ch * 8), hi);
+        h8 olo, ohi, rlo, rhi;
+        pcr::rope_pairs8(lo, hi, csr + ch * 8, olo, ohi, rlo, rhi);
+        _Float16* dh = q_hi + (int64_t)b * q_ts + (int64_t)h * kD;
+        _Float16* dl = q_lo + (int64_t)b * q_ts + (int64_t)h * kD;
+        *(h8*)(dh + ch * 8) = olo;
+        *(h8*)(dh + half + ch * 8) = ohi;
+        *(h8*)(dl + ch * 8) = rlo;
+        *(h8*)(dl + half + ch * 8) = rhi;
+    }
+    // rows [0, Hkv): K of kv head r; rows [Hkv, 2 Hkv): V of kv head r - Hkv -- projection head H + r, plane plane0 + r
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int sub = lane % kLPK, nrow = 2 * Hkv;
+    const int64_t plane0 = (int64_t)(layer * 2) * Hkv;
+    _Float16* fresh = (_Float16*)(uintptr_t)kv_base[b];
+    char* img = (char*)(uintptr_t)kvq_base[b];
+    float* sbase = (float*)(img + (int64_t)n_layers * 2 * Hkv * qcap * kD);
+    for (int r0 = wave * kGPW; r0 < nrow; r0 += 4 * kGPW) {     // (wave-uniform trip count: every lane runs the exchanges)
+        const int r = r0 + lane / kLPK;
+        const bool on = r < nrow;                               // (whole rows: uniform over a row's 8 lanes)
+        float lo[8], hi[8];
+        if (on) {
+            const float* src = row + (int64_t)(H + r) * kD;
+            load8(src + (layout ? sub * 16 : sub * 8), lo);
+            load8(src + (layout ? sub * 16 + 8 : half + sub * 8), hi);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) lo[e] = hi[e] = 0.0f;
+        }
+        h8 olo, ohi;
+        if (r < Hkv) {
+            h8 rlo, rhi;
+            pcr::rope_pairs8(lo, hi, csr + sub * 8, olo, ohi, rlo, rhi);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { olo[e] = (_Float16)lo[e]; ohi[e] = (_Float16)hi[e]; }
+        }
+        float x[16];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { x[e] = (float)olo[e]; x[8 + e] = (float)ohi[e]; }
+        uint32_t w[4];
+        float qs;
+        pcq::quant_row16(x, 3, w, qs);
+        if (on) {
+            _Float16* fp = fresh + (plane0 + r) * kD;
+            *(h8*)(fp + sub * 8) = olo;
+            *(h8*)(fp + half + sub * 8) = ohi;
+            char* cp = img + ((plane0 + r) * qcap + past) * kD;
+            *(u32x2*)(cp + sub * 8) = u32x2{w[0], w[1]};
+            *(u32x2*)(cp + half + sub * 8) = u32x2{w[2], w[3]};
+            if (sub == 0) sbase[(plane0 + r) * qcap + past] = qs;
+        }
+    }
+}
+
 __device__ __forceinline__ float code_f32(uint32_t w, int b) { return (float)(int)(int8_t)(w >> (8 * b)); }
 
 // grid (split, query head, slot)
@@ -54,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
     const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo, int64_t q_ts, const uint64_t* __restrict__ kv_base,
     const uint64_t* __restrict__ kvq_base, const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
     const int32_t* __restrict__ live, int layer, int n_layers, int H, int Hkv, int qcap, float scale_log2, int nsplit,
-    float* __restrict__ part_o, float* __restrict__ part_ml) {
+    float* __restrict__ part_o, float* __restrict__ part_ml, int fresh) {
     __shared__ float sm[4][kD + 2];
 
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
@@ -136,10 +223,11 @@ __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
         m = mn;
     }
 
-    // the row just appended: exact from the fp16 arena, the last key of group 0 of wave 0; staged into the image on the way
+    // the row just appended: exact from the fp16 arena, the last key of group 0 of wave 0; staged into the image on the way.
+    // fresh (uniform over the launch): the row lies in the slot's fresh-row buffer, plane stride D, and its image row is written
     if (has_new && wave == 0) {                   // (wave-uniform; every lane group of the wave loads the same row)
-        const _Float16* kp = (const _Float16*)(uintptr_t)kv_base[b] + (kplane * c + past) * kD + sub * 16;
-        const _Float16* vp = (const _Float16*)(uintptr_t)kv_base[b] + (vplane * c + past) * kD + sub * 16;
+        const _Float16* kp = (const _Float16*)(uintptr_t)kv_base[b] + (fresh ? kplane : kplane * c + past) * kD + sub * 16;
+        const _Float16* vp = (const _Float16*)(uintptr_t)kv_base[b] + (fresh ? vplane : vplane * c + past) * kD + sub * 16;
         const h8 k0v = *(const h8*)kp, k1v = *(const h8*)(kp + 8), v0v = *(const h8*)vp, v1v = *(const h8*)(vp + 8);
         float kx[16], vx[16];
 #pragma unroll
@@ -160,7 +248,7 @@ __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
             for (int e = 0; e < 16; ++e) acc[e] = fmaf(p, vx[e], acc[e] * sc);
             m = mn;
         }
-        if (h == kvh * G) {                       // the first pass over this kv head stages the row (wave-uniform)
+        if (!fresh && h == kvh * G) {             // the first pass over this kv head stages the row (wave-uniform)
             uint32_t wk[4], wv[4];
             float qsk, qsv;
             pcq::quant_row16(kx, 3, wk, qsk);
@@ -216,22 +304,63 @@ __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
 
 }  // namespace
 
+namespace {
+
+// Both attention entries: `fresh` = 0 reads the exact row from the arena and stages it, 1 reads it from the fresh-row buffer.
+int attn_slots_q8(const char* name, int fresh, const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                  const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                  float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo,
+                  const uint64_t* kvq_base, int32_t qcap, int32_t n_layers, void* stream) {
+    PC_REQUIRE(D == kD, PC_ERR_ARG, "%s: head_dim must be 128", name);
+    PC_REQUIRE(kvq_base != nullptr, PC_ERR_ARG, "%s: null pointer", name);
+    PC_REQUIRE(qcap >= 1 && n_layers >= 1 && layer < n_layers, PC_ERR_ARG,
+               "%s: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)", name);
+    SlotAttnArgs a = {(const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len, live, nullptr, nullptr,
+                      S, 0, layer, H, Hkv, 0.f, nsplit, 0, nullptr, nullptr, (_Float16*)out_frag_hi, (_Float16*)out_frag_lo};
+    if (const int rc = pcr::slot_attn_prepare(name, false, false, 8, a, D, softmax_scale, workspace, workspace_bytes)) return rc;
+    hipLaunchKernelGGL(attn_decode_slots_q8_kernel, dim3(a.ns_own, a.H, a.S), dim3(kThreads), 0, (hipStream_t)stream, a.q_hi, a.q_lo,
+                       a.q_ts, a.kv_base, kvq_base, a.cap, a.len, a.live, a.layer, n_layers, a.H, a.Hkv, qcap, a.scale_log2, a.ns_own,
+                       a.part_o, a.part_ml, fresh);
+    pcr::launch_attn_merge_slots(a, D, false, (hipStream_t)stream);
+    return pc_check_launch("attn_decode_slots_q8_kernel");
+}
+
+}  // namespace
+
 PC_EXPORT int pc_attn_decode_slots_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
                                       const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t layer,
                                       int32_t H, int32_t Hkv, int32_t D, float softmax_scale, int32_t nsplit, void* workspace,
                                       int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base,
                                       int32_t qcap, int32_t n_layers, void* stream) {
-    PC_REQUIRE(D == kD, PC_ERR_ARG, "pc_attn_decode_slots_q8: head_dim must be 128");
-    PC_REQUIRE(kvq_base != nullptr, PC_ERR_ARG, "pc_attn_decode_slots_q8: null pointer");
+    return attn_slots_q8("pc_attn_decode_slots_q8", 0, q_hi, q_lo, q_token_stride, kv_base, cap, len, live, S, layer, H, Hkv, D,
+                         softmax_scale, nsplit, workspace, workspace_bytes, out_frag_hi, out_frag_lo, kvq_base, qcap, n_layers, stream);
+}
+
+PC_EXPORT int pc_attn_decode_slots_q8_fresh(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                                            const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t layer,
+                                            int32_t H, int32_t Hkv, int32_t D, float softmax_scale, int32_t nsplit, void* workspace,
+                                            int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base,
+                                            int32_t qcap, int32_t n_layers, void* stream) {
+    return attn_slots_q8("pc_attn_decode_slots_q8_fresh", 1, q_hi, q_lo, q_token_stride, kv_base, cap, len, live, S, layer, H, Hkv, D,
+                         softmax_scale, nsplit, workspace, workspace_bytes, out_frag_hi, out_frag_lo, kvq_base, qcap, n_layers, stream);
+}
+
+PC_EXPORT int pc_rope_append_slots_q8(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
+                                      const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len,
+                                      const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                                      const uint64_t* kvq_base, int32_t qcap, int32_t n_layers, void* stream) {
+    PC_REQUIRE(S >= 1 && S <= 16 && layer >= 0 && H > 0 && Hkv > 0, PC_ERR_ARG, "pc_rope_append_slots_q8: bad sizes (1 <= S <= 16)");
+    PC_REQUIRE(D == kD, PC_ERR_ARG, "pc_rope_append_slots_q8: head_dim must be 128");
+    PC_REQUIRE(qkv && q_hi && q_lo && cs && kv_base && cap && len && live && kvq_base, PC_ERR_ARG,
+               "pc_rope_append_slots_q8: null pointer");
+    PC_REQUIRE(in_layout == 0 || in_layout == 1, PC_ERR_ARG,
+               "pc_rope_append_slots_q8: in_layout is 0 (natural) or 1 (rotary-pair tiles)");
     PC_REQUIRE(qcap >= 1 && n_layers >= 1 && layer < n_layers, PC_ERR_ARG,
-               "pc_attn_decode_slots_q8: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)");
-    SlotAttnArgs a = {(const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len, live, nullptr, nullptr,
-                      S, 0, layer, H, Hkv, 0.f, nsplit, 0, nullptr, nullptr, (_Float16*)out_frag_hi, (_Float16*)out_frag_lo};
-    if (const int rc = pcr::slot_attn_prepare("pc_attn_decode_slots_q8", false, false, 8, a, D, softmax_scale, workspace, workspace_bytes))
-        return rc;
-    hipLaunchKernelGGL(attn_decode_slots_q8_kernel, dim3(a.ns_own, a.H, a.S), dim3(kThreads), 0, (hipStream_t)stream, a.q_hi, a.q_lo,
-                       a.q_ts, a.kv_base, kvq_base, a.cap, a.len, a.live, a.layer, n_layers, a.H, a.Hkv, qcap, a.scale_log2, a.ns_own,
-                       a.part_o, a.part_ml);
-    pcr::launch_attn_merge_slots(a, D, false, (hipStream_t)stream);
-    return pc_check_launch("attn_decode_slots_q8_kernel");
+               "pc_rope_append_slots_q8: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)");
+    PC_REQUIRE(ld >= (int64_t)(H + 2 * Hkv) * D && ld % 4 == 0 && q_token_stride % 8 == 0 && ((uintptr_t)qkv & 15) == 0 &&
+                   ((uintptr_t)q_hi & 15) == 0 && ((uintptr_t)q_lo & 15) == 0,
+               PC_ERR_ARG, "pc_rope_append_slots_q8: rows must keep 16-byte alignment");
+    hipLaunchKernelGGL(rope_append_slots_q8_kernel, dim3(S), dim3(kThreads), 0, (hipStream_t)stream, qkv, ld, in_layout, (_Float16*)q_hi,
+                       (_Float16*)q_lo, q_token_stride, (const float2*)cs, kv_base, kvq_base, cap, len, live, layer, n_layers, H, Hkv, qcap);
+    return pc_check_launch("rope_append_slots_q8_kernel");
 }

@@ -229,6 +229,10 @@ SIGNATURES = {
                                        _vp, _vp]),
     "pc_attn_decode_slots_q8": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp,
                                           _vp, _vp, _i32, _i32, _vp]),
+    "pc_attn_decode_slots_q8_fresh": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64,
+                                                _vp, _vp, _vp, _i32, _i32, _vp]),
+    "pc_rope_append_slots_q8": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
+                                          _i32, _i32, _vp]),
     "pc_attn_decode_slots_trunk_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "pc_attn_decode_slots_trunk": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
                                              _vp, _i64, _vp, _vp, _vp]),
@@ -1015,6 +1019,30 @@ def attn_decode_slots_q8(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: i
                                         workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
                                         kvq_base.data_ptr(), qcap, n_layers, current_stream() if stream is None else stream)
     check(rc, "pc_attn_decode_slots_q8")
+
+
+def rope_append_slots_q8(qkv, ld: int, in_layout: int, q_hi, q_lo, q_ts: int, cs, kv_base, cap, length, live, S: int, layer: int,
+                         H: int, Hkv: int, D: int, kvq_base, qcap: int, n_layers: int, stream: Optional[int] = None) -> None:
+    """``rope_append_slots`` for slots without an fp16 arena (pc_rope_append_slots_q8): ``kv_base`` holds the addresses of the
+    slots' fresh-row buffers (fp16 ``[n_layers * 2 * Hkv][D]``); the step's K / V row goes there and, quantised, into image row
+    ``len`` of ``kvq_base``'s images (``qcap`` rows per plane)."""
+    rc = load().pc_rope_append_slots_q8(qkv.data_ptr(), ld, in_layout, q_hi.data_ptr(), q_lo.data_ptr(), q_ts, cs.data_ptr(),
+                                        kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(), live.data_ptr(), S, layer, H, Hkv, D,
+                                        kvq_base.data_ptr(), qcap, n_layers, current_stream() if stream is None else stream)
+    check(rc, "pc_rope_append_slots_q8")
+
+
+def attn_decode_slots_q8_fresh(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int, layer: int, H: int, Hkv: int, D: int,
+                               softmax_scale: float, nsplit: int, workspace, out_frag, kvq_base, qcap: int, n_layers: int,
+                               stream: Optional[int] = None) -> None:
+    """``attn_decode_slots_q8`` behind ``rope_append_slots_q8`` (pc_attn_decode_slots_q8_fresh): the exact row comes from the
+    fresh-row buffers behind ``kv_base`` and no image byte is written -> fragment planes (hi, lo)."""
+    rc = load().pc_attn_decode_slots_q8_fresh(q_hi.data_ptr(), q_lo.data_ptr(), q_ts, kv_base.data_ptr(), cap.data_ptr(),
+                                              length.data_ptr(), live.data_ptr(), S, layer, H, Hkv, D, softmax_scale, nsplit,
+                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                              out_frag[0].data_ptr(), out_frag[1].data_ptr(), kvq_base.data_ptr(), qcap, n_layers,
+                                              current_stream() if stream is None else stream)
+    check(rc, "pc_attn_decode_slots_q8_fresh")
 
 
 def attn_decode_slots_trunk_workspace_bytes(S: int, H: int, D: int, nsplit_own: int, nsplit_trunk: int) -> int:

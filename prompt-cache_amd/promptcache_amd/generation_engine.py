@@ -393,6 +393,17 @@ class GenerationEngine:
                           no_loop=self._no_batched_loop(False, False), not_batched=None if batched else why)
         return kv
 
+    @staticmethod
+    def _keep_arenas(keep_arenas: Optional[bool], slot_kv: str, generate_batch: bool = False) -> bool:
+        """Whether a batched loop keeps the fp16 slot arenas: the argument, else (``serve``) ``PC_SLOT_KEEP_ARENAS``, else True.
+        False where it cannot run -- ``check_slot_keep_arenas`` (model/llama_hip.py) -- raises ValueError, before anything is
+        allocated."""
+        from .model.llama_hip import check_slot_keep_arenas, parse_keep_arenas
+        if keep_arenas is None:
+            keep_arenas = True if generate_batch else parse_keep_arenas(os.environ.get("PC_SLOT_KEEP_ARENAS"))
+        check_slot_keep_arenas(bool(keep_arenas), slot_kv, generate_batch=generate_batch)
+        return bool(keep_arenas)
+
     def batch_plan(self, n_requests: int, params: GenerationParameters, slot_kv: Optional[str] = None) -> Tuple[bool, str]:
         """``(batched, reason)``: whether ``generate_batch`` decodes ``n_requests`` sequences together in one device loop
         (``model/llama_hip.py`` SlotLoop) or runs them one after another through ``generate``, and why.  Host logic only.
@@ -418,8 +429,8 @@ class GenerationEngine:
 
     @torch.inference_mode()
     def generate_batch(self, requests, params: GenerationParameters, stream_interval: int = 2,
-                       share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None
-                       ) -> Generator[Tuple[int, Output], None, None]:
+                       share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None,
+                       keep_arenas: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
         """Generate for several prompts at once: ``requests = [(token_ids, position_ids, cache), ...]``, each as
         ``CacheEngine.process(prompt, slot=k)`` returned it (every cache in a staged buffer of its own).  Yields ``(index,
         Output)`` pairs; per sequence the ``Output`` stream, the stop-token and stop-string handling, ``max_new_tokens`` and the
@@ -444,7 +455,9 @@ class GenerationEngine:
         ``slot_kv`` (None: ``PC_SLOT_KV``, default "fp16"): "int8" decodes over int8 images of the slots' K/V rows
         (``LlamaHIP.slot_loop(kv="int8")``) -- about half the attention's bytes, the format's accuracy, and 0.516 of
         an arena MORE memory per slot.  ValueError with ``share_trunk``, ``lookup`` > 0, head_dim other than 128, a model without
-        the slot loop or a batch that is not decoded in the device loop."""
+        the slot loop or a batch that is not decoded in the device loop.
+        ``keep_arenas=False`` (``serve``'s int8-only residency) raises ValueError here: the callers hand in one live
+        arena per sequence, so there is nothing to save."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         lookup = int(os.environ.get("PC_SLOT_LOOKUP", "0")) if lookup is None else int(lookup)
@@ -460,6 +473,7 @@ class GenerationEngine:
         else:
             kv_batched, kv_why = False, why
         slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, kv_batched, kv_why)
+        self._keep_arenas(keep_arenas, slot_kv, generate_batch=True)
         if lookup > 0 and share_trunk:
             offered = getattr(hf, "lookup_trunk_available", None)
             if offered is None or not offered():
@@ -512,12 +526,15 @@ class GenerationEngine:
             gc.collect()
 
     # -- a stream of requests: continuous batching ------------------------------------------------
-    def serve_plan(self, lookup: int = 0, slots: Optional[int] = None, slot_kv: Optional[str] = None) -> Tuple[bool, str]:
+    def serve_plan(self, lookup: int = 0, slots: Optional[int] = None, slot_kv: Optional[str] = None,
+                   keep_arenas: Optional[bool] = None) -> Tuple[bool, str]:
         """``_serve_plan``; ``slot_kv`` (None: ``PC_SLOT_KV``): with "int8" the reason of a batched plan says that the loop reads
-        int8 K/V images."""
+        int8 K/V images, and with ``keep_arenas=False`` (None: not named) that no slot keeps an fp16 arena."""
         batched, why = self._serve_plan(lookup, slots)
         if batched and (os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv) == "int8":
             why += ", K/V read from int8 images (slot_kv='int8')"
+            if keep_arenas is not None and not keep_arenas:
+                why += ", no fp16 slot arenas: every prefill runs in one shared arena (keep_arenas=False)"
         return batched, why
 
     def _serve_plan(self, lookup: int = 0, slots: Optional[int] = None) -> Tuple[bool, str]:
@@ -553,8 +570,8 @@ class GenerationEngine:
 
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
-              share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None
-              ) -> Generator[Tuple[int, Output], None, None]:
+              share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None,
+              keep_arenas: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
         """Continuous batching over ``cache_engine.slots`` slots.  ``requests``: any iterable -- it may be lazy -- of ``Prompt`` or
         ``(Prompt, GenerationParameters)``; ``params`` is the default for bare prompts.  Requests are numbered in the order they
         are pulled; yields ``(index, Output)``.  A request is pulled when a slot is free: ``cache_engine.process(prompt, slot=k)``,
@@ -577,11 +594,17 @@ class GenerationEngine:
         loop runs.  With ``share_trunk`` the step reads a group's shared rows once for all draft rows of the group.  In the
         lookup form ``last_serve_stats`` gains ``tokens`` (decoded in the loop) and ``steps`` (replays).
         ``slot_kv`` (None: ``PC_SLOT_KV``, default "fp16"): ``generate_batch``'s -- "int8" serves over int8 images of the slots' rows,
-        sized from ``cache_engine.max_ctx_length``; ValueError with ``share_trunk``, ``lookup`` > 0 or where ``serve_plan`` says no."""
+        sized from ``cache_engine.max_ctx_length``; ValueError with ``share_trunk``, ``lookup`` > 0 or where ``serve_plan`` says no.
+        ``keep_arenas=False`` (None: ``PC_SLOT_KEEP_ARENAS``, default 1; with ``slot_kv="int8"`` only): no slot keeps an
+        fp16 arena.  Every request is staged and prefilled in slot 0's buffer, whatever slot the scheduler gives it, its rows are
+        quantised into the slot's image as it enters the loop (``SlotLoopQ8Only``) and the buffer is free for the next request;
+        the buffers of slots 1.. are never allocated.  The loop is built with the first sequence that has more to decode and the
+        rest of the first fill is admitted in front of replay 0.  Tokens are ``slot_kv="int8"``'s."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         lookup = min(int(os.environ.get("PC_SERVE_LOOKUP", "0")) if lookup is None else int(lookup), 15)
         slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, *self._serve_plan())
+        drop = not self._keep_arenas(keep_arenas, slot_kv)
 
         def unpack(req):
             if isinstance(req, (tuple, list)):
@@ -617,7 +640,8 @@ class GenerationEngine:
 
         def admit_free_slots():
             """Pull requests into free slots: process, prefill and first token; sequences with more to decode enter the loop (or
-            wait for it to be built)."""
+            wait for it to be built).  ``drop``: everything runs in slot 0's buffer, so nobody can wait: the first such sequence
+            builds the loop, and a sequence that has entered lets go of the buffer."""
             nonlocal seed
             while True:
                 nxt = sched.next_request()
@@ -628,7 +652,7 @@ class GenerationEngine:
                 prompt, p = unpack(req)
                 if p is None:
                     raise ValueError("serve: a bare prompt needs the default params")
-                ids, pos, _, cache = cache_engine.process(prompt, slot=slot)
+                ids, pos, _, cache = cache_engine.process(prompt, slot=0 if drop else slot)
                 if not p.plain_greedy and seed is None:
                     seed = int(torch.randint(0, 2 ** 62, (1,)))
                 st = _Stream(self._render, p, stream_interval, ids, max(pos) + 1, index=index, slot=slot,
@@ -645,33 +669,42 @@ class GenerationEngine:
                 if loop is None:
                     pending.append(st)
                     sched.started(slot, index, 0)
+                    if drop:
+                        build_loop()
                 else:
                     trunk = sched.join(slot, st.past.arena.layout) if share_trunk and loop.nsplit_trunk else None
                     st.k = loop.admit(slot, *loop_args(st), *((st.corpus,) if read_k else ()), trunk=trunk)
                     sched.started(slot, index, loop.n)
+                if drop:
+                    st.past = cache = None                         # (the loop holds the rows; the buffer is the next request's)
                 seq[slot] = st
+
+        def build_loop():
+            """The ``each=True`` loop over the sequences waiting in ``pending``."""
+            nonlocal loop
+            slots_ = [st.slot for st in pending]
+            trunks = sched.group_first_fill(slots_, [st.past.arena.layout for st in pending]) if share_trunk else None
+            # (loop_args per sequence -> one list per argument)
+            pasts, toks0, poss, max_news, paramss, seeds_, hists, stops = map(list, zip(*map(loop_args, pending)))
+            if drafts:
+                loop = hf.lookup_slot_loop(pasts, toks0, poss, max_news, drafts, [st.corpus for st in pending], stop_ids=stops,
+                                           slots=S, max_keys=cache_engine.max_ctx_length, trunks=trunks, each=True,
+                                           slot_index=slots_, params=paramss, seeds=seeds_, histories=hists,
+                                           hist_cap=2 * cache_engine.max_ctx_length)
+            if loop is None:
+                loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
+                                    max_keys=cache_engine.max_ctx_length, trunks=trunks,
+                                    **({"kv": slot_kv} if slot_kv != "fp16" else {}), **({"keep_arenas": False} if drop else {}))
+            if loop is None:
+                raise RuntimeError("serve: the model refused a batched decode loop over these caches")
+            for k, st in enumerate(pending):
+                st.k = k
+            pending.clear()
 
         try:
             yield from admit_free_slots()
             if pending:
-                slots_ = [st.slot for st in pending]
-                trunks = sched.group_first_fill(slots_, [st.past.arena.layout for st in pending]) if share_trunk else None
-                # (loop_args per sequence -> one list per argument)
-                pasts, toks0, poss, max_news, paramss, seeds_, hists, stops = map(list, zip(*map(loop_args, pending)))
-                if drafts:
-                    loop = hf.lookup_slot_loop(pasts, toks0, poss, max_news, drafts, [st.corpus for st in pending], stop_ids=stops,
-                                               slots=S, max_keys=cache_engine.max_ctx_length, trunks=trunks, each=True,
-                                               slot_index=slots_, params=paramss, seeds=seeds_, histories=hists,
-                                               hist_cap=2 * cache_engine.max_ctx_length)
-                if loop is None:
-                    loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
-                                        max_keys=cache_engine.max_ctx_length, trunks=trunks,
-                                        **({"kv": slot_kv} if slot_kv != "fp16" else {}))
-                if loop is None:
-                    raise RuntimeError("serve: the model refused a batched decode loop over these caches")
-                for k, st in enumerate(pending):
-                    st.k = k
-                pending.clear()
+                build_loop()
             i = 0
             if loop is not None:
                 read, read_k = _reader(loop)                       # (one read loop for k = 0 and k > 0)

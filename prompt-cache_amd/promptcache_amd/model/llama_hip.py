@@ -501,7 +501,7 @@ class _SlotLoopHost:
         self._split_counts([a.length for a in arenas], max_news, trunks, max_keys)
         st = self.st = self._make_state(tokens, corpora, hist_cap)
         if self.kv == "int8":             # one int8 image per slot index, owned by the loop state and allocated before any capture
-            self.qcap, self.kvq = model._slot_kvq(st, S, max([a.cap for a in arenas] + [int(max_keys or 0)]))
+            self.qcap, self.kvq = model._slot_kvq(st, S, self._image_rows(arenas, max_news, max_keys))
         model._live_loop = self
         self.logits = st["logits"]
         self.host = torch.zeros((self.RING, S) + self._record, dtype=torch.int32, pin_memory=True)
@@ -519,8 +519,9 @@ class _SlotLoopHost:
                 self._admit(idx[j], arenas[j], tokens[j], positions[j], max_news[j], paramss[j], seeds[j], histories[j], stops[j],
                             None if l is None else (idx[l], T), None if corpora is None else corpora[j])
             return
-        for s, a, trunk in zip(idx, arenas, trunks):
-            self._enter(s, a, trunk, max_new, stop_ids)
+        seats = [self._seat(s, a) for s, a in zip(idx, arenas)]
+        for s, a, trunk, seat in zip(idx, arenas, trunks, seats):
+            self._enter(s, seat[0], trunk, max_new, stop_ids)
             self._quantise_entry(s, a)
 
         def col(vals, dtype, fill=0):
@@ -528,8 +529,8 @@ class _SlotLoopHost:
             for s, v in zip(idx, vals):
                 t[s] = v
             return t
-        st["kv_base"].copy_(col([a.buf.data_ptr() for a in arenas], torch.int64), non_blocking=True)
-        st["cap"].copy_(col([a.cap for a in arenas], torch.int32), non_blocking=True)
+        st["kv_base"].copy_(col([base for _, base, _ in seats], torch.int64), non_blocking=True)
+        st["cap"].copy_(col([cap for _, _, cap in seats], torch.int32), non_blocking=True)
         st["len"].copy_(col(self.len0, torch.int32), non_blocking=True)
         st["live"].copy_(col([1] * n, torch.int32), non_blocking=True)
         st["leader"].copy_(col([-1 if l is None else idx[l] for l, _ in trunks], torch.int32, -1), non_blocking=True)
@@ -546,6 +547,14 @@ class _SlotLoopHost:
             a = a.grown(max(need, 2 * a.cap))
         self.m._tail_done(a, 0, 1, a.length)
         return a
+
+    def _image_rows(self, arenas, max_news, max_keys) -> int:
+        """kv="int8": the rows per plane the images must hold -- every arena's capacity (the cap word bounds ``len``)."""
+        return max([a.cap for a in arenas] + [int(max_keys or 0)])
+
+    def _seat(self, s: int, a):
+        """-> (what the loop keeps of the arena a sequence enters slot ``s`` with, the slot's ``kv_base`` word, its ``cap`` word)."""
+        return a, a.buf.data_ptr(), a.cap
 
     def _quantise_entry(self, s: int, a) -> None:
         """kv="int8": rows [0, length) of the arena a sequence enters with -> the image of slot ``s`` (``pc_kv_quant_q8_rows``), on
@@ -606,14 +615,15 @@ class _SlotLoopHost:
         if ent[2]:
             ent[1].synchronize()
         arr = ent[0].numpy()
-        fields = dict(slot=s, cap=a.cap, kv_base=a.buf.data_ptr(), len=a.length, pos=int(position), id=int(token), leader=leader,
+        held, base, cap = self._seat(s, a)
+        fields = dict(slot=s, cap=cap, kv_base=base, len=a.length, pos=int(position), id=int(token), leader=leader,
                       trunk=T, budget=int(max_new), counter=self.ctr0 + self.n, **extra)
         off = _fill_arm_block(arr, self._arm_header, fields, seed, params, stop_ids, history, m.config.vocab_size)
         self._quantise_entry(s, a)
         self._arm(ent[0], arr, off, hist)
         ent[1].record()
         ent[2] = True
-        return self._enter(s, a, (None, 0) if leader < 0 else (leader, T), max_new, stop_ids)
+        return self._enter(s, held, (None, 0) if leader < 0 else (leader, T), max_new, stop_ids)
 
     def _set_length(self, a, length: int) -> None:
         a.length = length
@@ -730,6 +740,15 @@ class SlotLoop(_SlotLoopHost):
     def _graph(self):
         return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap if self.kv == "int8" else 0)
 
+    def slot_kv_bytes(self) -> int:
+        """Bytes of K/V storage behind the loop's slots: the int8 images and fresh-row buffers of its state (``kv="int8"``) plus
+        every distinct arena a sequence of the loop references."""
+        size = lambda t: t.numel() * t.element_size()
+        total = sum(map(size, self.kvq)) if self.kv == "int8" else 0
+        total += sum(map(size, getattr(self, "fresh", ())))
+        bufs = {a.buf.data_ptr(): a.buf for a in self.arenas if getattr(a, "buf", None) is not None}
+        return total + sum(map(size, bufs.values()))
+
     def _fill_state(self, col, tokens, positions, max_new, params, seeds, histories, stop_ids) -> None:
         """The state words of the loop over ``pc_sample_advance_slots``: one parameter block and one stop list for all slots."""
         st, S, n = self.st, self.S, len(tokens)
@@ -829,6 +848,54 @@ class SlotLoopQ8(SlotLoop):
     fp16 arenas stay complete, so ``close`` / ``retire`` and whatever reads an arena afterwards behave as ``SlotLoop``'s."""
 
     kv = "int8"
+
+
+class _ImageSeat:
+    """What a ``SlotLoopQ8Only`` keeps of the arena a sequence entered with: its rows at entry and the bound on its rows (the
+    image's) -- no buffer.  ``close`` / ``retire`` set ``length`` here and touch no arena."""
+
+    buf = None
+
+    def __init__(self, length: int, cap: int):
+        self.length, self.cap = int(length), int(cap)
+
+
+class SlotLoopQ8Only(SlotLoopQ8):
+    """``SlotLoopQ8`` without the fp16 slot arenas (``LlamaHIP.slot_loop(kv="int8", keep_arenas=False)``): a slot's
+    only K/V storage is its int8 image and a fresh-row buffer, fp16 ``[L * 2 * Hkv][D]``, holding the row of the current step
+    (``fresh``; ``st["kv_base"]`` holds these addresses).  The step runs ``pc_rope_append_slots_q8`` /
+    ``pc_attn_decode_slots_q8_fresh``.  A sequence enters from whatever arena its prefill ran in: ``materialize()``, the tail
+    ended, ``pc_kv_quant_q8_rows`` into the slot's image on the loop's stream in front of the arm launch -- after that the loop
+    holds no reference to the arena, which may be staged again at once (same stream: the quantise launch is ordered in front).
+    The cap word of a slot is ``qcap``: a sequence whose image is full ends by the device's "buffer full" rule.  ``qcap`` is the
+    larger of ``max_keys`` and the longest ``length + max_new + 2`` known at build; split counts are ``SlotLoopQ8``'s, so on the
+    same ``max_keys`` a sequence's tokens are that loop's, bit for bit."""
+
+    def _make_state(self, tokens, corpora, hist_cap) -> dict:
+        st = super()._make_state(tokens, corpora, hist_cap)
+        self.fresh = self.m._slot_fresh(st, self.S)          # (allocated before any capture, like the images)
+        return st
+
+    def _image_rows(self, arenas, max_news, max_keys) -> int:
+        return max([a.length + mn + 2 for a, mn in zip(arenas, max_news)] + [int(max_keys or 0)])
+
+    def _prepared(self, a, max_new: int):
+        """No arena is decoded in: nothing grows.  A residual tail still ends here, in front of the quantise launch."""
+        self.m._tail_done(a, 0, 1, a.length)
+        return a
+
+    def _seat(self, s: int, a):
+        return _ImageSeat(a.length, self.qcap), self.fresh[s].data_ptr(), self.qcap
+
+    def _quantise_entry(self, s: int, a) -> None:
+        if a.length > self.qcap:
+            raise RuntimeError(f"{type(self).__name__}: the sequence for slot {s} holds {a.length} rows, the loop's int8 images "
+                               f"{self.qcap} (build the loop with max_keys >= the longest sequence)")
+        m = self.m
+        _native.kv_quant_q8_rows(a.buf, a.cap, a.length, m.L * 2 * m.Hkv, m.D, self.kvq[s], self.qcap)
+
+    def _graph(self):
+        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap, fresh=True)
 
 
 class LookupSlotLoop(_SlotLoopHost):
@@ -1016,6 +1083,28 @@ def check_slot_kv(kv: str, share_trunk: bool = False, lookup: int = 0, head_dim:
         raise ValueError(f"slot_kv='int8' is implemented for head_dim 128 only (pc_attn_decode_slots_q8); head_dim = {head_dim}")
     if not_batched is not None:
         raise ValueError(f"slot_kv='int8' needs a batch decoded in the device loop, and this one is not: {not_batched}")
+
+
+def check_slot_keep_arenas(keep_arenas: bool, kv: str, generate_batch: bool = False) -> None:
+    """``ValueError`` for ``keep_arenas=False`` (int8-only slot residency) where it cannot run -- raised before anything
+    is allocated, behind ``check_slot_kv``'s own refusals of ``kv``.  Pure."""
+    if keep_arenas:
+        return
+    if generate_batch:
+        raise ValueError("keep_arenas=False is not for generate_batch: its callers hand in one live fp16 arena per sequence, so "
+                         "there is nothing to save; serve(slot_kv='int8', keep_arenas=False) prefills every request in one arena")
+    if kv != "int8":
+        raise ValueError(f"keep_arenas=False needs slot_kv='int8' (without the int8 images the fp16 arenas are the only K/V a "
+                         f"slot has); slot_kv = {kv!r}")
+
+
+def parse_keep_arenas(value) -> bool:
+    """``PC_SLOT_KEEP_ARENAS``: unset, empty or ``1`` keeps the fp16 slot arenas under ``slot_kv="int8"``, ``0`` drops them."""
+    if value is None or value in ("", "1"):
+        return True
+    if value == "0":
+        return False
+    raise ValueError(f"PC_SLOT_KEEP_ARENAS must be 0 or 1, not {value!r}")
 
 
 def parse_keep_fp16(value) -> bool:
@@ -2516,7 +2605,7 @@ class LlamaHIP:
     def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
                   slots: Optional[int] = None, slot_index=None, share_trunk: bool = False,
                   min_trunk: Optional[int] = None, each: bool = False, max_keys: Optional[int] = None,
-                  trunks=None, kv: str = "fp16") -> Optional["SlotLoop"]:
+                  trunks=None, kv: str = "fp16", keep_arenas: bool = True) -> Optional["SlotLoop"]:
         """A batched device-side decode loop over the arenas behind ``pasts`` (one ``past_key_values`` per sequence, each a
         batch-1 arena of its own): sequence k feeds ``tokens[k]`` at position ``positions[k]`` next.  ``params`` None or plain
         greedy: argmax; otherwise the sampled chain with ``seeds[k]`` (the stream continues at step 1) and ``histories[k]``.
@@ -2534,14 +2623,18 @@ class LlamaHIP:
         ``kv="int8"``: the loop keeps an int8 image (the format of ``pc_kv_quant_q8``) of every slot's rows and the
         attention reads that instead of the fp16 arena -- about half the bytes; accuracy is the format's.  The arenas stay
         complete (every decoded row is still appended), so memory GROWS by 0.516 of an arena per slot.  ``max_keys`` then also
-        sizes the images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError."""
+        sizes the images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError.
+        ``keep_arenas=False`` (with ``kv="int8"`` only): the loop keeps the images and one fresh-row buffer per slot
+        and NO reference to the arenas behind ``pasts`` -- their rows are quantised into the images on entry and the arenas are
+        free afterwards (``SlotLoopQ8Only``); with ``each=True`` one arena can prefill every sequence in turn."""
         check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, head_dim=self.D,
                       no_loop=None if self.slot_loop_available() else "the model has no batched decode loop")
+        check_slot_keep_arenas(keep_arenas, kv)
         front = self._slot_loop_front(pasts, stop_ids, each, share_trunk, min_trunk, trunks)
         if front is None:
             return None
         arenas, trunks = front
-        cls = SlotLoopQ8 if kv == "int8" else SlotLoop
+        cls = (SlotLoopQ8 if keep_arenas else SlotLoopQ8Only) if kv == "int8" else SlotLoop
         return cls(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each, max_keys)
 
     def _slot_loop_front(self, pasts, stop_ids, each: bool, share_trunk: bool, min_trunk, trunks):
@@ -2608,17 +2701,28 @@ class LlamaHIP:
             st["kvq_base"].copy_(torch.tensor([t.data_ptr() for t in st["kvq"]], dtype=torch.int64))
         return st["kvq_cap"], st["kvq"]
 
-    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0):
+    def _slot_fresh(self, st: dict, S: int):
+        """The fresh-row buffers of the S-slot step without arenas (``keep_arenas=False``): one per slot index, fp16
+        ``[L * 2 * Hkv][D]`` -- the K / V row of the current step.  Kept with the slot state."""
+        if "fresh" not in st:
+            st["fresh"] = [torch.zeros((self.L * 2 * self.Hkv, self.D), dtype=self.dtype, device=self.device) for _ in range(S)]
+        return st["fresh"]
+
+    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0, fresh: bool = False):
         """The captured S-slot decode step.  Everything that changes from step to step or from batch to batch -- arena
         addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch.
         ``nsplit_trunk`` > 0: the step with shared trunks; which slots share what is device data as well (leader / trunk).
         ``qcap`` > 0: the step over int8 images (``kv="int8"``); the image addresses are device data too, the key gains "q8" and
-        the images' rows per plane, which is an argument of the launch."""
+        the images' rows per plane, which is an argument of the launch.  ``fresh``: the step without arenas, which launches other
+        entries: the key gains "fresh"."""
         key = ("slots", S, nsplit, "trunk", nsplit_trunk) if nsplit_trunk else ("slots", S, nsplit)
         if each:
             key += ("each",)
         if qcap:
             key += ("q8", qcap)
+        if fresh:
+            key += ("fresh",)
+        more = {"fresh": True} if fresh else {}
         g = self._graphs.pop(key, None)
         if g is not None:
             self._graphs[key] = g
@@ -2630,20 +2734,23 @@ class LlamaHIP:
         # advances nothing, the live words are put back behind it
         live = st["live"].clone()
         st["live"].zero_()
-        self._forward_slots(st, S, nsplit, nsplit_trunk, each, qcap)
+        self._forward_slots(st, S, nsplit, nsplit_trunk, each, qcap, **more)
         torch.cuda.synchronize()
         prime_graph_capture(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._forward_slots(st, S, nsplit, nsplit_trunk, each, qcap)
+            self._forward_slots(st, S, nsplit, nsplit_trunk, each, qcap, **more)
         st["live"].copy_(live)
         self._graphs[key] = g
         return g
 
-    def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0) -> None:
+    def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0,
+                       fresh: bool = False) -> None:
         """One decode step over S slots: the <= 16-row projections of ``_layers_norm_fused`` around per-slot RoPE + append
         and attention; logits to ``st["logits"]``, then the advance launch.  ``qcap`` > 0: the attention reads the slots' int8
-        images (``pc_attn_decode_slots_q8``) and stages the appended row into them; the arenas are appended to as always."""
+        images (``pc_attn_decode_slots_q8``) and stages the appended row into them; the arenas are appended to as always.
+        ``fresh`` (with ``qcap``): no arenas -- ``st["kv_base"]`` holds the fresh-row buffers, ``pc_rope_append_slots_q8`` writes the
+        row there and into the image, ``pc_attn_decode_slots_q8_fresh`` reads both."""
         n = _native
         dev, c = self.device, self.config
         H, Hkv, D, hid, inter = self.H, self.Hkv, self.D, c.hidden_size, c.intermediate_size
@@ -2672,8 +2779,16 @@ class LlamaHIP:
                 n.gemm_w4(lw["wqkv_c4"], lw["wqkv_e4"], S, W, hid, n.EPI_STORE, x=x, norm_weight=lw["ln1"], eps=eps, y=qkv, ldy=W)
             else:
                 n.gemm_skinny_norm(self._w16(lw, "wqkv", True), x, lw["ln1"], eps, S, W, hid, n.EPI_STORE, y=qkv, ldy=W)
-            n.rope_append_slots(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D)
-            if qcap:
+            if fresh:
+                n.rope_append_slots_q8(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li,
+                                       H, Hkv, D, st["kvq_base"], qcap, self.L)
+            else:
+                n.rope_append_slots(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H,
+                                    Hkv, D)
+            if fresh:
+                n.attn_decode_slots_q8_fresh(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
+                                             self.softmax_scale, nsplit, ws, (ah, al), st["kvq_base"], qcap, self.L)
+            elif qcap:
                 n.attn_decode_slots_q8(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
                                        self.softmax_scale, nsplit, ws, (ah, al), st["kvq_base"], qcap, self.L)
             elif nsplit_trunk:

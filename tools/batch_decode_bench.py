@@ -15,6 +15,11 @@ B (W + K) / (W + B K) from the weight bytes W a decode step streams and the K/V 
         # events around one replay, median [min .. max]; plus the accuracy record of sequence 0: max |logit_int8 - logit_fp16|
         # of the first loop step and how many of 32 greedy tokens agree.  --out merges the run into the file under its
         # weight format, so the fp16 and the MXFP4 run share one JSON.
+    python tools/batch_decode_bench.py --slot-kv int8 --slot-drop-fp16 [--weight-format mxfp4] [--out profiles/slot_kv_only_bench.json]
+        # int8-only residency (slot_loop(kv="int8", keep_arenas=False)) beside today's int8 mode, S = 8 / 16: (a)
+        # torch.cuda.memory_allocated() after the first fill for the fp16 loop, the int8 mode and int8-only -- the latter with
+        # every sequence prefilled in ONE arena, measured before the other slots' arenas exist; (b) step time, legs interleaved
+        # with the order rotating.  --out merges under "decode" / the weight format.
 """
 import argparse
 import json
@@ -143,6 +148,126 @@ def slot_kv_bench(args):
     print(json.dumps(result))
 
 
+def slot_kv_only_bench(args):
+    """--slot-kv int8 --slot-drop-fp16: memory after the first fill and step time of the int8-only loop beside today's int8 mode."""
+    import gc
+    steps, warm = max(args.new, 40), 8
+    fmt_w = args.weight_format
+    lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0, **({"weight_format": fmt_w} if fmt_w != "fp16" else {}))
+    m = lm.hf_model
+    sizes = [int(b) for b in args.batches.split(",")] if args.batches != "1,2,4,8,16" else [8, 16]
+    mem_model = torch.cuda.memory_allocated()
+    eng = CacheEngine(4096, lm, slots=max(sizes))
+    fmt = lm.get_formatter()
+    sp, pp = synth.persona_like()
+    eng.add_schema(fmt(sp))
+    prompt = Prompt(pp, [fmt])
+    mem_engine = torch.cuda.memory_allocated()                                 # model + modules + slot 0's arena
+
+    def prefill(slot):
+        ids, pos, _, cache = eng.process(prompt, slot=slot)
+        out = lm(input_ids=torch.tensor([ids], device="cuda:0"), position_ids=torch.tensor([pos], device="cuda:0"),
+                 past_key_values=cache, use_cache=True)
+        past = out.past_key_values
+        return past, past.arena.length, int(torch.argmax(out.logits[0, -1])), max(pos) + 2
+
+    def forget():                                                              # the loop states (images, fresh rows) and their graphs
+        m.__dict__.pop("_slot_sts", None)
+        m._graphs.clear()
+        gc.collect()
+
+    arena_bytes = eng.prompt_cache.arena.buf.numel() * 2
+    mem = {}
+    for S in sizes:                                                            # (a) int8-only first: one arena exists
+        forget()
+        loop = None
+        for k in range(S):
+            past, n0, tok, pos = prefill(0)
+            if loop is None:
+                loop = m.slot_loop([past], [tok], [pos], steps + 1, each=True, slots=S, slot_index=[0], max_keys=4096, kv="int8",
+                                   keep_arenas=False)
+            else:
+                loop.admit(k, past, tok, pos, steps + 1, None, 0, (), ())
+            del past
+        torch.cuda.synchronize()
+        mem[S] = {"int8_only": {"allocated": torch.cuda.memory_allocated(), "slot_kv_bytes": loop.slot_kv_bytes(),
+                                "beyond_engine": torch.cuda.memory_allocated() - mem_engine}}
+        loop.close({})
+        del loop
+    forget()
+    pre = [prefill(k) for k in range(max(sizes))]                              # now every slot's arena exists
+    keys = pre[0][1]
+    for S in sizes:
+        for kv in ("fp16", "int8"):
+            forget()
+            loop = m.slot_loop([p[0] for p in pre[:S]], [p[2] for p in pre[:S]], [p[3] for p in pre[:S]], steps + 1, each=True, slots=S,
+                               max_keys=4096, kv=kv)
+            torch.cuda.synchronize()
+            # (arenas of slots S.. exist by now at the smaller S: counted out)
+            extra = (max(sizes) - S) * arena_bytes
+            mem[S][kv] = {"allocated": torch.cuda.memory_allocated() - extra, "slot_kv_bytes": loop.slot_kv_bytes(),
+                          "beyond_engine": torch.cuda.memory_allocated() - extra - mem_engine}
+            loop.close({})
+            del loop
+    forget()
+    row_bytes = m.L * 2 * m.Hkv * m.D * 2
+    result = {"shape": "llama2-7b (random init)", "weight_format": fmt_w, "prompt": f"persona schema, {keys} keys per slot after the prefill",
+              "steps": steps, "warm_steps_dropped": warm, "repeats": args.repeats, "arena_rows": 4096,
+              "memory_how": "torch.cuda.memory_allocated() with the loop built and every sequence entered (each=True, max_keys 4096); "
+                            "beyond_engine: minus model + schema modules + slot 0's arena; int8_only measured before the arenas of slots "
+                            "1.. exist, the other two with the arenas of slots beyond S counted out",
+              "allocated_model": mem_model, "allocated_model_modules_one_arena": mem_engine, "arena_bytes": arena_bytes,
+              "kv_row_bytes_fp16": row_bytes,
+              "how": "SlotLoop stepped by hand, greedy; ms per replay from the HIP events around it (SlotLoop.elapsed_ms), steps "
+                     f"{warm}..{steps - 1} of every repetition; legs interleaved, order rotating; median [min .. max]", "rows": {}}
+
+    def leg(S, only):
+        pasts = []
+        for past, n0, _, _ in pre[:S]:
+            past.arena.length = n0
+            pasts.append(past)
+        loop = m.slot_loop(pasts, [t for _, _, t, _ in pre[:S]], [p for _, _, _, p in pre[:S]], steps + 1, kv="int8",
+                           **({"keep_arenas": False} if only else {}))
+        try:
+            for _ in range(steps):
+                loop.enqueue()
+            toks = [loop.token(0, i) for i in range(steps)]
+            ms = [loop.elapsed_ms(i) for i in range(warm, steps)]
+        finally:
+            loop.close([0] * S)
+        return ms, toks
+
+    for S in sizes:
+        times = {"int8": [], "int8_only": []}
+        same = None
+        for r in range(args.repeats + 1):                                       # (repetition 0 captures the graphs: dropped)
+            order = ["int8", "int8_only"] if r % 2 == 0 else ["int8_only", "int8"]
+            got = {name: leg(S, name == "int8_only") for name in order}
+            if r == 0:
+                same = got["int8"][1] == got["int8_only"][1]
+                continue
+            for name in order:
+                times[name] += got[name][0]
+        row = {name + "_ms": {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "n": len(v)}
+               for name, v in times.items()}
+        row["int8_only_median_within_int8_max"] = row["int8_only_ms"]["median"] <= row["int8_ms"]["max"]
+        row["tokens_of_sequence_0_equal"] = same
+        row["memory"] = mem[S]
+        row["arithmetic_bytes"] = {"fp16": S * 4096 * row_bytes, "int8": S * 4096 * row_bytes + S * 4096 * (row_bytes // 2 // m.D) * (m.D + 4),
+                                   "int8_only": S * 4096 * (row_bytes // 2 // m.D) * (m.D + 4) + S * row_bytes + 4096 * row_bytes}
+        result["rows"][str(S)] = row
+        print(json.dumps({str(S): row}), file=sys.stderr, flush=True)
+    if args.out:
+        merged = {}
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                merged = json.loads(fh.read() or "{}")
+        merged.setdefault("decode", {})["weights_" + fmt_w] = result
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(merged, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--new", type=int, default=64, help="greedy tokens per sequence")
@@ -152,10 +277,15 @@ def main():
     ap.add_argument("--share-trunk", action="store_true", help="add leg (c): generate_batch(share_trunk=True)")
     ap.add_argument("--slot-kv", choices=("fp16", "int8"), default="fp16",
                     help="int8: measure the slot loop over int8 K/V images beside the fp16 slot loop (S = 4 / 8 / 16, or --batches)")
+    ap.add_argument("--slot-drop-fp16", action="store_true",
+                    help="with --slot-kv int8: measure int8-only residency (keep_arenas=False) beside today's int8 mode: memory and step time")
     ap.add_argument("--weight-format", choices=("fp16", "mxfp4"), default="fp16", help="with --slot-kv int8: the decoder weights")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "batch_decode_bench measures on the GPU"
+    if args.slot_drop_fp16:
+        assert args.slot_kv == "int8", "--slot-drop-fp16 needs --slot-kv int8"
+        return slot_kv_only_bench(args)
     if args.slot_kv == "int8":
         return slot_kv_bench(args)
     batches = [int(b) for b in args.batches.split(",")]

@@ -48,13 +48,13 @@ def waves(ge, eng, prompts, lens, slots):
     return time.perf_counter() - t0, sum(lens), replays
 
 
-def served(ge, eng, prompts, lens, lookup=0):
-    """(b): serve.  -> (seconds, tokens decoded, replays, idle-row fraction)."""
+def served(ge, eng, prompts, lens, lookup=0, **kw):
+    """(b): serve (``kw``: further arguments of ``serve``).  -> (seconds, tokens decoded, replays, idle-row fraction)."""
     base = GenerationParameters(temperature=0.0, stop_token_ids=[], stop_str=[])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _r, _out in ge.serve(eng, ((p, dataclasses.replace(base, max_new_tokens=n)) for p, n in zip(prompts, lens)),
-                             stream_interval=10 ** 9, lookup=lookup):
+                             stream_interval=10 ** 9, lookup=lookup, **kw):
         pass
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -102,6 +102,27 @@ def lookup_legs(ge, eng, prompts, lens, ks, repeats, slots):
             "legs": out}
 
 
+def slot_drop_legs(ge, eng, prompts, lens, repeats, slots, fmt_w):
+    """serve(slot_kv="int8") and serve(slot_kv="int8", keep_arenas=False), interleaved with the order rotating."""
+    legs = {"int8": dict(slot_kv="int8"), "int8_only": dict(slot_kv="int8", keep_arenas=False)}
+    answers = {}
+    for name, kw in legs.items():                                     # warm: both steps captured
+        served(ge, eng, prompts, lens, **kw)
+        answers[name] = {r: list(t) for r, t in ge.last_serve_tokens.items()}
+    runs = {name: [] for name in legs}
+    for r in range(repeats):
+        for name in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            dt, n, replays, _ = served(ge, eng, prompts, lens, **legs[name])
+            runs[name].append(n / dt)
+            print(f"{name}: {n / dt:.1f} tok/s, {replays} replays", file=sys.stderr, flush=True)
+    out = {name: {"tok_s": {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}}
+           for name, v in runs.items()}
+    return {"shape": "llama2-7b (random init)", "weight_format": fmt_w, "requests": len(prompts), "slots": slots, "max_new_tokens": lens,
+            "how": "greedy; decoded tokens per second over the whole serve run, prefills included; legs interleaved in one process, "
+                   f"order rotating, {repeats} repetitions", "legs": out,
+            "requests_with_equal_tokens": sum(answers["int8"][r] == answers["int8_only"][r] for r in answers["int8"])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lookup", type=int, nargs="*", default=[])
@@ -110,6 +131,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--only-serve", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--slot-drop-fp16", action="store_true",
+                    help="serve(slot_kv='int8') against serve(slot_kv='int8', keep_arenas=False); --out merges under the weight format")
     ap.add_argument("--weight-format", default="fp16", help="fp16 or mxfp4 (with PC_W4_STREAM / PC_W4_MAX_ROWS from the environment)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "serve_bench measures on the GPU"
@@ -125,6 +148,18 @@ def main():
     ge = GenerationEngine(lm)
     assert ge.serve_plan()[0], ge.serve_plan()[1]
     served(ge, eng, prompts, lens)                                    # warm: graphs captured, code objects loaded
+    if args.slot_drop_fp16:
+        res = slot_drop_legs(ge, eng, prompts, lens, args.repeats, args.slots, args.weight_format)
+        if args.out:
+            merged = {}
+            if os.path.exists(args.out):
+                with open(args.out) as fh:
+                    merged = json.loads(fh.read() or "{}")
+            merged.setdefault("serve", {})["weights_" + args.weight_format] = res
+            with open(args.out, "w") as fh:
+                fh.write(json.dumps(merged, indent=1) + "\n")
+        print(json.dumps(res))
+        return
     if args.lookup:
         line = json.dumps(lookup_legs(ge, eng, prompts, lens, args.lookup, args.repeats, args.slots))
         if args.out:
