@@ -44,7 +44,8 @@ def main():
     ap.add_argument("--slot-kv", choices=("fp16", "int8"), default=None,
                     help="with --batch / --serve: what the batched loop's attention reads (default: PC_SLOT_KV, else fp16); int8 = "
                          "int8 images of the slots' K/V rows, about half the bytes per step, the format's accuracy, and 0.516 of a "
-                         "slot buffer MORE memory per slot (the fp16 buffers stay); not with --share-trunk or --lookup")
+                         "slot buffer MORE memory per slot (the fp16 buffers stay); not with --share-trunk; with --lookup K under "
+                         "--serve only (serve(lookup=K, slot_kv='int8'): the K + 1 row step reads the images), not under --batch alone")
     ap.add_argument("--slot-drop-fp16", action="store_true",
                     help="with --serve and --slot-kv int8: no slot keeps an fp16 buffer (keep_arenas=False; default: "
                          "PC_SLOT_KEEP_ARENAS): every prompt is prefilled in one shared buffer and lives on as its int8 image")
@@ -112,12 +113,14 @@ def main():
             ids, pos, _, cache = cache_engine.process(pk, return_full_position_ids=lm.use_full_position_ids, slot=k)
             reqs.append((ids, pos, cache))
         batched, why = gen_engine.batch_plan(len(reqs), params, slot_kv=a.slot_kv)
+        # (int8 images under lookup are serve's: generate_batch refuses the pair, so this batch decodes one token per step)
+        lookup_b = 0 if a.slot_kv == "int8" and a.lookup else a.lookup
         for _pass in ("warm", "timed"):              # (the first pass captures the batched step)
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2, share_trunk=a.share_trunk,
-                                                     lookup=a.lookup, slot_kv=a.slot_kv):
+                                                     lookup=lookup_b, slot_kv=a.slot_kv):
                 lasts[k] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

@@ -805,6 +805,37 @@ int pc_attn_decode_slots_q8_fresh(const void* q_hi, const void* q_lo, int64_t q_
                                   int32_t Hkv, int32_t D, float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes,
                                   void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base, int32_t qcap, int32_t n_layers,
                                   void* stream);
+/* Prompt-lookup drafts over int8 images: the k + 1 row step of pc_rope_append_slots_rows / pc_attn_verify_slots with a slot's keys
+ * read from its image.  What the step computes is what pc_attn_decode_slots_q8 computes one token at a time: the token at
+ * position p attends to rows [0, p) as IMAGE rows and to its own row p exactly -- so draft row i of a slot with length len sees
+ * image keys [0, len + i), rows len .. len + i - 1 of which this step's append has just quantised, and key len + i in fp16.  The
+ * result does not depend on where step boundaries fall.  `fresh` (0 | 1, uniform over a launch) says where the fp16 rows of the
+ * step live: 0 = arena rows len + i behind kv_base[b] (plane stride cap[b]), 1 = a fresh-row buffer behind kv_base[b], fp16
+ * [P][k + 1][128], row i.  A slot runs when it is live, 0 <= len, len + k + 1 <= cap[b] AND len + k + 1 <= qcap; any other slot
+ * is left alone by both launches (the host keeps qcap >= len + k + 1 for every slot whose cap word lets it run).
+ * pc_rope_append_slots_rows_q8: pc_rope_append_slots_rows' arguments plus kvq_base / qcap / n_layers / fresh, grid (draft row,
+ * slot).  q_hi / q_lo and the fp16 K / V rows are pc_rope_append_slots_rows' bits (both in_layout values); every row also goes,
+ * quantised with the arithmetic of pc_kv_quant_q8 bit for bit, to image row len + i (codes and scale).  Nothing else is written.
+ * At k = 0, fresh = 1 it is pc_rope_append_slots_q8.  PC_ERR_ARG with nothing launched: what either parent refuses, head_dim !=
+ * 128, k outside 0..15, S * (k + 1) > 64, fresh outside 0..1.
+ * pc_attn_verify_slots_q8: pc_attn_verify_slots' arguments plus the same four.  Grid, tile columns and per-wave key slices are
+ * that entry's, cut from the len + k image keys; codes enter the fp16 MFMA as fp16 values (exact), the K scale multiplies the
+ * score together with the softmax scale, the V scale is folded into p in fp32 before p is split; code * scale is never rounded to
+ * fp16.  The exact key is one more record per (row, head), index nsplit: m = q . k * scale * log2 e, l = 1, O = v, written by the
+ * workgroups of split 0; the merge launch takes nsplit + 1 records, so the workspace is
+ * pc_attn_verify_slots_q8_workspace_bytes.  The launch writes no image byte; a (slot, row, head) depends on that slot's words,
+ * k and nsplit only.  PC_ERR_ARG with nothing launched: what pc_attn_decode_slots_q8 or pc_attn_verify_slots refuses, fresh
+ * outside 0..1. */
+int pc_rope_append_slots_rows_q8(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
+                                 const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len,
+                                 const int32_t* live, int32_t S, int32_t k, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                                 const uint64_t* kvq_base, int32_t qcap, int32_t n_layers, int32_t fresh, void* stream);
+int64_t pc_attn_verify_slots_q8_workspace_bytes(int32_t S, int32_t k, int32_t H, int32_t D, int32_t nsplit);
+int pc_attn_verify_slots_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base, const int32_t* cap,
+                            const int32_t* len, const int32_t* live, int32_t S, int32_t k, int32_t layer, int32_t H, int32_t Hkv,
+                            int32_t D, float softmax_scale, int32_t nsplit, void* workspace, int64_t workspace_bytes,
+                            void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base, int32_t qcap, int32_t n_layers,
+                            int32_t fresh, void* stream);
 int pc_rope_append_slots(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
                          const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live,
                          int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, void* stream);

@@ -226,7 +226,8 @@ void launch_trunk(const SlotAttnArgs& a, hipStream_t st) {
 template <int D>
 void launch_merge(const SlotAttnArgs& a, bool trunk, hipStream_t st) {
     hipLaunchKernelGGL((pcr::attn_merge_slots_kernel<D>), dim3(a.H, a.S * (a.k + 1)), dim3(D), 0, st, a.part_o, a.part_ml, a.cap,
-                       a.len, a.live, trunk ? a.leader : nullptr, a.trunk, a.kv_base, a.S, a.k, a.H, a.ns_trunk, a.ns_trunk + a.ns_own, a.of_hi, a.of_lo);
+                       a.len, a.live, trunk ? a.leader : nullptr, a.trunk, a.kv_base, a.S, a.k, a.H, a.ns_trunk,
+                       a.ns_trunk + a.ns_own + a.ns_extra, a.of_hi, a.of_lo);
 }
 
 bool rows_shape_ok(int S, int k) { return S >= 1 && S <= 16 && k >= 0 && k <= 15 && S * (k + 1) <= kMaxRows; }
@@ -246,7 +247,8 @@ int slot_attn_prepare(const char* name, bool rows, bool trunk, int ws_align, Slo
     PC_REQUIRE(a.q_ts % 8 == 0 && (!rows || a.q_ts >= (int64_t)a.H * D) && ((uintptr_t)a.q_hi & 15) == 0 && ((uintptr_t)a.q_lo & 15) == 0 &&
                    (a.H * D) % 32 == 0, PC_ERR_ARG,
                "%s: q rows must keep 16-byte alignment and H * head_dim be a multiple of 32", name);
-    const int64_t nrec = (int64_t)a.S * (a.k + 1) * a.H * (a.ns_own + a.ns_trunk);     // (what <name>_workspace_bytes counts)
+    // (what <name>_workspace_bytes counts; ns_extra: pc_attn_verify_slots_q8's exact-key record)
+    const int64_t nrec = (int64_t)a.S * (a.k + 1) * a.H * (a.ns_own + a.ns_trunk + a.ns_extra);
     PC_REQUIRE(workspace_bytes >= nrec * (D + 2) * (int64_t)sizeof(float) && ((uintptr_t)workspace & (ws_align - 1)) == 0, PC_ERR_ARG,
                "%s: workspace too small (%s_workspace_bytes) or misaligned", name, name);
     a.scale_log2 = softmax_scale * 1.4426950408889634f;

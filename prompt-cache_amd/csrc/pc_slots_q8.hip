@@ -31,6 +31,12 @@
 // slot's FRESH-ROW buffer, fp16 [P][D] (plane stride D): the append launch writes the step's K / V row there AND quantises it into
 // image row len (rope_append_slots_q8_kernel), and the attention -- the kernel above with `fresh` set -- reads the exact row from
 // kv_base[b] + plane * D and stages nothing.  cap[b] is still the bound on len.
+//
+// Prompt-lookup drafts over images (pc_rope_append_slots_rows_q8 / pc_attn_verify_slots_q8, model/llama_hip.py LookupSlotLoopQ8):
+// the step of pc_lookup_slots.hip, k + 1 rows per slot.  The append launch writes every row as fp16 (arena row len + i, or row i
+// of a fresh-row buffer that is now [P][k + 1][D]) AND as image row len + i; the attention gives draft row i the image keys
+// [0, len + i) and its own key exact -- what the one-row step above computes for the token at that position, whatever the step
+// boundaries and however many drafts were accepted.
 #include <hip/hip_fp16.h>
 #include <math.h>
 
@@ -55,25 +61,29 @@ constexpr int kU = 4;                // keys in flight per group
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-// ---- RoPE + append without an arena, one workgroup per slot -------------------------------------------------------------------
-// q: the work items and the arithmetic of rope_append_slots_rows_kernel at k = 0 (pcr::rope_pairs8), bit for bit.  K / V: a row of
+// ---- RoPE + append of k + 1 rows per slot into image and fp16 row, one workgroup per (draft row, slot) ------------------------
+// (pc_rope_append_slots_rows_q8; pc_rope_append_slots_q8 is its k = 0, fresh = 1 case.)  A slot runs under lookup_slot_runs and
+// with len + k + 1 <= qcap; row r = b (k + 1) + i of the projection is rotated with row r of the table.
+// q: the work items and the arithmetic of rope_append_slots_rows_kernel (pcr::rope_pairs8), bit for bit.  K / V: a row of
 // a kv head is held by 8 consecutive lanes, lane `sub` with features [8 sub, 8 sub + 8) and [64 + 8 sub, 64 + 8 sub + 8) -- K as
 // that kernel's rotary work item has them, V loaded the same way --, rounded to fp16 as that kernel rounds what it stores.  The
-// fp16 row goes to plane (layer * 2) * Hkv + h (K) / + Hkv (V) of the fresh-row buffer kv_base[b] (plane stride D), and through
-// pcq::quant_row16 -- the row maximum is an exchange among the 8 lanes; a code depends on its value and that maximum only -- into
-// image row len: this lane's first two code dwords are bytes [8 sub, 8 sub + 8) of the row, the other two bytes [64 + 8 sub, ..).
+// fp16 row of plane (layer * 2) * Hkv + h (K) / + Hkv (V) goes -- `fresh` is uniform over the launch -- to row i of the fresh-row
+// buffer kv_base[b] (fp16 [P][k + 1][D]) or to arena row len + i (plane stride cap[b]), and through pcq::quant_row16 -- the row
+// maximum is an exchange among the 8 lanes; a code depends on its value and that maximum only -- into image row len + i: this
+// lane's first two code dwords are bytes [8 sub, 8 sub + 8) of the row, the other two bytes [64 + 8 sub, ..).
 __global__ __launch_bounds__(kThreads) void rope_append_slots_q8_kernel(
     const float* __restrict__ qkv, int64_t ld, int layout, _Float16* __restrict__ q_hi, _Float16* __restrict__ q_lo, int64_t q_ts,
     const float2* __restrict__ cs, const uint64_t* __restrict__ kv_base, const uint64_t* __restrict__ kvq_base,
-    const int32_t* __restrict__ cap, const int32_t* __restrict__ len, const int32_t* __restrict__ live, int layer, int n_layers, int H,
-    int Hkv, int qcap) {
-    const int b = blockIdx.x;
-    if (live[b] == 0) return;
-    const int past = len[b];
-    if (past < 0 || past >= cap[b] || past >= qcap) return;     // (nothing of this slot is written anywhere)
+    const int32_t* __restrict__ cap, const int32_t* __restrict__ len, const int32_t* __restrict__ live, int k, int layer, int n_layers,
+    int H, int Hkv, int qcap, int fresh_rows) {
+    const int i = blockIdx.x, b = blockIdx.y;
+    if (!lookup_slot_runs(cap, len, live, b, k)) return;
+    if (len[b] + k + 1 > qcap) return;                          // (nothing of this slot is written anywhere)
+    const int past = len[b] + i;                                // (< cap and < qcap)
+    const int rr = b * (k + 1) + i;
     constexpr int half = kD / 2;
-    const float2* csr = cs + (int64_t)b * half;
-    const float* row = qkv + (int64_t)b * ld;
+    const float2* csr = cs + (int64_t)rr * half;
+    const float* row = qkv + (int64_t)rr * ld;
     for (int it = threadIdx.x; it < H * kLPK; it += kThreads) {
         const int h = it / kLPK, ch = it - h * kLPK;
         const float* src = row + (int64_t)h * kD;
@@ -82,8 +92,8 @@ __global__ __launch_bounds__(kThreads) void rope_append_slots_q8_kernel(
         load8(src + (layout ? ch * 16 + 8 : half + ch * 8), hi);
         h8 olo, ohi, rlo, rhi;
         pcr::rope_pairs8(lo, hi, csr + ch * 8, olo, ohi, rlo, rhi);
-        _Float16* dh = q_hi + (int64_t)b * q_ts + (int64_t)h * kD;
-        _Float16* dl = q_lo + (int64_t)b * q_ts + (int64_t)h * kD;
+        _Float16* dh = q_hi + (int64_t)rr * q_ts + (int64_t)h * kD;
+        _Float16* dl = q_lo + (int64_t)rr * q_ts + (int64_t)h * kD;
         *(h8*)(dh + ch * 8) = olo;
         *(h8*)(dh + half + ch * 8) = ohi;
         *(h8*)(dl + ch * 8) = rlo;
@@ -93,7 +103,10 @@ __global__ __launch_bounds__(kThreads) void rope_append_slots_q8_kernel(
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int sub = lane % kLPK, nrow = 2 * Hkv;
     const int64_t plane0 = (int64_t)(layer * 2) * Hkv;
+    // where plane p's fp16 row lies: fresh + p * pstride + roff
     _Float16* fresh = (_Float16*)(uintptr_t)kv_base[b];
+    const int64_t pstride = fresh_rows ? (int64_t)(k + 1) * kD : (int64_t)cap[b] * kD;
+    const int64_t roff = fresh_rows ? (int64_t)i * kD : (int64_t)past * kD;
     char* img = (char*)(uintptr_t)kvq_base[b];
     float* sbase = (float*)(img + (int64_t)n_layers * 2 * Hkv * qcap * kD);
     for (int r0 = wave * kGPW; r0 < nrow; r0 += 4 * kGPW) {     // (wave-uniform trip count: every lane runs the exchanges)
@@ -123,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void rope_append_slots_q8_kernel(
         float qs;
         pcq::quant_row16(x, 3, w, qs);
         if (on) {
-            _Float16* fp = fresh + (plane0 + r) * kD;
+            _Float16* fp = fresh + (plane0 + r) * pstride + roff;
             *(h8*)(fp + sub * 8) = olo;
             *(h8*)(fp + half + sub * 8) = ohi;
             char* cp = img + ((plane0 + r) * qcap + past) * kD;
@@ -302,6 +315,76 @@ __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
     }
 }
 
+// ---- k + 1 causally ordered query rows per slot over the int8 image (pc_attn_verify_slots_q8) ----------------------------------
+// attn_verify_slots_kernel<128, 1> (pc_lookup_slots.hip) with the tile loop reading codes (pcr::attn_rows_tiles_q8): grid (split,
+// kv head x pass, slot), a tile column is (draft row i, query head g of the kv head), 16 per pass.  The IMAGE keys of the slot
+// are [0, len + k) -- rows len .. len + k - 1 are what pc_rope_append_slots_rows_q8 has just quantised -- and column (i, .) sees
+// those below len + i: every key in front of its own, quantised, however the rows were spread over steps.  The wave slices are cut
+// from len + k.  Its OWN key, len + i, is exact: the workgroups of split 0 leave it as one more record per (row, head), index
+// nsplit behind the nsplit records of the slices: m = q . k * scale_log2 with q = (float)hi + (float)lo, the 128 products summed
+// in fp32 as a wave's xor tree over lane pairs (an order D alone fixes), l = 1, O = v.  k / v: arena row len + i, or row i of the
+// fresh-row buffer (`fresh_rows`, uniform over the launch).  Every record is written by exactly one workgroup and read by the
+// merge launch only; no image byte is written.
+__global__ __launch_bounds__(kThreads, 2) void attn_verify_slots_q8_kernel(
+    const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo, int64_t q_ts, const uint64_t* __restrict__ kv_base,
+    const uint64_t* __restrict__ kvq_base, const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
+    const int32_t* __restrict__ live, int k, int layer, int n_layers, int H, int Hkv, int qcap, float scale_log2, int nsplit,
+    float* __restrict__ part_o, float* __restrict__ part_ml, int fresh_rows) {
+    __shared__ __attribute__((aligned(16))) char smem[pcr::rows_lds_bytes<kD, 1>()];
+    const int lane = threadIdx.x & 63, n = lane & 15, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int split = blockIdx.x, b = blockIdx.z;
+    if (!lookup_slot_runs(cap, len, live, b, k)) return;
+    const int past = len[b], cb = cap[b];
+    if (past + k + 1 > qcap) return;                 // out of contract: nothing leaves the image
+    const int G = H / Hkv, cols = (k + 1) * G, passes = (cols + 15) / 16;
+    const int kvh = blockIdx.y / passes, col0 = (blockIdx.y - kvh * passes) * 16;
+    const int nimg = past + k;                       // image keys of the slot (< qcap)
+    const int nrec = nsplit + 1;
+
+    int64_t qoff[1], rec[1];
+    bool pad[1];
+    int lim[1];
+    {
+        const int c = col0 + n;
+        pad[0] = c >= cols;
+        const int di = pad[0] ? 0 : c / G, gh = pad[0] ? 0 : c - di * G;
+        lim[0] = pad[0] ? 0 : past + di;
+        qoff[0] = (int64_t)(b * (k + 1) + di) * q_ts + (int64_t)(kvh * G + gh) * kD;
+        rec[0] = ((int64_t)(b * (k + 1) + di) * H + kvh * G + gh) * nrec + split;
+    }
+    int cpw = (nimg + nsplit * 4 - 1) / (nsplit * 4);              // keys per wave
+    cpw = (cpw + 15) & ~15;
+    const int k0 = (split * 4 + wave) * cpw;
+    const int k1 = (k0 + cpw < nimg) ? k0 + cpw : nimg;
+
+    const int64_t kplane = (int64_t)(layer * 2) * Hkv + kvh, vplane = kplane + Hkv;
+    const char* img = (const char*)(uintptr_t)kvq_base[b];
+    const float* sbase = (const float*)(img + (int64_t)n_layers * 2 * Hkv * qcap * kD);
+    pcr::attn_rows_tiles_q8<1>(q_hi, q_lo, qoff, pad, lim, rec, img + kplane * qcap * kD, img + vplane * qcap * kD,
+                               sbase + kplane * qcap, sbase + vplane * qcap, k0, k1, scale_log2, smem, part_o, part_ml);
+
+    if (split != 0) return;
+    // the exact key of every column of this pass: one column per wave turn, two features per lane
+    const _Float16* ex = (const _Float16*)(uintptr_t)kv_base[b];
+    for (int cc = wave; cc < 16; cc += 4) {
+        const int c = col0 + cc;
+        if (c >= cols) break;                                       // (wave-uniform)
+        const int di = c / G, h = kvh * G + (c - di * G), row = b * (k + 1) + di;
+        const int64_t ko = (fresh_rows ? kplane * (k + 1) + di : kplane * cb + past + di) * kD + lane * 2;
+        const int64_t vo = (fresh_rows ? vplane * (k + 1) + di : vplane * cb + past + di) * kD + lane * 2;
+        const int64_t qo = (int64_t)row * q_ts + (int64_t)h * kD + lane * 2;
+        const pca::h2 qh = *(const pca::h2*)(q_hi + qo), ql = *(const pca::h2*)(q_lo + qo);
+        const pca::h2 kx = *(const pca::h2*)(ex + ko), vx = *(const pca::h2*)(ex + vo);
+        float d = ((float)qh[0] + (float)ql[0]) * (float)kx[0];
+        d = fmaf((float)qh[1] + (float)ql[1], (float)kx[1], d);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) d += __shfl_xor(d, o);
+        const int64_t r = ((int64_t)row * H + h) * nrec + nsplit;
+        *(float2*)(part_o + r * kD + lane * 2) = make_float2((float)vx[0], (float)vx[1]);
+        if (lane == 0) { part_ml[r * 2] = d * scale_log2; part_ml[r * 2 + 1] = 1.0f; }
+    }
+}
+
 }  // namespace
 
 namespace {
@@ -345,22 +428,73 @@ PC_EXPORT int pc_attn_decode_slots_q8_fresh(const void* q_hi, const void* q_lo, 
                          softmax_scale, nsplit, workspace, workspace_bytes, out_frag_hi, out_frag_lo, kvq_base, qcap, n_layers, stream);
 }
 
+namespace {
+
+// Both append entries: pc_rope_append_slots_q8 is k = 0 with the fresh-row buffer.
+int rope_append_q8(const char* name, const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
+                   const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S,
+                   int32_t k, int32_t layer, int32_t H, int32_t Hkv, int32_t D, const uint64_t* kvq_base, int32_t qcap,
+                   int32_t n_layers, int32_t fresh, void* stream) {
+    PC_REQUIRE(S >= 1 && S <= 16 && k >= 0 && k <= 15 && S * (k + 1) <= 64 && layer >= 0 && H > 0 && Hkv > 0, PC_ERR_ARG,
+               "%s: bad sizes (1 <= S <= 16, 0 <= k <= 15, S * (k + 1) <= 64)", name);
+    PC_REQUIRE(D == kD, PC_ERR_ARG, "%s: head_dim must be 128", name);
+    PC_REQUIRE(qkv && q_hi && q_lo && cs && kv_base && cap && len && live && kvq_base, PC_ERR_ARG, "%s: null pointer", name);
+    PC_REQUIRE(in_layout == 0 || in_layout == 1, PC_ERR_ARG, "%s: in_layout is 0 (natural) or 1 (rotary-pair tiles)", name);
+    PC_REQUIRE(fresh == 0 || fresh == 1, PC_ERR_ARG, "%s: fresh is 0 (arena rows) or 1 (fresh-row buffers)", name);
+    PC_REQUIRE(qcap >= 1 && n_layers >= 1 && layer < n_layers, PC_ERR_ARG,
+               "%s: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)", name);
+    PC_REQUIRE(ld >= (int64_t)(H + 2 * Hkv) * D && ld % 4 == 0 && q_token_stride % 8 == 0 && ((uintptr_t)qkv & 15) == 0 &&
+                   ((uintptr_t)q_hi & 15) == 0 && ((uintptr_t)q_lo & 15) == 0,
+               PC_ERR_ARG, "%s: rows must keep 16-byte alignment", name);
+    hipLaunchKernelGGL(rope_append_slots_q8_kernel, dim3(k + 1, S), dim3(kThreads), 0, (hipStream_t)stream, qkv, ld, in_layout,
+                       (_Float16*)q_hi, (_Float16*)q_lo, q_token_stride, (const float2*)cs, kv_base, kvq_base, cap, len, live, k, layer,
+                       n_layers, H, Hkv, qcap, fresh);
+    return pc_check_launch("rope_append_slots_q8_kernel");
+}
+
+}  // namespace
+
 PC_EXPORT int pc_rope_append_slots_q8(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo, int64_t q_token_stride,
                                       const float* cs, const uint64_t* kv_base, const int32_t* cap, const int32_t* len,
                                       const int32_t* live, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
                                       const uint64_t* kvq_base, int32_t qcap, int32_t n_layers, void* stream) {
-    PC_REQUIRE(S >= 1 && S <= 16 && layer >= 0 && H > 0 && Hkv > 0, PC_ERR_ARG, "pc_rope_append_slots_q8: bad sizes (1 <= S <= 16)");
-    PC_REQUIRE(D == kD, PC_ERR_ARG, "pc_rope_append_slots_q8: head_dim must be 128");
-    PC_REQUIRE(qkv && q_hi && q_lo && cs && kv_base && cap && len && live && kvq_base, PC_ERR_ARG,
-               "pc_rope_append_slots_q8: null pointer");
-    PC_REQUIRE(in_layout == 0 || in_layout == 1, PC_ERR_ARG,
-               "pc_rope_append_slots_q8: in_layout is 0 (natural) or 1 (rotary-pair tiles)");
+    return rope_append_q8("pc_rope_append_slots_q8", qkv, ld, in_layout, q_hi, q_lo, q_token_stride, cs, kv_base, cap, len, live, S, 0,
+                          layer, H, Hkv, D, kvq_base, qcap, n_layers, 1, stream);
+}
+
+PC_EXPORT int pc_rope_append_slots_rows_q8(const float* qkv, int64_t ld, int32_t in_layout, void* q_hi, void* q_lo,
+                                           int64_t q_token_stride, const float* cs, const uint64_t* kv_base, const int32_t* cap,
+                                           const int32_t* len, const int32_t* live, int32_t S, int32_t k, int32_t layer, int32_t H,
+                                           int32_t Hkv, int32_t D, const uint64_t* kvq_base, int32_t qcap, int32_t n_layers,
+                                           int32_t fresh, void* stream) {
+    return rope_append_q8("pc_rope_append_slots_rows_q8", qkv, ld, in_layout, q_hi, q_lo, q_token_stride, cs, kv_base, cap, len, live, S,
+                          k, layer, H, Hkv, D, kvq_base, qcap, n_layers, fresh, stream);
+}
+
+PC_EXPORT int64_t pc_attn_verify_slots_q8_workspace_bytes(int32_t S, int32_t k, int32_t H, int32_t D, int32_t nsplit) {
+    if (S < 1 || k < 0 || H < 1 || D < 1 || nsplit < 1) return 0;
+    return (int64_t)S * (k + 1) * H * (nsplit + 1) * (D + 2) * (int64_t)sizeof(float);
+}
+
+PC_EXPORT int pc_attn_verify_slots_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                                      const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t k, int32_t layer,
+                                      int32_t H, int32_t Hkv, int32_t D, float softmax_scale, int32_t nsplit, void* workspace,
+                                      int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base,
+                                      int32_t qcap, int32_t n_layers, int32_t fresh, void* stream) {
+    const char* name = "pc_attn_verify_slots_q8";
+    PC_REQUIRE(D == kD, PC_ERR_ARG, "%s: head_dim must be 128", name);
+    PC_REQUIRE(kvq_base != nullptr, PC_ERR_ARG, "%s: null pointer", name);
     PC_REQUIRE(qcap >= 1 && n_layers >= 1 && layer < n_layers, PC_ERR_ARG,
-               "pc_rope_append_slots_q8: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)");
-    PC_REQUIRE(ld >= (int64_t)(H + 2 * Hkv) * D && ld % 4 == 0 && q_token_stride % 8 == 0 && ((uintptr_t)qkv & 15) == 0 &&
-                   ((uintptr_t)q_hi & 15) == 0 && ((uintptr_t)q_lo & 15) == 0,
-               PC_ERR_ARG, "pc_rope_append_slots_q8: rows must keep 16-byte alignment");
-    hipLaunchKernelGGL(rope_append_slots_q8_kernel, dim3(S), dim3(kThreads), 0, (hipStream_t)stream, qkv, ld, in_layout, (_Float16*)q_hi,
-                       (_Float16*)q_lo, q_token_stride, (const float2*)cs, kv_base, kvq_base, cap, len, live, layer, n_layers, H, Hkv, qcap);
-    return pc_check_launch("rope_append_slots_q8_kernel");
+               "%s: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)", name);
+    PC_REQUIRE(fresh == 0 || fresh == 1, PC_ERR_ARG, "%s: fresh is 0 (arena rows) or 1 (fresh-row buffers)", name);
+    // one record more per (row, head) than pc_attn_verify_slots: the exact key's
+    SlotAttnArgs a = {(const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len, live, nullptr, nullptr,
+                      S, k, layer, H, Hkv, 0.f, nsplit, 0, nullptr, nullptr, (_Float16*)out_frag_hi, (_Float16*)out_frag_lo, 1};
+    if (const int rc = pcr::slot_attn_prepare(name, true, false, 16, a, D, softmax_scale, workspace, workspace_bytes)) return rc;
+    const int passes = pc_ceil_div((a.k + 1) * (a.H / a.Hkv), 16);
+    hipLaunchKernelGGL(attn_verify_slots_q8_kernel, dim3(a.ns_own, a.Hkv * passes, a.S), dim3(kThreads), 0, (hipStream_t)stream, a.q_hi,
+                       a.q_lo, a.q_ts, a.kv_base, kvq_base, a.cap, a.len, a.live, a.k, a.layer, n_layers, a.H, a.Hkv, qcap, a.scale_log2,
+                       a.ns_own, a.part_o, a.part_ml, fresh);
+    pcr::launch_attn_merge_slots(a, D, false, (hipStream_t)stream);
+    return pc_check_launch("attn_verify_slots_q8_kernel");
 }

@@ -233,6 +233,11 @@ SIGNATURES = {
                                                 _vp, _vp, _vp, _i32, _i32, _vp]),
     "pc_rope_append_slots_q8": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
                                           _i32, _i32, _vp]),
+    "pc_rope_append_slots_rows_q8": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
+                                               _i32, _vp, _i32, _i32, _i32, _vp]),
+    "pc_attn_verify_slots_q8_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
+    "pc_attn_verify_slots_q8": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i64,
+                                          _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "pc_attn_decode_slots_trunk_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "pc_attn_decode_slots_trunk": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
                                              _vp, _i64, _vp, _vp, _vp]),
@@ -1096,6 +1101,37 @@ def attn_verify_slots(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int,
                                      workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
                                      current_stream() if stream is None else stream)
     check(rc, "pc_attn_verify_slots")
+
+
+def rope_append_slots_rows_q8(qkv, ld: int, in_layout: int, q_hi, q_lo, q_ts: int, cs, kv_base, cap, length, live, S: int, k: int,
+                              layer: int, H: int, Hkv: int, D: int, kvq_base, qcap: int, n_layers: int, fresh: bool,
+                              stream: Optional[int] = None) -> None:
+    """``rope_append_slots_rows`` that also quantises every row into image row ``len + i`` of ``kvq_base``'s images
+    (pc_rope_append_slots_rows_q8).  ``fresh``: the fp16 rows go to the fresh-row buffers behind ``kv_base`` (fp16
+    ``[n_layers * 2 * Hkv][k + 1][D]``) instead of arena rows ``len + i``."""
+    rc = load().pc_rope_append_slots_rows_q8(qkv.data_ptr(), ld, in_layout, q_hi.data_ptr(), q_lo.data_ptr(), q_ts, cs.data_ptr(),
+                                             kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(), live.data_ptr(), S, k, layer, H,
+                                             Hkv, D, kvq_base.data_ptr(), qcap, n_layers, int(fresh),
+                                             current_stream() if stream is None else stream)
+    check(rc, "pc_rope_append_slots_rows_q8")
+
+
+def attn_verify_slots_q8_workspace_bytes(S: int, k: int, H: int, D: int, nsplit: int) -> int:
+    return int(load().pc_attn_verify_slots_q8_workspace_bytes(S, k, H, D, nsplit))
+
+
+def attn_verify_slots_q8(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, S: int, k: int, layer: int, H: int, Hkv: int, D: int,
+                         softmax_scale: float, nsplit: int, workspace, out_frag, kvq_base, qcap: int, n_layers: int, fresh: bool,
+                         stream: Optional[int] = None) -> None:
+    """``attn_verify_slots`` over int8 images behind ``rope_append_slots_rows_q8`` (pc_attn_verify_slots_q8): draft row i sees image
+    keys ``[0, len + i)`` and its own key exact, from arena row ``len + i`` or (``fresh``) row i of the fresh-row buffer ->
+    fragment planes (hi, lo)."""
+    rc = load().pc_attn_verify_slots_q8(q_hi.data_ptr(), q_lo.data_ptr(), q_ts, kv_base.data_ptr(), cap.data_ptr(), length.data_ptr(),
+                                        live.data_ptr(), S, k, layer, H, Hkv, D, softmax_scale, nsplit, workspace.data_ptr(),
+                                        workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(), out_frag[1].data_ptr(),
+                                        kvq_base.data_ptr(), qcap, n_layers, int(fresh),
+                                        current_stream() if stream is None else stream)
+    check(rc, "pc_attn_verify_slots_q8")
 
 
 def attn_verify_slots_trunk_workspace_bytes(S: int, k: int, H: int, D: int, nsplit_own: int, nsplit_trunk: int) -> int:

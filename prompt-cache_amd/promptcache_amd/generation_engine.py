@@ -382,15 +382,18 @@ class GenerationEngine:
             return "PC_DEVICE_SAMPLE=0"
         return None
 
-    def _slot_kv(self, slot_kv: Optional[str], share_trunk: bool, lookup: int, batched: bool, why: str) -> str:
+    def _slot_kv(self, slot_kv: Optional[str], share_trunk: bool, lookup: int, batched: bool, why: str, serve: bool = False) -> str:
         """The K/V mode a batched loop runs with: the argument, else ``PC_SLOT_KV``, else "fp16".  "int8" where the loop cannot
-        run it -- ``check_slot_kv`` (model/llama_hip.py) -- raises ValueError, before anything is asked of the model."""
+        run it -- ``check_slot_kv`` (model/llama_hip.py) -- raises ValueError, before anything is asked of the model.  ``serve``:
+        the caller is ``serve``, where "int8" goes with ``lookup`` > 0 on a model that says ``lookup_slot_q8_available()``."""
         kv = os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv
         if kv != "fp16":
             from .model.llama_hip import check_slot_kv
             hf = getattr(self.lm, "hf_model", None)
+            offered = getattr(hf, "lookup_slot_q8_available", None) if serve else None
             check_slot_kv(kv, share_trunk=bool(share_trunk), lookup=int(lookup), head_dim=getattr(hf, "D", None),
-                          no_loop=self._no_batched_loop(False, False), not_batched=None if batched else why)
+                          no_loop=self._no_batched_loop(False, False), not_batched=None if batched else why,
+                          **({"lookup_q8": True} if offered is not None and offered() else {}))
         return kv
 
     @staticmethod
@@ -594,7 +597,10 @@ class GenerationEngine:
         loop runs.  With ``share_trunk`` the step reads a group's shared rows once for all draft rows of the group.  In the
         lookup form ``last_serve_stats`` gains ``tokens`` (decoded in the loop) and ``steps`` (replays).
         ``slot_kv`` (None: ``PC_SLOT_KV``, default "fp16"): ``generate_batch``'s -- "int8" serves over int8 images of the slots' rows,
-        sized from ``cache_engine.max_ctx_length``; ValueError with ``share_trunk``, ``lookup`` > 0 or where ``serve_plan`` says no.
+        sized from ``cache_engine.max_ctx_length``; ValueError with ``share_trunk`` or where ``serve_plan`` says no.  Together with
+        ``lookup`` > 0 the lookup step itself reads the images (``LlamaHIP.lookup_slot_loop(kv="int8")``): every draft
+        row attends to the quantised rows in front of it and to its own row exactly, so on identical logits the tokens are
+        ``serve(slot_kv="int8")``'s; ValueError on a model without that step (``lookup_slot_q8_available``).
         ``keep_arenas=False`` (None: ``PC_SLOT_KEEP_ARENAS``, default 1; with ``slot_kv="int8"`` only): no slot keeps an
         fp16 arena.  Every request is staged and prefilled in slot 0's buffer, whatever slot the scheduler gives it, its rows are
         quantised into the slot's image as it enters the loop (``SlotLoopQ8Only``) and the buffer is free for the next request;
@@ -603,7 +609,7 @@ class GenerationEngine:
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         lookup = min(int(os.environ.get("PC_SERVE_LOOKUP", "0")) if lookup is None else int(lookup), 15)
-        slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, *self._serve_plan())
+        slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, *self._serve_plan(), serve=True)
         drop = not self._keep_arenas(keep_arenas, slot_kv)
 
         def unpack(req):
@@ -681,7 +687,7 @@ class GenerationEngine:
 
         def build_loop():
             """The ``each=True`` loop over the sequences waiting in ``pending``."""
-            nonlocal loop
+            nonlocal loop, read_k
             slots_ = [st.slot for st in pending]
             trunks = sched.group_first_fill(slots_, [st.past.arena.layout for st in pending]) if share_trunk else None
             # (loop_args per sequence -> one list per argument)
@@ -690,13 +696,15 @@ class GenerationEngine:
                 loop = hf.lookup_slot_loop(pasts, toks0, poss, max_news, drafts, [st.corpus for st in pending], stop_ids=stops,
                                            slots=S, max_keys=cache_engine.max_ctx_length, trunks=trunks, each=True,
                                            slot_index=slots_, params=paramss, seeds=seeds_, histories=hists,
-                                           hist_cap=2 * cache_engine.max_ctx_length)
+                                           hist_cap=2 * cache_engine.max_ctx_length,
+                                           **({"kv": slot_kv} if slot_kv != "fp16" else {}), **({"keep_arenas": False} if drop else {}))
             if loop is None:
                 loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
                                     max_keys=cache_engine.max_ctx_length, trunks=trunks,
                                     **({"kv": slot_kv} if slot_kv != "fp16" else {}), **({"keep_arenas": False} if drop else {}))
             if loop is None:
                 raise RuntimeError("serve: the model refused a batched decode loop over these caches")
+            read_k = _reader(loop)[1]                              # (keep_arenas=False admits the rest of the first fill at once)
             for k, st in enumerate(pending):
                 st.k = k
             pending.clear()

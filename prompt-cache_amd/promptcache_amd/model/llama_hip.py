@@ -659,6 +659,15 @@ class _SlotLoopHost:
     def _ring_row_reused(self, step: int) -> None:
         pass
 
+    def slot_kv_bytes(self) -> int:
+        """Bytes of K/V storage behind the loop's slots: the int8 images and fresh-row buffers of its state (``kv="int8"``) plus
+        every distinct arena a sequence of the loop references."""
+        size = lambda t: t.numel() * t.element_size()
+        total = sum(map(size, self.kvq)) if self.kv == "int8" else 0
+        total += sum(map(size, getattr(self, "fresh", ())))
+        bufs = {a.buf.data_ptr(): a.buf for a in self.arenas if getattr(a, "buf", None) is not None}
+        return total + sum(map(size, bufs.values()))
+
     def kill(self, k: int) -> None:
         """Switch sequence ``k`` off from the next replay on (ordered behind the replays already enqueued)."""
         s = self.idx[k]
@@ -739,15 +748,6 @@ class SlotLoop(_SlotLoopHost):
 
     def _graph(self):
         return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap if self.kv == "int8" else 0)
-
-    def slot_kv_bytes(self) -> int:
-        """Bytes of K/V storage behind the loop's slots: the int8 images and fresh-row buffers of its state (``kv="int8"``) plus
-        every distinct arena a sequence of the loop references."""
-        size = lambda t: t.numel() * t.element_size()
-        total = sum(map(size, self.kvq)) if self.kv == "int8" else 0
-        total += sum(map(size, getattr(self, "fresh", ())))
-        bufs = {a.buf.data_ptr(): a.buf for a in self.arenas if getattr(a, "buf", None) is not None}
-        return total + sum(map(size, bufs.values()))
 
     def _fill_state(self, col, tokens, positions, max_new, params, seeds, histories, stop_ids) -> None:
         """The state words of the loop over ``pc_sample_advance_slots``: one parameter block and one stop list for all slots."""
@@ -860,24 +860,31 @@ class _ImageSeat:
         self.length, self.cap = int(length), int(cap)
 
 
-class SlotLoopQ8Only(SlotLoopQ8):
-    """``SlotLoopQ8`` without the fp16 slot arenas (``LlamaHIP.slot_loop(kv="int8", keep_arenas=False)``, DESIGN 3.28): a slot's
-    only K/V storage is its int8 image and a fresh-row buffer, fp16 ``[L * 2 * Hkv][D]``, holding the row of the current step
-    (``fresh``; ``st["kv_base"]`` holds these addresses).  The step runs ``pc_rope_append_slots_q8`` /
-    ``pc_attn_decode_slots_q8_fresh``.  A sequence enters from whatever arena its prefill ran in: ``materialize()``, the tail
-    ended, ``pc_kv_quant_q8_rows`` into the slot's image on the loop's stream in front of the arm launch -- after that the loop
-    holds no reference to the arena, which may be staged again at once (same stream: the quantise launch is ordered in front).
-    The cap word of a slot is ``qcap``: a sequence whose image is full ends by the device's "buffer full" rule.  ``qcap`` is the
-    larger of ``max_keys`` and the longest ``length + max_new + 2`` known at build; split counts are ``SlotLoopQ8``'s, so on the
-    same ``max_keys`` a sequence's tokens are that loop's, bit for bit."""
+class _ImageRows:
+    """Images sized by the sequences, not by their arenas (in front of a ``_SlotLoopHost`` leaf with ``kv = "int8"``): ``qcap`` is
+    the larger of ``max_keys`` and the longest ``length + max_new + k + 2`` known at build, and a sequence that is longer than the
+    images raises when it enters."""
+
+    def _image_rows(self, arenas, max_news, max_keys) -> int:
+        return max([a.length + mn + self.k + 2 for a, mn in zip(arenas, max_news)] + [int(max_keys or 0)])
+
+    def _quantise_entry(self, s: int, a) -> None:
+        if a.length > self.qcap:
+            raise RuntimeError(f"{type(self).__name__}: the sequence for slot {s} holds {a.length} rows, the loop's int8 images "
+                               f"{self.qcap} (build the loop with max_keys >= the longest sequence)")
+        m = self.m
+        _native.kv_quant_q8_rows(a.buf, a.cap, a.length, m.L * 2 * m.Hkv, m.D, self.kvq[s], self.qcap)
+
+
+class _ImageOnly(_ImageRows):
+    """No fp16 slot arenas (``keep_arenas=False``): a slot's only K/V storage is its image and a fresh-row buffer,
+    fp16 ``[L * 2 * Hkv][k + 1][D]``, holding the rows of the current step (``fresh``; ``st["kv_base"]`` holds these addresses).
+    The cap word of a slot is ``qcap``, and the loop keeps an ``_ImageSeat`` in place of the arena a sequence entered with."""
 
     def _make_state(self, tokens, corpora, hist_cap) -> dict:
         st = super()._make_state(tokens, corpora, hist_cap)
-        self.fresh = self.m._slot_fresh(st, self.S)          # (allocated before any capture, like the images)
+        self.fresh = self.m._slot_fresh(st, self.S, self.k + 1)          # (allocated before any capture, like the images)
         return st
-
-    def _image_rows(self, arenas, max_news, max_keys) -> int:
-        return max([a.length + mn + 2 for a, mn in zip(arenas, max_news)] + [int(max_keys or 0)])
 
     def _prepared(self, a, max_new: int):
         """No arena is decoded in: nothing grows.  A residual tail still ends here, in front of the quantise launch."""
@@ -887,12 +894,17 @@ class SlotLoopQ8Only(SlotLoopQ8):
     def _seat(self, s: int, a):
         return _ImageSeat(a.length, self.qcap), self.fresh[s].data_ptr(), self.qcap
 
-    def _quantise_entry(self, s: int, a) -> None:
-        if a.length > self.qcap:
-            raise RuntimeError(f"{type(self).__name__}: the sequence for slot {s} holds {a.length} rows, the loop's int8 images "
-                               f"{self.qcap} (build the loop with max_keys >= the longest sequence)")
-        m = self.m
-        _native.kv_quant_q8_rows(a.buf, a.cap, a.length, m.L * 2 * m.Hkv, m.D, self.kvq[s], self.qcap)
+
+class SlotLoopQ8Only(_ImageOnly, SlotLoopQ8):
+    """``SlotLoopQ8`` without the fp16 slot arenas (``LlamaHIP.slot_loop(kv="int8", keep_arenas=False)``, DESIGN 3.28): a slot's
+    only K/V storage is its int8 image and a fresh-row buffer, fp16 ``[L * 2 * Hkv][D]``, holding the row of the current step
+    (``fresh``; ``st["kv_base"]`` holds these addresses).  The step runs ``pc_rope_append_slots_q8`` /
+    ``pc_attn_decode_slots_q8_fresh``.  A sequence enters from whatever arena its prefill ran in: ``materialize()``, the tail
+    ended, ``pc_kv_quant_q8_rows`` into the slot's image on the loop's stream in front of the arm launch -- after that the loop
+    holds no reference to the arena, which may be staged again at once (same stream: the quantise launch is ordered in front).
+    The cap word of a slot is ``qcap``: a sequence whose image is full ends by the device's "buffer full" rule.  ``qcap`` is the
+    larger of ``max_keys`` and the longest ``length + max_new + 2`` known at build; split counts are ``SlotLoopQ8``'s, so on the
+    same ``max_keys`` a sequence's tokens are that loop's, bit for bit."""
 
     def _graph(self):
         return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap, fresh=True)
@@ -1037,6 +1049,33 @@ class LookupSlotLoop(_SlotLoopHost):
             super().kill(j)
 
 
+class LookupSlotLoopQ8(_ImageRows, LookupSlotLoop):
+    """``LookupSlotLoop`` whose attention reads int8 images of the slots' K / V rows
+    (``LlamaHIP.lookup_slot_loop(kv="int8")``): ``SlotLoopQ8``'s images, held by the (S, k) state.  Every step writes
+    its ``k + 1`` rows per slot into arena AND image (``pc_rope_append_slots_rows_q8``) and draft row i attends to image keys
+    ``[0, len + i)`` and to its own key exactly (``pc_attn_verify_slots_q8``) -- the function of the token sequence that
+    ``SlotLoopQ8`` computes one token at a time, wherever the step boundaries fall.  The fp16 arenas stay complete.  A sequence
+    that could outgrow the images (``length + max_new + k + 2 > qcap``) raises when it enters."""
+
+    kv = "int8"
+
+    def _prepared(self, a, max_new: int):
+        a = super()._prepared(a, max_new)
+        qcap = getattr(self, "qcap", None)           # (None while the loop is built: the images are sized from these sequences)
+        if qcap is not None and a.length + max_new + self.k + 2 > qcap:
+            raise RuntimeError(f"{type(self).__name__}: a sequence of {a.length} rows with max_new = {max_new} needs "
+                               f"{a.length + max_new + self.k + 2} image rows, the loop's int8 images hold {qcap} (build the loop "
+                               "with a larger max_keys)")
+        return a
+
+
+class LookupSlotLoopQ8Only(_ImageOnly, LookupSlotLoopQ8):
+    """``LookupSlotLoopQ8`` without the fp16 slot arenas (``lookup_slot_loop(kv="int8", keep_arenas=False)``): ``SlotLoopQ8Only``'s
+    residency under the lookup step.  The fresh-row buffers hold the step's ``k + 1`` rows per plane, the cap word of a slot is
+    ``qcap`` and ``kv_base`` holds the fresh addresses, so the draft / arm / verify launches are ``LookupSlotLoop``'s; a sequence
+    whose image is full ends by the device's "no room for a step" rule."""
+
+
 WEIGHT_FORMATS = ("fp16", "mxfp4")
 
 
@@ -1062,11 +1101,12 @@ SLOT_KV = ("fp16", "int8")
 
 
 def check_slot_kv(kv: str, share_trunk: bool = False, lookup: int = 0, head_dim: Optional[int] = None, no_loop: Optional[str] = None,
-                  not_batched: Optional[str] = None) -> None:
+                  not_batched: Optional[str] = None, lookup_q8: bool = False) -> None:
     """``ValueError`` naming the conflict for a ``slot_kv`` / ``kv`` mode the batched decode loop cannot run -- raised before
     anything is allocated.  Pure.  ``no_loop``: why the model has no slot loop (Falcon / MPT, ``load_in_8bit``,
     ``PC_DECODE_TAIL=1``), ``not_batched``: why ``batch_plan`` / ``serve_plan`` would not decode this batch in the device loop
-    (None: they would)."""
+    (None: they would).  ``lookup_q8``: the caller is ``serve`` / ``lookup_slot_loop`` and the model has the lookup step over
+    int8 images (``lookup_slot_q8_available``) -- ``lookup > 0`` is then no conflict."""
     if kv not in SLOT_KV:
         raise ValueError(f"slot_kv must be one of {SLOT_KV}, not {kv!r}")
     if kv != "int8":
@@ -1074,7 +1114,7 @@ def check_slot_kv(kv: str, share_trunk: bool = False, lookup: int = 0, head_dim:
     if share_trunk:
         raise ValueError("slot_kv='int8' and share_trunk exclude each other (the shared-trunk attention reads the leader's fp16 "
                          "arena; int8 images under share_trunk are not implemented)")
-    if int(lookup) > 0:
+    if int(lookup) > 0 and not lookup_q8:
         raise ValueError("slot_kv='int8' and lookup > 0 exclude each other (the k + 1 row verify step reads the fp16 arenas; "
                          "int8 images under lookup are not implemented)")
     if no_loop is not None:
@@ -2701,11 +2741,13 @@ class LlamaHIP:
             st["kvq_base"].copy_(torch.tensor([t.data_ptr() for t in st["kvq"]], dtype=torch.int64))
         return st["kvq_cap"], st["kvq"]
 
-    def _slot_fresh(self, st: dict, S: int):
+    def _slot_fresh(self, st: dict, S: int, rows: int = 1):
         """The fresh-row buffers of the S-slot step without arenas (``keep_arenas=False``): one per slot index, fp16
-        ``[L * 2 * Hkv][D]`` -- the K / V row of the current step.  Kept with the slot state."""
+        ``[L * 2 * Hkv][D]`` -- the K / V row of the current step (the lookup step's (S, k) state: ``[L * 2 * Hkv][rows][D]``,
+        ``rows = k + 1``).  Kept with the slot state."""
         if "fresh" not in st:
-            st["fresh"] = [torch.zeros((self.L * 2 * self.Hkv, self.D), dtype=self.dtype, device=self.device) for _ in range(S)]
+            shape = (self.L * 2 * self.Hkv, self.D) if rows == 1 else (self.L * 2 * self.Hkv, rows, self.D)
+            st["fresh"] = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(S)]
         return st["fresh"]
 
     def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0, fresh: bool = False):
@@ -2822,7 +2864,8 @@ class LlamaHIP:
     def lookup_slot_loop(self, pasts, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
                          slots: Optional[int] = None, max_keys: Optional[int] = None, share_trunk: bool = False,
                          min_trunk: Optional[int] = None, trunks=None, each: bool = False, slot_index=None, params=None, seeds=None,
-                         histories=None, hist_cap: Optional[int] = None) -> Optional["LookupSlotLoop"]:
+                         histories=None, hist_cap: Optional[int] = None, kv: str = "fp16",
+                         keep_arenas: bool = True) -> Optional["LookupSlotLoop"]:
         """``slot_loop`` with prompt-lookup drafts: up to ``k + 1`` greedy tokens per sequence and step (``LookupSlotLoop``).
         ``corpora[j]``: the ids sequence j's drafts may copy from besides its own output (``lookup_loop``'s ``corpus_ids``).  None
         where ``slot_loop`` gives None, where the model has no lookup step (``lookup_available``) and where ``S * (k + 1)``
@@ -2833,7 +2876,15 @@ class LlamaHIP:
         ``each``: the step ends in ``pc_lookup_verify_slots_each`` -- ``params`` (None / plain greedy: argmax),
         ``max_new`` and ``stop_ids`` may then be lists with one entry per sequence, ``seeds`` / ``histories`` are ``slot_loop``'s,
         sequence j sits in slot ``slot_index[j]`` and ``LookupSlotLoop.admit`` puts new sequences into slots whose sequence was
-        retired.  ``hist_cap``: the ids a slot's draft history holds, fixed for the loop (default 8192)."""
+        retired.  ``hist_cap``: the ids a slot's draft history holds, fixed for the loop (default 8192).
+        ``kv="int8"`` / ``keep_arenas=False``: ``slot_loop``'s -- the step reads int8 images of the slots' rows
+        (``LookupSlotLoopQ8``), without fp16 slot arenas where asked (``LookupSlotLoopQ8Only``); ``max_keys`` then also sizes the
+        images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError."""
+        if kv != "fp16" or not keep_arenas:       # (with the mode off nothing is asked of the model here)
+            check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, lookup=k, head_dim=getattr(self, "D", None),
+                          no_loop=None if self.slot_loop_available() else "the model has no batched decode loop",
+                          lookup_q8=kv == "int8" and self.lookup_slot_q8_available())
+            check_slot_keep_arenas(keep_arenas, kv)
         n = len(pasts)
         if not self.lookup_available() or not 1 <= n <= SlotLoop.MAX_SLOTS:
             return None
@@ -2844,10 +2895,16 @@ class LlamaHIP:
         if front is None:
             return None
         arenas, trunks = front
+        cls = (LookupSlotLoopQ8 if keep_arenas else LookupSlotLoopQ8Only) if kv == "int8" else LookupSlotLoop
         if each:
-            return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
-                                  slot_index, params, seeds, histories, hist_cap)
-        return LookupSlotLoop(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks)
+            return cls(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
+                       slot_index, params, seeds, histories, hist_cap)
+        return cls(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks)
+
+    def lookup_slot_q8_available(self) -> bool:
+        """Whether ``lookup_slot_loop(kv="int8")`` can run: the lookup step, the slot step and head_dim 128
+        (``pc_attn_verify_slots_q8``)."""
+        return bool(self.lookup_available() and self.slot_loop_available() and self.D == 128)
 
     def lookup_trunk_available(self) -> bool:
         """Whether ``lookup_slot_loop`` can share trunks: the lookup step and the slot step are both there."""
@@ -2893,6 +2950,13 @@ class LlamaHIP:
         each = bool(getattr(loop, "each", False))
         if each:
             key += ("each",)
+        more = {"each": True} if each else {}
+        if loop.kv == "int8":             # the step over int8 images: their rows per plane are an argument of the launches
+            key += ("q8", loop.qcap)
+            more["qcap"] = loop.qcap
+            if getattr(loop, "fresh", None) is not None:
+                key += ("fresh",)
+                more["fresh"] = True
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2903,24 +2967,27 @@ class LlamaHIP:
         # nothing but the record counters, which are put back behind it with the live words
         live, ctr = st["live"].clone(), st["ctr"].clone()
         st["live"].zero_()
-        self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk, **({"each": True} if each else {}))
+        self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk, **more)
         torch.cuda.synchronize()
         prime_graph_capture(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk, **({"each": True} if each else {}))
+            self._forward_lookup_slots(st, S, k, loop.nsplit, loop.nmax, loop.nsplit_trunk, **more)
         st["live"].copy_(live)
         st["ctr"].copy_(ctr)
         self._graphs[key] = (g, st["hist"])
         return g
 
     def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3, nsplit_trunk: int = 0,
-                              each: bool = False) -> None:
+                              each: bool = False, qcap: int = 0, fresh: bool = False) -> None:
         """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
         k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
         projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop (on the 4-bit
         images up to ``w4_max_rows`` rows).
-        ``nsplit_trunk`` > 0: the attention with shared trunks (leader / trunk words of the state)."""
+        ``nsplit_trunk`` > 0: the attention with shared trunks (leader / trunk words of the state).
+        ``qcap`` > 0: the step over the slots' int8 images -- ``pc_rope_append_slots_rows_q8`` writes every row into
+        image and arena, ``pc_attn_verify_slots_q8`` reads the image and the row's own key; ``fresh``: no arenas, ``st["kv_base"]``
+        holds the fresh-row buffers."""
         n = _native
         dev, c = self.device, self.config
         H, Hkv, D, hid, inter = self.H, self.Hkv, self.D, c.hidden_size, c.intermediate_size
@@ -2937,7 +3004,8 @@ class LlamaHIP:
         qkv = torch.empty((R, W), dtype=torch.float32, device=dev)
         q16 = torch.zeros((R, H * D), dtype=self.dtype, device=dev)
         q16l = torch.zeros((R, H * D), dtype=self.dtype, device=dev)
-        ws_bytes = (n.attn_verify_slots_trunk_workspace_bytes(S, k, H, D, nsplit, nsplit_trunk) if nsplit_trunk
+        ws_bytes = (n.attn_verify_slots_q8_workspace_bytes(S, k, H, D, nsplit) if qcap
+                    else n.attn_verify_slots_trunk_workspace_bytes(S, k, H, D, nsplit, nsplit_trunk) if nsplit_trunk
                     else n.attn_verify_slots_workspace_bytes(S, k, H, D, nsplit))
         ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev)
 
@@ -2951,6 +3019,12 @@ class LlamaHIP:
         w4 = self.w4_stream and R <= self.w4_max_rows
 
         def attend(li):
+            if qcap:
+                n.rope_append_slots_rows_q8(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, *slot, S, k, li, H, Hkv, D, st["kvq_base"], qcap,
+                                            self.L, fresh)
+                n.attn_verify_slots_q8(q16, q16l, H * D, *slot, S, k, li, H, Hkv, D, self.softmax_scale, nsplit, ws, (ah, al),
+                                       st["kvq_base"], qcap, self.L, fresh)
+                return
             n.rope_append_slots_rows(qkv, W, 0 if w4 else 1, q16, q16l, H * D, cs, *slot, S, k, li, H, Hkv, D)
             if nsplit_trunk:
                 n.attn_verify_slots_trunk(q16, q16l, H * D, *slot, st["leader"], st["trunk"], S, k, li, H, Hkv, D, self.softmax_scale,

@@ -12,7 +12,8 @@ counts the host simulation gives for the same lengths (slot_scheduler.replay_cou
 --lookup K [K ...]: prompt-lookup drafts in the serving loop (serve(lookup=K)) against plain serve, legs interleaved in
 one process: per K a leg whose corpus is the plain leg's own output of the request behind what serve gives it (every draft right)
 and a leg with an empty corpus (nothing to copy but the sequence's own output).  Medians of --repeats; tokens per second over the
-whole run, prefills included, plus replays and tokens per replay.
+whole run, prefills included, plus replays and tokens per replay.  With ``--slot-kv int8 [--slot-drop-fp16]`` every right-corpus leg
+runs once more over int8 K/V images (serve(lookup=K, slot_kv="int8"[, keep_arenas=False])).
 """
 import argparse
 import dataclasses
@@ -62,31 +63,34 @@ def served(ge, eng, prompts, lens, lookup=0, **kw):
     return dt, sum(len(t) for t in ge.last_serve_tokens.values()), st["replays"], 1.0 - st["live_rows"] / max(1, st["replays"] * eng.slots)
 
 
-def lookup_legs(ge, eng, prompts, lens, ks, repeats, slots):
-    """Plain serve and, per k, serve(lookup=k) with a full-acceptance and an empty corpus, interleaved.  -> the result dict."""
+def lookup_legs(ge, eng, prompts, lens, ks, repeats, slots, modes=None):
+    """Plain serve and, per k, serve(lookup=k) with a full-acceptance and an empty corpus, interleaved.  -> the result dict.
+    ``modes`` (``--slot-kv int8 [--slot-drop-fp16]``): name -> further arguments of ``serve``; every lookup leg with
+    the right corpus then runs once more per mode (``lookup3_right_int8``, ...), in the same interleaving."""
     real = type(ge)._lookup_corpus
     served(ge, eng, prompts, lens)                                    # (the plain leg's outputs: what a right draft copies)
     answers = {r: list(t) for r, t in ge.last_serve_tokens.items()}
 
-    def leg(k, corpus):
+    def leg(k, corpus, kw):
         order = iter(range(len(prompts)))                             # (asked once per request, in the order they are pulled)
         if corpus == "right":
             ge._lookup_corpus = lambda cache, ids: real(cache, ids) + answers[next(order)]
         elif corpus == "none":
             ge._lookup_corpus = lambda cache, ids: []
         try:
-            dt, n, replays, idle = served(ge, eng, prompts, lens, k)
+            dt, n, replays, idle = served(ge, eng, prompts, lens, k, **kw)
         finally:
             ge.__dict__.pop("_lookup_corpus", None)
         same = sum(answers[r] == list(t) for r, t in ge.last_serve_tokens.items())
         return dict(tok_s=n / dt, replays=replays, tokens=n, seconds=dt, same_as_plain=same)
-    legs = [("plain", 0, None)] + [(f"lookup{k}_{c}", k, c) for k in ks for c in ("right", "none")]
-    for name, k, c in legs[1:]:
-        leg(k, c)                                                     # warm: the (S, k) step is captured
-    runs = {name: [] for name, _, _ in legs}
+    legs = [("plain", 0, None, {})] + [(f"lookup{k}_{c}", k, c, {}) for k in ks for c in ("right", "none")]
+    legs += [(f"lookup{k}_right_{m}", k, "right", kw) for k in ks for m, kw in (modes or {}).items()]
+    for name, k, c, kw in legs[1:]:
+        leg(k, c, kw)                                                 # warm: the (S, k) step is captured
+    runs = {name: [] for name, _, _, _ in legs}
     for _ in range(repeats):
-        for name, k, c in legs:
-            runs[name].append(leg(k, c))
+        for name, k, c, kw in legs:
+            runs[name].append(leg(k, c, kw))
             print(f"{name}: {runs[name][-1]['tok_s']:.1f} tok/s, {runs[name][-1]['replays']} replays", file=sys.stderr, flush=True)
     out = {}
     for name, rs in runs.items():
@@ -133,6 +137,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--slot-drop-fp16", action="store_true",
                     help="serve(slot_kv='int8') against serve(slot_kv='int8', keep_arenas=False); --out merges under the weight format")
+    ap.add_argument("--slot-kv", default="fp16", help="int8 with --lookup: add serve(lookup=k, slot_kv='int8') legs (and, with "
+                                                      "--slot-drop-fp16, keep_arenas=False legs) to the lookup legs")
     ap.add_argument("--weight-format", default="fp16", help="fp16 or mxfp4 (with PC_W4_STREAM / PC_W4_MAX_ROWS from the environment)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "serve_bench measures on the GPU"
@@ -148,6 +154,17 @@ def main():
     ge = GenerationEngine(lm)
     assert ge.serve_plan()[0], ge.serve_plan()[1]
     served(ge, eng, prompts, lens)                                    # warm: graphs captured, code objects loaded
+    if args.lookup and args.slot_kv == "int8":                         # serve(lookup=k) over fp16 arenas against the int8 modes
+        modes = {"int8": dict(slot_kv="int8")}
+        if args.slot_drop_fp16:
+            modes["int8_only"] = dict(slot_kv="int8", keep_arenas=False)
+        res = lookup_legs(ge, eng, prompts, lens, args.lookup, args.repeats, args.slots, modes)
+        res["weight_format"] = args.weight_format
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res) + "\n")
+        print(json.dumps(res))
+        return
     if args.slot_drop_fp16:
         res = slot_drop_legs(ge, eng, prompts, lens, args.repeats, args.slots, args.weight_format)
         if args.out:
