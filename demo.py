@@ -57,6 +57,9 @@ def main():
                          "try 7) from the context per step and verify them in one K+1-row forward (default: PC_LOOKUP, else off); "
                          "with --batch also for the batched loop (generate_batch(lookup=K): N * (K + 1) <= 64 rows per step) and "
                          "with --serve for the serving loop (serve(lookup=K): sampled requests draft and verify too)")
+    ap.add_argument("--loop-prefill", action="store_true", default=None,
+                    help="with --serve and --lookup K: a request admitted into the running loop is prefilled inside its step -- K + 1 "
+                         "of its new tokens per replay, nobody else waits (serve(loop_prefill=True)); not with --slot-kv int8")
     ap.add_argument("--lookup-sampled", action="store_true", default=None,
                     help="with --lookup K: sampled generations (and greedy ones with a repetition penalty) draft and verify too, "
                          "the sampler drawing every row (SampleLookupLoop; default: PC_LOOKUP_SAMPLE=1, else off)")
@@ -138,13 +141,14 @@ def main():
             for r in range(a.serve):
                 pr = Prompt(prompt_text[:cut] + f"<user>{synth.words(4 + r % 5, 5000 + r)}</user>" + prompt_text[cut:], preproc)
                 yield pr, dataclasses.replace(params, max_new_tokens=budgets[r % len(budgets)])
-        batched, why = gen_engine.serve_plan(a.lookup or 0, cache_engine.slots, slot_kv=a.slot_kv, **skw)
+        pkw = dict(loop_prefill=True) if a.loop_prefill else {}
+        batched, why = gen_engine.serve_plan(a.lookup or 0, cache_engine.slots, slot_kv=a.slot_kv, **skw, **pkw)
         for _pass in ("warm", "timed"):
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk, lookup=a.lookup,
-                                              slot_kv=a.slot_kv, **skw):
+                                              slot_kv=a.slot_kv, **skw, **pkw):
                 lasts[r] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

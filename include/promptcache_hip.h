@@ -1036,6 +1036,41 @@ typedef struct pc_lookup_slot_state {   /* the S-slot device arrays of the captu
 int pc_lookup_slot_arm(const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state, int32_t S, int32_t k,
                        int32_t hist_cap, void* stream);
 
+/* ---- forced rows: a request's question fed through the draft rows of the running step (csrc/pc_lookup_common.h) --------------------
+ * One more word per slot, forced int32[S]: the prompt tokens still to be fed behind ids[b][0]; 0 for a slot armed by
+ * pc_lookup_slot_arm.  Such a slot is armed with hist[L - 1] = ids[b][0] = t_0 (L = hist_len[b]) and hist[L .. L + forced[b]) =
+ * t_1 .. -- the device reads those ids before it writes there.  A RUNNING slot with R = forced[b] > 0 takes, per step:
+ *   draft   m = min(k, R); ids[b][1 + j] = hist[b][L + j] for j < m, pad rows and pos as pc_lookup_draft_slots, ndraft[b] = m; no
+ *           n-gram search.
+ *   rows    R > k: nothing is drawn.  R <= k: row R alone is drawn, as a sequence's first token is: pc_sample_advance's draw on
+ *           logits row b * (k + 1) + R with (seeds[b], step draws[b]) under history_bits[b] as it stands (the rows in front are
+ *           prompt tokens: no bits are added); a greedy block takes the argmax.
+ *   accept  R > k: the record is EMPTY; hist_len[b] += k + 1, ids[b][0] = hist[b][L + k], pos[b][0] += k + 1, len[b] += k + 1,
+ *           forced[b] = R - k - 1; budget, draws and bitmap stay.
+ *           R <= k, g the token of row R: the record is {1, g}; hist[b][L + R] = g, hist_len[b] += R + 1, ids[b][0] = g,
+ *           pos[b][0] += R + 1, len[b] += R + 1, forced[b] = 0, budget[b] -= 1, draws[b] = 1, the bit of g is set; live[b] = 0
+ *           when g is one of stop_ids[b], the budget reached 0 or the new len[b] + k + 1 > cap[b].
+ *   ctr[b] += 1 either way.  After the step that emits g every word of the slot but ctr[b] is what pc_lookup_slot_arm writes
+ *   behind a prefill that drew g.  A slot that does not run takes the EMPTY record and live[b] = 0 of pc_lookup_verify_slots.
+ * The host keeps L + R + budget <= hist_cap (indices are clamped into the buffer otherwise).  With forced all zero the draft and
+ * verify entries write exactly the words of pc_lookup_draft_slots / pc_lookup_verify_slots_each; other arguments as there.
+ *
+ * pc_lookup_slot_arm_prompt: pc_lookup_slot_arm on the same block, whose hist_len ids run through the LAST question token, `id` /
+ * `pos` are t_0 and its position, `len` the staged rows and `budget` the tokens the sequence may emit.  All hist_len ids are copied;
+ * then hist_len[slot] = hist_len - n_forced, forced[slot] = n_forced and draws[slot] = 0 (the first token is still to be drawn).
+ * 0 <= n_forced < hist_len.  Ordinary vector stores only. */
+int pc_lookup_slot_arm_prompt(const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state,
+                              int32_t* forced, int32_t n_forced, int32_t S, int32_t k, int32_t hist_cap, void* stream);
+int pc_lookup_draft_slots_prompt(const int32_t* hist, const int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos,
+                                 int32_t* ndraft, const int32_t* cap, const int32_t* len, const int32_t* live, const int32_t* forced,
+                                 int32_t S, int32_t k, int32_t nmax, void* stream);
+int pc_lookup_verify_slots_prompt(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k,
+                                  const pc_sample_params* params_dev, const uint64_t* seeds, uint32_t* history_bits, uint32_t* row_bits,
+                                  int32_t* draws, int32_t* row_token, int32_t* hist, int32_t* hist_len, int32_t hist_cap, int64_t* ids,
+                                  int32_t* pos, int32_t* len, const int32_t* cap, int32_t* live, const int32_t* ndraft, int32_t* budget,
+                                  const int32_t* stop_ids, int32_t* ring, int32_t* counters, int32_t* forced, int32_t ring_cap,
+                                  void* stream);
+
 /* Diagnostics used by the GPU test-suite: dumps the MFMA C/D lane map and the LDS transpose-read
  * map the attention kernel relies on (probe_kernel in csrc/pc_misc.hip). */
 /* dev hook (tools/gemm_trace.py): weight-streaming launches issued by this thread stamp per-wave wall-clock times

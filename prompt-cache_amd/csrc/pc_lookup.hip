@@ -72,16 +72,23 @@ __global__ __launch_bounds__(kDraftThreads) void lookup_draft_kernel(const int32
     lookup_draft_rule(hist, hist_len, hist_cap, ids, pos, ndraft, k, nmax, s_best, s_key);
 }
 
-// One workgroup per slot: the rule above on the slot's own history and words.
+// One workgroup per slot: the rule above on the slot's own history and words.  `forced` (null: pc_lookup_draft_slots): a slot
+// with forced rows feeds its question instead (lookup_draft_forced_rule; uniform over the workgroup).
 __global__ __launch_bounds__(kDraftThreads) void lookup_draft_slots_kernel(const int32_t* __restrict__ hist,
                                                                             const int32_t* __restrict__ hist_len, int hist_cap,
                                                                             int64_t* ids, int32_t* pos, int32_t* ndraft,
                                                                             const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
-                                                                            const int32_t* __restrict__ live, int k, int nmax) {
+                                                                            const int32_t* __restrict__ live, int k, int nmax,
+                                                                            const int32_t* __restrict__ forced) {
     __shared__ int s_best[kDraftThreads / 64];
     __shared__ int s_key;
     const int b = blockIdx.x;
     if (!lookup_slot_runs(cap, len, live, b, k)) return;
+    if (const int R = lookup_forced_rows(forced, b)) {
+        lookup_draft_forced_rule(hist + (int64_t)b * hist_cap, hist_len[b], hist_cap, ids + (int64_t)b * (k + 1), pos + (int64_t)b * (k + 1),
+                                 ndraft + b, k, R);
+        return;
+    }
     lookup_draft_rule(hist + (int64_t)b * hist_cap, hist_len + b, hist_cap, ids + (int64_t)b * (k + 1), pos + (int64_t)b * (k + 1),
                       ndraft + b, k, nmax, s_best, s_key);
 }
@@ -154,10 +161,13 @@ __global__ __launch_bounds__(64) void lookup_accept_slots_kernel(const int32_t* 
 // pc_slot_arm (pc_slots.hip) for the words of pc_lookup_verify_slots_each's step: the launch sits on the stream between two
 // replays, the block is host memory read with system-scope loads, live[slot] = 1 is the last store.  One workgroup: the header
 // goes through LDS, the bitmap row and the history ids are copied by all threads, two 32-bit words per load.
+// `forced` (null: pc_lookup_slot_arm): pc_lookup_slot_arm_prompt -- the last n_forced ids of the block are a question still to be
+// fed: they are copied behind hist_len like the rest, and the slot starts with hist_len - n_forced, forced = n_forced, draws = 0.
 constexpr int kLookupArmWords = (int)(sizeof(pc_lookup_slot_arm_block) / 8);
 
 __global__ __launch_bounds__(kDraftThreads) void lookup_slot_arm_kernel(const unsigned long long* __restrict__ src, pc_lookup_slot_state st,
-                                                                        int S, int k, int hw, int hist_cap) {
+                                                                        int S, int k, int hw, int hist_cap, int32_t* forced,
+                                                                        int n_forced) {
     typedef __attribute__((address_space(1))) unsigned long long g64;
     __shared__ __attribute__((aligned(8))) unsigned long long h[kLookupArmWords];
     const int tid = threadIdx.x;
@@ -165,7 +175,7 @@ __global__ __launch_bounds__(kDraftThreads) void lookup_slot_arm_kernel(const un
     __syncthreads();
     const pc_lookup_slot_arm_block& b = *(const pc_lookup_slot_arm_block*)h;
     const int s = b.slot, hl = b.hist_len;
-    if (s < 0 || s >= S || b.hist_words != hw || hl < 1 || hl > hist_cap) return;      // (the block changed under the launch: touch nothing)
+    if (s < 0 || s >= S || b.hist_words != hw || hl < 1 || hl > hist_cap || n_forced >= hl) return;      // (the block changed under the launch: touch nothing)
     const unsigned long long* bits = src + kLookupArmWords;
     const unsigned long long* hids = bits + (hw + 1) / 2;
     uint32_t* row = st.history_bits + (int64_t)s * hw;
@@ -188,13 +198,14 @@ __global__ __launch_bounds__(kDraftThreads) void lookup_slot_arm_kernel(const un
         st.trunk[s] = b.trunk;
         st.budget[s] = b.budget;
         st.counters[s] = b.counter;
-        st.draws[s] = 1;
+        st.draws[s] = forced ? 0 : 1;
         st.seeds[s] = b.seed;
         st.params[s] = b.params;
         st.ids[(int64_t)s * (k + 1)] = b.id;
         st.pos[(int64_t)s * (k + 1)] = b.pos;
         st.ndraft[s] = 0;
-        st.hist_len[s] = hl;
+        st.hist_len[s] = hl - n_forced;
+        if (forced) forced[s] = n_forced;
     } else if (tid >= 64 && tid < 72) {
         st.stop_ids[s * 8 + tid - 64] = b.stop_ids[tid - 64];
     }
@@ -232,17 +243,36 @@ PC_EXPORT int pc_lookup_verify(const float* logits, int64_t ldl, int32_t vocab, 
     return pc_check_launch("lookup_accept_kernel");
 }
 
+namespace {
+
+// pc_lookup_draft_slots (forced null) and pc_lookup_draft_slots_prompt
+int draft_slots(const char* name, const int32_t* hist, const int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos,
+                int32_t* ndraft, const int32_t* cap, const int32_t* len, const int32_t* live, const int32_t* forced, int32_t S, int32_t k,
+                int32_t nmax, void* stream) {
+    PC_REQUIRE(hist && hist_len && ids && pos && ndraft && cap && len && live, PC_ERR_ARG, "%s: null pointer", name);
+    PC_REQUIRE(S >= 1 && S <= 16 && k >= 1 && k < kMaxRows && S * (k + 1) <= kMaxSlotRows && nmax >= 1 && nmax <= kMaxNgram &&
+                   hist_cap >= 1 && hist_cap < (1 << 24), PC_ERR_ARG,
+               "%s: need 1 <= S <= 16, 1 <= k <= %d, S * (k + 1) <= %d, 1 <= nmax <= %d, 1 <= hist_cap < 2^24", name,
+               kMaxRows - 1, kMaxSlotRows, kMaxNgram);
+    hipLaunchKernelGGL(lookup_draft_slots_kernel, dim3(S), dim3(kDraftThreads), 0, (hipStream_t)stream, hist, hist_len, hist_cap, ids, pos,
+                       ndraft, cap, len, live, k, nmax, forced);
+    return pc_check_launch("lookup_draft_slots_kernel");
+}
+
+}  // namespace
+
 PC_EXPORT int pc_lookup_draft_slots(const int32_t* hist, const int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos,
                                     int32_t* ndraft, const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t k,
                                     int32_t nmax, void* stream) {
-    PC_REQUIRE(hist && hist_len && ids && pos && ndraft && cap && len && live, PC_ERR_ARG, "pc_lookup_draft_slots: null pointer");
-    PC_REQUIRE(S >= 1 && S <= 16 && k >= 1 && k < kMaxRows && S * (k + 1) <= kMaxSlotRows && nmax >= 1 && nmax <= kMaxNgram &&
-                   hist_cap >= 1 && hist_cap < (1 << 24), PC_ERR_ARG,
-               "pc_lookup_draft_slots: need 1 <= S <= 16, 1 <= k <= %d, S * (k + 1) <= %d, 1 <= nmax <= %d, 1 <= hist_cap < 2^24",
-               kMaxRows - 1, kMaxSlotRows, kMaxNgram);
-    hipLaunchKernelGGL(lookup_draft_slots_kernel, dim3(S), dim3(kDraftThreads), 0, (hipStream_t)stream, hist, hist_len, hist_cap, ids, pos,
-                       ndraft, cap, len, live, k, nmax);
-    return pc_check_launch("lookup_draft_slots_kernel");
+    return draft_slots("pc_lookup_draft_slots", hist, hist_len, hist_cap, ids, pos, ndraft, cap, len, live, nullptr, S, k, nmax, stream);
+}
+
+PC_EXPORT int pc_lookup_draft_slots_prompt(const int32_t* hist, const int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos,
+                                           int32_t* ndraft, const int32_t* cap, const int32_t* len, const int32_t* live,
+                                           const int32_t* forced, int32_t S, int32_t k, int32_t nmax, void* stream) {
+    PC_REQUIRE(forced, PC_ERR_ARG, "pc_lookup_draft_slots_prompt: null pointer");
+    return draft_slots("pc_lookup_draft_slots_prompt", hist, hist_len, hist_cap, ids, pos, ndraft, cap, len, live, forced, S, k, nmax,
+                       stream);
 }
 
 PC_EXPORT int pc_lookup_verify_slots(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k, int32_t* row_argmax,
@@ -264,25 +294,42 @@ PC_EXPORT int pc_lookup_verify_slots(const float* logits, int64_t ldl, int32_t v
     return pc_check_launch("lookup_accept_slots_kernel");
 }
 
-PC_EXPORT int pc_lookup_slot_arm(const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state, int32_t S,
-                                 int32_t k, int32_t hist_cap, void* stream) {
-    PC_REQUIRE(host_block && state, PC_ERR_ARG, "pc_lookup_slot_arm: null pointer");
+namespace {
+
+// pc_lookup_slot_arm (forced null, n_forced 0) and pc_lookup_slot_arm_prompt
+int slot_arm(const char* name, const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state,
+             int32_t* forced, int32_t n_forced, int32_t S, int32_t k, int32_t hist_cap, void* stream) {
+    PC_REQUIRE(host_block && state, PC_ERR_ARG, "%s: null pointer", name);
     PC_REQUIRE(state->kv_base && state->cap && state->len && state->live && state->leader && state->trunk && state->ids && state->pos &&
                    state->ndraft && state->budget && state->hist_len && state->counters && state->draws && state->seeds && state->params &&
-                   state->stop_ids && state->history_bits && state->hist, PC_ERR_ARG, "pc_lookup_slot_arm: null pointer in the slot state");
+                   state->stop_ids && state->history_bits && state->hist, PC_ERR_ARG, "%s: null pointer in the slot state", name);
     PC_REQUIRE(S >= 1 && S <= 16 && k >= 1 && k < kMaxRows && S * (k + 1) <= kMaxSlotRows && hist_cap >= 1 && hist_cap < (1 << 24), PC_ERR_ARG,
-               "pc_lookup_slot_arm: need 1 <= S <= 16, 1 <= k <= %d, S * (k + 1) <= %d, 1 <= hist_cap < 2^24", kMaxRows - 1, kMaxSlotRows);
+               "%s: need 1 <= S <= 16, 1 <= k <= %d, S * (k + 1) <= %d, 1 <= hist_cap < 2^24", name, kMaxRows - 1, kMaxSlotRows);
     PC_REQUIRE(((uintptr_t)host_block & 7) == 0 && ((uintptr_t)state->params & 7) == 0 && ((uintptr_t)state->seeds & 7) == 0 &&
                    ((uintptr_t)state->kv_base & 7) == 0 && ((uintptr_t)state->ids & 7) == 0, PC_ERR_ARG,
-               "pc_lookup_slot_arm: the block and the 64-bit state arrays must be 8-byte aligned");
+               "%s: the block and the 64-bit state arrays must be 8-byte aligned", name);
     const int32_t slot = host_block->slot, hw = host_block->hist_words, hl = host_block->hist_len;   // (pinned HOST memory: readable here)
-    PC_REQUIRE(slot >= 0 && slot < S, PC_ERR_ARG, "pc_lookup_slot_arm: slot outside [0, S)");
+    PC_REQUIRE(slot >= 0 && slot < S, PC_ERR_ARG, "%s: slot outside [0, S)", name);
     PC_REQUIRE(hw >= 1 && hw <= (1 << 19) && hl >= 1 && hl <= hist_cap, PC_ERR_ARG,
-               "pc_lookup_slot_arm: need 1 <= hist_words <= 2^19 and 1 <= hist_len <= hist_cap");
+               "%s: need 1 <= hist_words <= 2^19 and 1 <= hist_len <= hist_cap", name);
+    PC_REQUIRE(n_forced >= 0 && n_forced < hl, PC_ERR_ARG, "%s: n_forced must be in [0, hist_len)", name);
     PC_REQUIRE((int64_t)nbytes == (int64_t)sizeof(pc_lookup_slot_arm_block) + (((int64_t)hw * 4 + 7) & ~(int64_t)7) +
                                       (((int64_t)hl * 4 + 7) & ~(int64_t)7), PC_ERR_ARG,
-               "pc_lookup_slot_arm: nbytes must be sizeof(pc_lookup_slot_arm_block) + 4 * hist_words + 4 * hist_len, each rounded up to 8");
+               "%s: nbytes must be sizeof(pc_lookup_slot_arm_block) + 4 * hist_words + 4 * hist_len, each rounded up to 8", name);
     hipLaunchKernelGGL(lookup_slot_arm_kernel, dim3(1), dim3(kDraftThreads), 0, (hipStream_t)stream, (const unsigned long long*)host_block,
-                       *state, S, k, hw, hist_cap);
+                       *state, S, k, hw, hist_cap, forced, n_forced);
     return pc_check_launch("lookup_slot_arm_kernel");
+}
+
+}  // namespace
+
+PC_EXPORT int pc_lookup_slot_arm(const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state, int32_t S,
+                                 int32_t k, int32_t hist_cap, void* stream) {
+    return slot_arm("pc_lookup_slot_arm", host_block, nbytes, state, nullptr, 0, S, k, hist_cap, stream);
+}
+
+PC_EXPORT int pc_lookup_slot_arm_prompt(const pc_lookup_slot_arm_block* host_block, int32_t nbytes, const pc_lookup_slot_state* state,
+                                        int32_t* forced, int32_t n_forced, int32_t S, int32_t k, int32_t hist_cap, void* stream) {
+    PC_REQUIRE(forced, PC_ERR_ARG, "pc_lookup_slot_arm_prompt: null pointer");
+    return slot_arm("pc_lookup_slot_arm_prompt", host_block, nbytes, state, forced, n_forced, S, k, hist_cap, stream);
 }

@@ -135,3 +135,75 @@ __device__ __forceinline__ int lookup_accept_slots_rule(const int32_t* __restric
     }
     return emit;
 }
+
+// ---- forced rows: a question fed through the draft rows of the step over slots (pc_lookup_*_slots_prompt) ----------------------
+// forced[b] = R > 0: R prompt tokens are still to be fed behind ids[b][0].  They stand in hist[L .. L + R) (L = hist_len[b],
+// hist[L - 1] = ids[b][0]); the host armed the slot so (pc_lookup_slot_arm_prompt) and L + R + budget <= hist_cap.  A null
+// `forced` and forced[b] <= 0 are today's slot.
+__device__ __forceinline__ int lookup_forced_rows(const int32_t* __restrict__ forced, int b) {
+    const int R = forced ? forced[b] : 0;
+    return R > 0 ? R : 0;
+}
+
+// (an index into the slot's history, kept inside the buffer whatever the words hold)
+__device__ __forceinline__ int lookup_hist_at(int i, int hist_cap) { return i < 0 ? 0 : (i >= hist_cap ? hist_cap - 1 : i); }
+
+// The draft of a RUNNING slot with R forced rows, by one workgroup: rows 1..m feed the next m = min(k, R) prompt tokens, pad rows
+// and positions are lookup_draft_rule's, no n-gram search runs.
+__device__ __forceinline__ void lookup_draft_forced_rule(const int32_t* __restrict__ hist, int L, int hist_cap, int64_t* ids, int32_t* pos,
+                                                         int32_t* ndraft, int k, int R) {
+    const int tid = threadIdx.x;
+    const int m = R < k ? R : k;
+    const int64_t id0 = ids[0];
+    const int p0 = pos[0];
+    if (tid < k) ids[1 + tid] = tid < m ? (int64_t)hist[lookup_hist_at(L + tid, hist_cap)] : id0;
+    if (tid >= 1 && tid <= k) pos[tid] = p0 + tid;
+    if (tid == 0) ndraft[0] = m;
+}
+
+// The accept rule of a RUNNING slot b with R forced rows, by one wave (pc_lookup_verify_slots_prompt).  R > k: the question goes
+// on -- an EMPTY record, the k + 1 rows are kept, row 0 of the next step is the prompt token behind them.  R <= k: the question
+// ends in row m = R, whose draw g (tok[m], the only row drawn) is the sequence's first token: from here on the words are what
+// pc_lookup_slot_arm writes behind a prefill that drew g, the counter apart.  The stop-id, spent-budget and no-room rules apply
+// to g as to any emitted token.
+__device__ __forceinline__ void lookup_accept_forced_rule(const int32_t* __restrict__ tok, int rows, int V, int b, int R, int32_t* forced,
+                                                          uint32_t* hist_bits, int32_t* draws, int32_t* hist, int32_t* hist_len,
+                                                          int hist_cap, int64_t* ids, int32_t* pos, int32_t* len,
+                                                          const int32_t* __restrict__ cap, int32_t* live, int32_t* budget,
+                                                          const int32_t* __restrict__ stop_ids, int32_t* ring, int32_t* ctr,
+                                                          int ring_cap) {
+    if (threadIdx.x != 0) return;
+    const int k = rows - 1;
+    const int c = ctr[b];
+    int32_t* rec = ring + ((int64_t)b * ring_cap + (int64_t)(((unsigned)c) % (unsigned)ring_cap)) * (rows + 1);
+    hist += (int64_t)b * hist_cap;
+    ids += (int64_t)b * rows;
+    pos += (int64_t)b * rows;
+    const int L = hist_len[b], p0 = pos[0], pl = len[b];
+    ctr[b] = c + 1;
+    if (R > k) {
+        rec[0] = 0;
+        hist_len[b] = L + k + 1;
+        ids[0] = hist[lookup_hist_at(L + k, hist_cap)];
+        pos[0] = p0 + k + 1;
+        len[b] = pl + k + 1;
+        forced[b] = R - k - 1;
+        return;
+    }
+    const int m = R, g = tok[m], bud = budget[b];
+    rec[0] = 1;
+    rec[1] = g;
+    if (L >= 0 && L + m < hist_cap) hist[L + m] = g;
+    hist_len[b] = L + m + 1;
+    ids[0] = g;
+    pos[0] = p0 + m + 1;
+    len[b] = pl + m + 1;
+    forced[b] = 0;
+    budget[b] = bud - 1;
+    draws[b] = 1;
+    if (g >= 0 && g < V) hist_bits[(int64_t)b * ((V + 31) >> 5) + (g >> 5)] |= 1u << (g & 31);
+    bool stop = false;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) stop = stop || g == stop_ids[b * 8 + j];
+    if (stop || bud - 1 <= 0 || pl + m + 1 + k + 1 > cap[b]) live[b] = 0;
+}

@@ -535,44 +535,55 @@ __global__ __launch_bounds__(64) void lookup_sample_accept_kernel(const int32_t*
 // pc_lookup_verify_slots_each, first launch: lookup_sample_rows_kernel per slot -- one workgroup per row r = b * (k + 1) + i of
 // the S * (k + 1)-row verify forward, with parameter block b, seed b, draws[b] and bitmap row b.  A greedy block takes the argmax
 // of its processed row, so greedy and sampled requests share the step.  Rows of a slot that does not run and pad rows
-// (i > ndraft[b]) leave at once (uniform over the workgroup).
+// (i > ndraft[b]) leave at once (uniform over the workgroup).  `forced` (null: pc_lookup_verify_slots_each): of a slot with
+// R = forced[b] > 0 rows only the row that ends its question is drawn -- row R where R <= k, none otherwise -- as the first token
+// of a sequence is: under the bitmap as armed (the rows in front of it are prompt tokens) at step draws[b].
 __global__ __launch_bounds__(kThreads) void lookup_sample_rows_slots_kernel(
     const float* __restrict__ logits, int64_t ldl, int V, int k, const pc_sample_params* __restrict__ prm,
     const uint64_t* __restrict__ seeds, const uint32_t* __restrict__ hist, uint32_t* row_bits, const int32_t* __restrict__ draws,
     const int64_t* __restrict__ ids, const int32_t* __restrict__ ndraft, const int32_t* __restrict__ cap,
-    const int32_t* __restrict__ len, const int32_t* __restrict__ live, int32_t* row_token) {
+    const int32_t* __restrict__ len, const int32_t* __restrict__ live, int32_t* row_token, const int32_t* __restrict__ forced) {
     const int r = blockIdx.x, b = r / (k + 1), i = r - b * (k + 1);
     if (!lookup_slot_runs(cap, len, live, b, k)) return;
+    const int R = lookup_forced_rows(forced, b);
     int nd = ndraft[b];
     nd = nd < 0 ? 0 : (nd > k ? k : nd);
-    if (i > nd) return;
+    if (R ? i != R : i > nd) return;                   // (R > k: no row has index R)
     const int hw = (V + 31) >> 5;
     const uint32_t* hb = hist + (int64_t)b * hw;
     uint32_t* rb = row_bits + (int64_t)r * hw;
     for (int w = threadIdx.x; w < hw; w += kThreads) rb[w] = hb[w];
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && !R) {
         for (int j = 1; j <= i; ++j) {
             const int64_t t = ids[(int64_t)b * (k + 1) + j];
             if (t >= 0 && t < V) rb[t >> 5] |= 1u << (t & 31);
         }
     }
     __syncthreads();
-    const uint32_t step = (uint32_t)draws[b] + (uint32_t)i;
+    const uint32_t step = (uint32_t)draws[b] + (R ? 0u : (uint32_t)i);
     const int bi = sample_row(logits + (int64_t)r * ldl, V, prm + b, rb, seeds[b], step, nullptr);
     if (threadIdx.x == 0) row_token[r] = bi;
 }
 
 // ... second launch, one wave per slot: lookup_accept_slots_rule on the rows' draws, then the sampled loop's own words of the
 // slot -- the emitted tokens' bits into bitmap row b and the slot's random stream advanced by what was emitted, counted behind
-// the stop cut (the draws of rejected rows are not consumed).
+// the stop cut (the draws of rejected rows are not consumed).  `forced` (null: pc_lookup_verify_slots_each): a running slot with
+// forced rows takes lookup_accept_forced_rule instead (uniform over the wave).
 __global__ __launch_bounds__(64) void lookup_accept_slots_each_kernel(const int32_t* __restrict__ row_token, int rows, int V,
                                                                       uint32_t* hist_bits, int32_t* draws, int32_t* hist, int32_t* hist_len,
                                                                       int hist_cap, int64_t* ids, int32_t* pos, int32_t* len,
                                                                       const int32_t* __restrict__ cap, int32_t* live, const int32_t* ndraft,
                                                                       int32_t* budget, const int32_t* __restrict__ stop_ids, int32_t* ring,
-                                                                      int32_t* ctr, int ring_cap) {
+                                                                      int32_t* ctr, int ring_cap, int32_t* forced) {
     const int lane = threadIdx.x, b = blockIdx.x;
+    if (const int R = lookup_forced_rows(forced, b)) {
+        if (lookup_slot_runs(cap, len, live, b, rows - 1)) {
+            lookup_accept_forced_rule(row_token + b * rows, rows, V, b, R, forced, hist_bits, draws, hist, hist_len, hist_cap, ids, pos, len,
+                                      cap, live, budget, stop_ids, ring, ctr, ring_cap);
+            return;
+        }
+    }
     const int d = draws[b];
     int a;
     const int emit = lookup_accept_slots_rule(row_token + b * rows, rows, b, hist, hist_len, hist_cap, ids, pos, len, cap, live, ndraft,
@@ -657,24 +668,51 @@ PC_EXPORT int pc_lookup_verify_sample(const float* logits, int64_t ldl, int32_t 
     return pc_check_launch("lookup_sample_accept_kernel");
 }
 
+namespace {
+
+// pc_lookup_verify_slots_each (forced null) and pc_lookup_verify_slots_prompt
+int verify_slots_each(const char* name, const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k,
+                      const pc_sample_params* params_dev, const uint64_t* seeds, uint32_t* history_bits, uint32_t* row_bits,
+                      int32_t* draws, int32_t* row_token, int32_t* hist, int32_t* hist_len, int32_t hist_cap, int64_t* ids, int32_t* pos,
+                      int32_t* len, const int32_t* cap, int32_t* live, const int32_t* ndraft, int32_t* budget, const int32_t* stop_ids,
+                      int32_t* ring, int32_t* counters, int32_t* forced, int32_t ring_cap, void* stream) {
+    PC_REQUIRE(logits && params_dev && seeds && history_bits && row_bits && draws && row_token && hist && hist_len && ids && pos && len &&
+                   cap && live && ndraft && budget && stop_ids && ring && counters, PC_ERR_ARG, "%s: null pointer", name);
+    PC_REQUIRE(S >= 1 && S <= 16 && k >= 1 && k <= 15 && S * (k + 1) <= 64 && ldl >= vocab && ring_cap > 0 && hist_cap >= 1, PC_ERR_ARG,
+               "%s: need 1 <= S <= 16, 1 <= k <= 15, S * (k + 1) <= 64, ldl >= vocab, ring_cap > 0, hist_cap >= 1", name);
+    PC_REQUIRE(vocab > 0 && vocab < (1 << 24), PC_ERR_ARG, "%s: vocab must be in [1, 2^24)", name);
+    PC_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)params_dev & 7) == 0 && ((uintptr_t)seeds & 7) == 0, PC_ERR_ARG,
+               "%s: logits must be 4-byte, params and seeds 8-byte aligned", name);
+    hipLaunchKernelGGL(lookup_sample_rows_slots_kernel, dim3(S * (k + 1)), dim3(kThreads), 0, (hipStream_t)stream, logits, ldl, vocab, k,
+                       params_dev, seeds, history_bits, row_bits, draws, ids, ndraft, cap, len, live, row_token, forced);
+    int rc = pc_check_launch("lookup_sample_rows_slots_kernel");
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(lookup_accept_slots_each_kernel, dim3(S), dim3(64), 0, (hipStream_t)stream, row_token, k + 1, vocab, history_bits,
+                       draws, hist, hist_len, hist_cap, ids, pos, len, cap, live, ndraft, budget, stop_ids, ring, counters, ring_cap, forced);
+    return pc_check_launch("lookup_accept_slots_each_kernel");
+}
+
+}  // namespace
+
 PC_EXPORT int pc_lookup_verify_slots_each(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k,
                                           const pc_sample_params* params_dev, const uint64_t* seeds, uint32_t* history_bits,
                                           uint32_t* row_bits, int32_t* draws, int32_t* row_token, int32_t* hist, int32_t* hist_len,
                                           int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* len, const int32_t* cap, int32_t* live,
                                           const int32_t* ndraft, int32_t* budget, const int32_t* stop_ids, int32_t* ring,
                                           int32_t* counters, int32_t ring_cap, void* stream) {
-    PC_REQUIRE(logits && params_dev && seeds && history_bits && row_bits && draws && row_token && hist && hist_len && ids && pos && len &&
-                   cap && live && ndraft && budget && stop_ids && ring && counters, PC_ERR_ARG, "pc_lookup_verify_slots_each: null pointer");
-    PC_REQUIRE(S >= 1 && S <= 16 && k >= 1 && k <= 15 && S * (k + 1) <= 64 && ldl >= vocab && ring_cap > 0 && hist_cap >= 1, PC_ERR_ARG,
-               "pc_lookup_verify_slots_each: need 1 <= S <= 16, 1 <= k <= 15, S * (k + 1) <= 64, ldl >= vocab, ring_cap > 0, hist_cap >= 1");
-    PC_REQUIRE(vocab > 0 && vocab < (1 << 24), PC_ERR_ARG, "pc_lookup_verify_slots_each: vocab must be in [1, 2^24)");
-    PC_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)params_dev & 7) == 0 && ((uintptr_t)seeds & 7) == 0, PC_ERR_ARG,
-               "pc_lookup_verify_slots_each: logits must be 4-byte, params and seeds 8-byte aligned");
-    hipLaunchKernelGGL(lookup_sample_rows_slots_kernel, dim3(S * (k + 1)), dim3(kThreads), 0, (hipStream_t)stream, logits, ldl, vocab, k,
-                       params_dev, seeds, history_bits, row_bits, draws, ids, ndraft, cap, len, live, row_token);
-    int rc = pc_check_launch("lookup_sample_rows_slots_kernel");
-    if (rc != PC_OK) return rc;
-    hipLaunchKernelGGL(lookup_accept_slots_each_kernel, dim3(S), dim3(64), 0, (hipStream_t)stream, row_token, k + 1, vocab, history_bits,
-                       draws, hist, hist_len, hist_cap, ids, pos, len, cap, live, ndraft, budget, stop_ids, ring, counters, ring_cap);
-    return pc_check_launch("lookup_accept_slots_each_kernel");
+    return verify_slots_each("pc_lookup_verify_slots_each", logits, ldl, vocab, S, k, params_dev, seeds, history_bits, row_bits, draws,
+                             row_token, hist, hist_len, hist_cap, ids, pos, len, cap, live, ndraft, budget, stop_ids, ring, counters,
+                             nullptr, ring_cap, stream);
+}
+
+PC_EXPORT int pc_lookup_verify_slots_prompt(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t k,
+                                            const pc_sample_params* params_dev, const uint64_t* seeds, uint32_t* history_bits,
+                                            uint32_t* row_bits, int32_t* draws, int32_t* row_token, int32_t* hist, int32_t* hist_len,
+                                            int32_t hist_cap, int64_t* ids, int32_t* pos, int32_t* len, const int32_t* cap,
+                                            int32_t* live, const int32_t* ndraft, int32_t* budget, const int32_t* stop_ids,
+                                            int32_t* ring, int32_t* counters, int32_t* forced, int32_t ring_cap, void* stream) {
+    PC_REQUIRE(forced, PC_ERR_ARG, "pc_lookup_verify_slots_prompt: null pointer");
+    return verify_slots_each("pc_lookup_verify_slots_prompt", logits, ldl, vocab, S, k, params_dev, seeds, history_bits, row_bits, draws,
+                             row_token, hist, hist_len, hist_cap, ids, pos, len, cap, live, ndraft, budget, stop_ids, ring, counters,
+                             forced, ring_cap, stream);
 }

@@ -249,6 +249,10 @@ SIGNATURES = {
     "pc_lookup_verify_slots_each": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pc_lookup_slot_arm": (C.c_int, [_vp, _i32, C.POINTER(LookupSlotState), _i32, _i32, _i32, _vp]),
+    "pc_lookup_slot_arm_prompt": (C.c_int, [_vp, _i32, C.POINTER(LookupSlotState), _vp, _i32, _i32, _i32, _i32, _vp]),
+    "pc_lookup_draft_slots_prompt": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "pc_lookup_verify_slots_prompt": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pc_quant_act_i8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_rmsnorm_quant_i8": (C.c_int, [_vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp]),
     "pc_outlier_corr": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -1239,6 +1243,46 @@ def lookup_slot_arm(host_pinned, nbytes: int, state: LookupSlotState, S: int, k:
     rc = load().pc_lookup_slot_arm(host_pinned.data_ptr(), nbytes, C.byref(state), S, k, hist_cap,
                                    current_stream() if stream is None else stream)
     check(rc, "pc_lookup_slot_arm")
+
+
+def lookup_slot_arm_prompt(host_pinned, nbytes: int, state: LookupSlotState, forced, n_forced: int, S: int, k: int, hist_cap: int,
+                           stream: Optional[int] = None) -> None:
+    """``lookup_slot_arm`` for a sequence whose question is fed through the running step (pc_lookup_slot_arm_prompt): the last
+    ``n_forced`` history ids of the block are still to be fed -- ``hist_len[slot]`` stops in front of them, ``forced[slot] =
+    n_forced`` (``forced`` int32 [S]) and ``draws[slot] = 0``."""
+    rc = load().pc_lookup_slot_arm_prompt(host_pinned.data_ptr(), nbytes, C.byref(state), _ptr(forced), n_forced, S, k, hist_cap,
+                                          current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_slot_arm_prompt")
+
+
+def lookup_draft_slots_prompt(hist, hist_len, ids, pos, ndraft, cap, length, live, forced, S: int, k: int, nmax: int = 3,
+                              stream: Optional[int] = None) -> None:
+    """``lookup_draft_slots`` with forced rows (pc_lookup_draft_slots_prompt): a running slot with ``forced[b]`` > 0 feeds the next
+    prompt tokens of its history instead of drafts."""
+    assert hist.dim() == 2 and hist.shape[0] == S and hist.is_contiguous() and ids.numel() >= S * (k + 1) and pos.numel() >= S * (k + 1)
+    assert forced is None or forced.numel() >= S
+    rc = load().pc_lookup_draft_slots_prompt(hist.data_ptr(), hist_len.data_ptr(), hist.shape[1], ids.data_ptr(), pos.data_ptr(),
+                                             ndraft.data_ptr(), cap.data_ptr(), length.data_ptr(), live.data_ptr(), _ptr(forced), S, k,
+                                             nmax, current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_draft_slots_prompt")
+
+
+def lookup_verify_slots_prompt(logits, ldl: int, vocab: int, S: int, k: int, params, seeds, history_bits, row_bits, draws, row_token,
+                               hist, hist_len, ids, pos, length, cap, live, ndraft, budget, stop_ids, ring, counters, forced,
+                               ring_cap: int, stream: Optional[int] = None) -> None:
+    """``lookup_verify_slots_each`` with forced rows (pc_lookup_verify_slots_prompt): a running slot with ``forced[b]`` > 0 keeps its
+    rows as prompt rows and draws its first token from the row that ends the question."""
+    R, hw = S * (k + 1), (vocab + 31) // 32
+    assert ring.numel() >= S * ring_cap * (k + 2) and row_token.numel() >= R and ids.numel() >= R and stop_ids.numel() >= 8 * S
+    assert row_bits.numel() >= R * hw and history_bits.numel() >= S * hw and params.numel() >= S * C.sizeof(SampleParams)
+    assert hist.dim() == 2 and hist.shape[0] == S and hist.is_contiguous() and (forced is None or forced.numel() >= S)
+    rc = load().pc_lookup_verify_slots_prompt(logits.data_ptr(), ldl, vocab, S, k, params.data_ptr(), seeds.data_ptr(),
+                                              history_bits.data_ptr(), row_bits.data_ptr(), draws.data_ptr(), row_token.data_ptr(),
+                                              hist.data_ptr(), hist_len.data_ptr(), hist.shape[1], ids.data_ptr(), pos.data_ptr(),
+                                              length.data_ptr(), cap.data_ptr(), live.data_ptr(), ndraft.data_ptr(), budget.data_ptr(),
+                                              stop_ids.data_ptr(), ring.data_ptr(), counters.data_ptr(), _ptr(forced), ring_cap,
+                                              current_stream() if stream is None else stream)
+    check(rc, "pc_lookup_verify_slots_prompt")
 
 
 def sample_params_bytes(temperature: float, repetition_penalty: float, top_p: float, top_k: int, seed: int) -> bytes:

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import gc
 import os
+import time
 from dataclasses import dataclass, field
 from typing import Generator, List, Optional, Tuple
 
@@ -530,10 +531,15 @@ class GenerationEngine:
 
     # -- a stream of requests: continuous batching ------------------------------------------------
     def serve_plan(self, lookup: int = 0, slots: Optional[int] = None, slot_kv: Optional[str] = None,
-                   keep_arenas: Optional[bool] = None) -> Tuple[bool, str]:
+                   keep_arenas: Optional[bool] = None, loop_prefill: bool = False) -> Tuple[bool, str]:
         """``_serve_plan``; ``slot_kv`` (None: ``PC_SLOT_KV``): with "int8" the reason of a batched plan says that the loop reads
-        int8 K/V images, and with ``keep_arenas=False`` (None: not named) that no slot keeps an fp16 arena."""
+        int8 K/V images, and with ``keep_arenas=False`` (None: not named) that no slot keeps an fp16 arena.  ``loop_prefill=True``
+        (``serve``'s): the reason of a plan in the lookup form says that admitted requests are prefilled inside the step; where
+        ``serve`` would refuse the mode (``check_loop_prefill``) this raises the same ValueError."""
         batched, why = self._serve_plan(lookup, slots)
+        if loop_prefill:
+            self._loop_prefill(True, lookup, slots, os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv)
+            why += ", requests admitted into the running loop are prefilled inside its step (loop_prefill=True)"
         if batched and (os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv) == "int8":
             why += ", K/V read from int8 images (slot_kv='int8')"
             if keep_arenas is not None and not keep_arenas:
@@ -557,6 +563,19 @@ class GenerationEngine:
             return True, "one device loop, one token per replay: " + why
         return True, "one device loop, new prompts admitted as slots free up"
 
+    def _loop_prefill(self, loop_prefill: Optional[bool], lookup: int, slots: Optional[int], slot_kv: str) -> bool:
+        """Whether ``serve`` prefills admitted requests inside the lookup step: the argument, else ``PC_SERVE_LOOP_PREFILL``
+        (default 0).  True where it cannot run -- ``check_loop_prefill`` (model/llama_hip.py) -- raises ValueError, before
+        anything is allocated."""
+        if loop_prefill is None:
+            loop_prefill = os.environ.get("PC_SERVE_LOOP_PREFILL", "0") == "1"
+        if loop_prefill:
+            from .model.llama_hip import check_loop_prefill
+            batched, why = self._serve_plan()
+            k, no_drafts = self._serve_drafts(lookup, slots) if batched else (0, why)
+            check_loop_prefill(True, k, slot_kv, no_drafts)
+        return bool(loop_prefill)
+
     def _serve_drafts(self, lookup: int, slots: Optional[int]) -> Tuple[int, Optional[str]]:
         """``(k, None)``: ``serve(lookup=...)`` over ``slots`` slots runs the lookup form with k drafts per sequence and replay (k
         above 15 is taken as 15); ``(0, why)``: it runs the one-token loop (``why`` None: ``lookup`` is off)."""
@@ -574,7 +593,8 @@ class GenerationEngine:
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
               share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None,
-              keep_arenas: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
+              keep_arenas: Optional[bool] = None, loop_prefill: Optional[bool] = None
+              ) -> Generator[Tuple[int, Output], None, None]:
         """Continuous batching over ``cache_engine.slots`` slots.  ``requests``: any iterable -- it may be lazy -- of ``Prompt`` or
         ``(Prompt, GenerationParameters)``; ``params`` is the default for bare prompts.  Requests are numbered in the order they
         are pulled; yields ``(index, Output)``.  A request is pulled when a slot is free: ``cache_engine.process(prompt, slot=k)``,
@@ -605,12 +625,24 @@ class GenerationEngine:
         fp16 arena.  Every request is staged and prefilled in slot 0's buffer, whatever slot the scheduler gives it, its rows are
         quantised into the slot's image as it enters the loop (``SlotLoopQ8Only``) and the buffer is free for the next request;
         the buffers of slots 1.. are never allocated.  The loop is built with the first sequence that has more to decode and the
-        rest of the first fill is admitted in front of replay 0.  Tokens are ``slot_kv="int8"``'s."""
+        rest of the first fill is admitted in front of replay 0.  Tokens are ``slot_kv="int8"``'s.
+        ``loop_prefill`` (None: ``PC_SERVE_LOOP_PREFILL``, default 0; with ``lookup`` > 0 in the lookup form only): a
+        request admitted into the RUNNING loop is not prefilled on its own -- its new tokens are fed through the k + 1 rows of its
+        slot, ``ceil(q / (k + 1))`` replays in which nobody else waits (``LookupSlotLoop.admit_prompt``), and its first token is
+        drawn on the device and comes back in the ring; ``ttft_ms`` is then the wall time from admission to that read.  The
+        first fill, a request whose position ids are not ``p, p + 1, ...``, one whose question and budget do not fit the draft
+        history and one with ``q = 1 mod (k + 1)`` new tokens (its last token would be fed by an ordinary, drafting step, in front of
+        the position gap ``generate`` leaves behind a prompt) are prefilled serially, as without the mode.  Question rows are
+        appended without the serial prefill's residual tail, so logits differ from the serial flow at the level decoded rows
+        already do.  ``last_serve_stats`` gains
+        ``loop_prefills`` (requests prefilled inside the loop) and ``step_prefills`` (requests prefilled by a step of their
+        own).  ValueError without the lookup form and with ``slot_kv="int8"``."""
         if share_trunk is None:
             share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
         lookup = min(int(os.environ.get("PC_SERVE_LOOKUP", "0")) if lookup is None else int(lookup), 15)
         slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, *self._serve_plan(), serve=True)
         drop = not self._keep_arenas(keep_arenas, slot_kv)
+        in_loop = self._loop_prefill(loop_prefill, lookup, getattr(cache_engine, "slots", None), slot_kv)
 
         def unpack(req):
             if isinstance(req, (tuple, list)):
@@ -634,6 +666,8 @@ class GenerationEngine:
         stats = self.last_serve_stats = dict(replays=0, rows=0, live_rows=0, requests=0)
         if drafts:
             stats.update(tokens=0, steps=0)
+        if in_loop:
+            stats.update(loop_prefills=0, step_prefills=0)
         self.last_serve_trace = sched.trace
         tokens = self.last_serve_tokens = {}          # request index -> the tokens it decoded
         seq = {}            # slot -> stream of the running sequence
@@ -664,6 +698,10 @@ class GenerationEngine:
                 st = _Stream(self._render, p, stream_interval, ids, max(pos) + 1, index=index, slot=slot,
                              seed=0 if p.plain_greedy else seed + index, device_stops=split_stop_ids(p.stop_token_ids)[0])
                 tokens[index] = st.new_ids
+                if in_loop and loop is not None and admit_prompt(st, list(ids), list(pos), cache):
+                    continue
+                if in_loop:
+                    stats["step_prefills"] += 1
                 out = self._first_token(st, list(ids), list(pos), cache)
                 if drafts:
                     st.corpus = self._lookup_corpus(cache, ids)        # (behind the prefill: the staged layout is carried out)
@@ -685,6 +723,28 @@ class GenerationEngine:
                     st.past = cache = None                         # (the loop holds the rows; the buffer is the next request's)
                 seq[slot] = st
 
+        def admit_prompt(st, ids, pos, cache) -> bool:
+            """``loop_prefill``: the request goes into the running loop unprefilled (``LookupSlotLoop.admit_prompt``) -- where its
+            positions are contiguous, question and budget fit the draft history and q is not 1 mod (k + 1): such a question's
+            last token is fed by an ordinary step, whose drafts would sit at positions without the gap ``generate`` leaves in
+            front of the first decoded token.  False: it takes the serial path."""
+            q, p = len(ids), st.params
+            if not (getattr(loop, "prompt_rows", False) and q % (loop.k + 1) != 1 and p.max_new_tokens >= 1
+                    and pos == list(range(pos[0], pos[0] + q))
+                    and q + p.max_new_tokens <= loop.hist_cap and getattr(cache, "arena", None) is not None):
+                return False
+            st.t_admit = time.perf_counter()
+            cache.arena.materialize()                              # (the staged layout is carried out: the trunk rows are there)
+            trunk = sched.join(st.slot, cache.arena.layout) if share_trunk and loop.nsplit_trunk else None
+            # the first decoded token sits at position first_free + 1, as behind a serial prefill: one behind the question's end
+            st.k = loop.admit_prompt(st.slot, cache, ids, pos[0], p.max_new_tokens, None if p.plain_greedy else p, st.seed,
+                                     st.output_ids, st.device_stops, self._lookup_corpus(cache, []), trunk=trunk, decode_gap=1)
+            st.past = cache
+            stats["loop_prefills"] += 1
+            sched.started(st.slot, st.index, loop.n)
+            seq[st.slot] = st
+            return True
+
         def build_loop():
             """The ``each=True`` loop over the sequences waiting in ``pending``."""
             nonlocal loop, read_k
@@ -696,7 +756,7 @@ class GenerationEngine:
                 loop = hf.lookup_slot_loop(pasts, toks0, poss, max_news, drafts, [st.corpus for st in pending], stop_ids=stops,
                                            slots=S, max_keys=cache_engine.max_ctx_length, trunks=trunks, each=True,
                                            slot_index=slots_, params=paramss, seeds=seeds_, histories=hists,
-                                           hist_cap=2 * cache_engine.max_ctx_length,
+                                           hist_cap=2 * cache_engine.max_ctx_length, **({"prompt_rows": True} if in_loop else {}),
                                            **({"kv": slot_kv} if slot_kv != "fp16" else {}), **({"keep_arenas": False} if drop else {}))
             if loop is None:
                 loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
@@ -721,14 +781,16 @@ class GenerationEngine:
                 # the step in flight cannot exhaust a budget -- a sequence has room for more than its k + 1 tokens
                 while loop.n <= i:
                     loop.enqueue()
+                # (loop_prefill: a sequence "starts" at the replay that draws its first token; the replays in front feed its question)
+                first = loop.first_step if in_loop and hasattr(loop, "first_step") else loop._start.__getitem__
                 if loop.n == i + 1 and wants_look_ahead(
-                        [(loop._start[st.k], st.last_step - (len(st.new_ids) - 1)) for st in seq.values()], i, read_k):
+                        [(first(st.k), st.last_step - (len(st.new_ids) - 1)) for st in seq.values()], i, read_k):
                     loop.enqueue()                                 # the replay AFTER the one whose tokens are read below
                 ms = loop.elapsed_ms(i)
                 stats["rows"] += S
                 for slot in sorted(seq):
                     st = seq[slot]
-                    if loop._start[st.k] > i:
+                    if first(st.k) > i:
                         continue
                     toks = read(st.k, i)
                     outs = []
@@ -737,6 +799,8 @@ class GenerationEngine:
                     else:
                         stats["live_rows"] += 1
                         st.total_ms += ms
+                        if not st.new_ids:                         # (loop_prefill: the first token, from the ring)
+                            st.ttft_ms = st.total_ms = (time.perf_counter() - st.t_admit) * 1e3
                         for token in toks:
                             out = st.emit(token)
                             if read_k:

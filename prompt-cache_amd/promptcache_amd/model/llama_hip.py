@@ -413,6 +413,19 @@ def lookup_admit_history(corpus, token: int, max_new: int, hist_cap: int) -> lis
     return ids[max(0, len(ids) - keep):] + [int(token)]
 
 
+def lookup_prompt_history(corpus, ids, max_new: int, hist_cap: int) -> list:
+    """The draft history a sequence enters a ``LookupSlotLoop(prompt_rows=True)`` with through ``admit_prompt``: ``corpus ++ ids``
+    with the whole question ``ids`` kept and the OLDEST corpus ids dropped until the history, the first token and the rest of the
+    budget fit (``len + max_new <= hist_cap``) -- the ids ``lookup_admit_history`` keeps behind a serial prefill of ``ids``.
+    ValueError when ``len(ids) + max_new`` alone does not fit."""
+    q = len(ids)
+    if q + max_new > hist_cap:
+        raise ValueError(f"lookup admission: a question of {q} ids and max_new = {max_new} do not fit a draft history of {hist_cap}")
+    keep = hist_cap - max_new - q
+    c = [int(t) for t in corpus]
+    return c[max(0, len(c) - keep):] + [int(t) for t in ids]
+
+
 def _is_sampled(params) -> bool:
     """Whether ``params`` take the sampled chain (None / greedy without a repetition penalty: the argmax of the raw row)."""
     return params is not None and not (params.greedy and params.repetition_penalty <= 1.0)
@@ -589,17 +602,20 @@ class _SlotLoopHost:
             raise RuntimeError(f"{name}.admit: the cache is not a staged batch-1 arena")
         return a
 
-    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, trunk, corpus=None) -> int:
+    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, trunk, corpus=None, question=None) -> int:
+        """``question`` (``LookupSlotLoop.admit_prompt``): the ids still to be prefilled, ``token`` the first of them -- the arena
+        also gets room for their rows, and the leaf's ``_admit_check`` / ``_arm`` see them."""
         m, name = self.m, type(self).__name__
+        more = () if question is None else (question,)
         if getattr(m, "_live_loop", None) is not self:
             raise RuntimeError(f"{name}: another device loop on this model took over")
         if not 0 <= s < self.S or max_new < 1:
             raise ValueError(f"{name}.admit: slot {s} outside [0, {self.S}) or max_new < 1")
-        running, extra, hist = self._admit_check(s, corpus, token, int(max_new))
+        running, extra, hist = self._admit_check(s, corpus, token, int(max_new), *more)
         if any(a is self.arenas[k] for k in running):
             raise RuntimeError(f"{name}.admit: the arena belongs to a running sequence")
         a.materialize()
-        a = self._prepared(a, max_new)
+        a = self._prepared(a, max_new + len(question or ()))
         leader, T = (-1, 0) if trunk is None else (int(trunk[0]), int(trunk[1]))
         if leader >= 0:
             lead = self._slot_seq[leader] if leader != s else None
@@ -620,7 +636,7 @@ class _SlotLoopHost:
                       trunk=T, budget=int(max_new), counter=self.ctr0 + self.n, **extra)
         off = _fill_arm_block(arr, self._arm_header, fields, seed, params, stop_ids, history, m.config.vocab_size)
         self._quantise_entry(s, a)
-        self._arm(ent[0], arr, off, hist)
+        self._arm(ent[0], arr, off, hist, *more)
         ent[1].record()
         ent[2] = True
         return self._enter(s, held, (None, 0) if leader < 0 else (leader, T), max_new, stop_ids)
@@ -628,10 +644,13 @@ class _SlotLoopHost:
     def _set_length(self, a, length: int) -> None:
         a.length = length
 
+    def _length_after(self, k: int, consumed: int) -> int:
+        return self.len0[k] + consumed
+
     def retire(self, k: int, consumed: int) -> None:
         """Sequence ``k`` is over and its consumer used ``consumed`` of what it produced (``close``'s unit): its arena's ``length``
         goes to exactly that (``close``'s rule, for one sequence) -- before the buffer is staged again for the slot's next sequence."""
-        self._set_length(self.arenas[k], self.len0[k] + int(consumed))
+        self._set_length(self.arenas[k], self._length_after(k, int(consumed)))
         self._retired.add(k)
 
     @torch.inference_mode()
@@ -687,9 +706,9 @@ class _SlotLoopHost:
         that were not retired one by one."""
         if isinstance(consumed, dict):
             consumed = [consumed.get(k) for k in range(len(self.arenas))]
-        for a, l0, c in zip(self.arenas, self.len0, consumed):
+        for k, (a, c) in enumerate(zip(self.arenas, consumed)):
             if c is not None:
-                self._set_length(a, l0 + int(c))
+                self._set_length(a, self._length_after(k, int(c)))
         if getattr(self.m, "_live_loop", None) is self:
             self.m._live_loop = None
 
@@ -924,18 +943,26 @@ class LookupSlotLoop(_SlotLoopHost):
     ``kill(j)``; ``close(consumed)`` with the TOKENS each sequence's consumer used; ``logits`` is the ``[R][V]`` fp32 tensor of
     the last replay.  ``trunks`` (``lookup_slot_loop(share_trunk=True)``): ``SlotLoop``'s grouping -- the step then
     reads a group's shared rows from the leader's arena, once for all draft rows of all members
-    (``pc_attn_verify_slots_trunk``); ``nsplit_trunk`` > 0 says so."""
+    (``pc_attn_verify_slots_trunk``); ``nsplit_trunk`` > 0 says so.
+
+    ``prompt_rows`` (``LookupSlotLoopPrompt``, ``each=True`` only): the step runs the ``_prompt`` entries over one more word per slot,
+    ``forced``, and ``admit_prompt`` feeds a request's question through the slot's ``k + 1`` rows -- ``ceil(q / (k + 1))`` replays
+    with EMPTY records, the last of which draws the first token (``first_step`` says which replay that is)."""
 
     _arm_header = _native.LookupSlotArmBlock
+    prompt_rows = False
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arenas, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
                  slots: Optional[int] = None, max_keys: Optional[int] = None, trunks=None, each: bool = False, slot_index=None,
                  params=None, seeds=None, histories=None, hist_cap: Optional[int] = None):
         assert 1 <= k <= 15, k
+        assert each or not self.prompt_rows, "prompt_rows needs each=True"
         self.k, self.nmax = int(k), int(nmax)
         self._record = (self.k + 2,)      # a step leaves {count, tokens...} per slot: ``host`` is [RING][S][k + 2]
         self._end = []                    # the replay at which the slot's next sequence entered (None: none has)
+        self._prefill = []                # admit_prompt: (question length, replays its prefill takes) of sequence j; (0, 0): none
+        self._gaps = {}                   # replay -> [(slot, position gap)]: added to pos[slot][0] behind that replay
         self._build(model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each,
                     max_keys, corpora, hist_cap)
 
@@ -963,8 +990,10 @@ class LookupSlotLoop(_SlotLoopHost):
         """``each``: ``hist_cap`` ids of draft history per slot (default 8192), fixed here: the captured step holds the buffer."""
         m, S, k = self.m, self.S, self.k
         if self.each:
-            st = m._lookup_slot_state(S, k, 8192 if hist_cap is None else int(hist_cap), each=True)
+            st = m._lookup_slot_state(S, k, 8192 if hist_cap is None else int(hist_cap), each=True, prompt=self.prompt_rows)
             self.hist_cap = st["hist"].shape[1]
+            if self.prompt_rows:
+                st["forced"].zero_()
         else:
             self._hists = [[int(t) for t in c] + [int(tok)] for c, tok in zip(corpora, tokens)]
             st = m._lookup_slot_state(S, k, max(map(len, self._hists)) + self.max_new)
@@ -1012,22 +1041,82 @@ class LookupSlotLoop(_SlotLoopHost):
         return self._admit(int(slot_index), self._admit_arena(past), token, position, max_new, params, seed, history, stop_ids, trunk,
                            corpus)
 
-    def _admit_check(self, s: int, corpus, token, max_new: int):
-        hist = lookup_admit_history(corpus, token, max_new, self.hist_cap)
+    @torch.inference_mode()
+    def admit_prompt(self, slot_index: int, past, ids, position0: int, max_new: int, params, seed: int, history, stop_ids, corpus,
+                     trunk=None, decode_gap: int = 0) -> int:
+        """``admit`` without the serial prefill (``prompt_rows=True`` loops): ``past`` holds the staged rows only, and the question
+        ``ids`` -- at positions ``position0, position0 + 1, ...`` -- is fed through the slot's rows from the next replay on, k + 1
+        tokens per replay; the replay that feeds the last one draws the sequence's first token on the device (step 0 of the
+        stream ``seed``, under the bits of ``history``) and leaves it in the ring.  ``max_new`` counts that token.  The staging is
+        carried out (``materialize()``), the arena gets ``T + q + max_new + k + 2`` rows and the WHOLE question stays in the draft
+        history behind ``corpus``, the ids in front of it (``lookup_prompt_history``; ValueError where question and budget alone do
+        not fit ``hist_cap``).  ``decode_gap``: added to the position of the first token once it is drawn (``GenerationEngine``
+        places it one position behind the question's end + 1).  Question rows are appended as plain fp16 rows, as decoded rows
+        are.  -> the new sequence's index; ``first_step`` gives the replay that carries its first token."""
+        if not self.prompt_rows:
+            raise RuntimeError("LookupSlotLoop.admit_prompt needs a loop built with prompt_rows=True")
+        ids, s = [int(t) for t in ids], int(slot_index)
+        if not ids:
+            raise ValueError("LookupSlotLoop.admit_prompt: an empty question")
+        if decode_gap and len(ids) % (self.k + 1) == 1:
+            # (the forced rows run out at a step's end: an ordinary step feeds the last token and may draft behind it, gap or not)
+            raise ValueError(f"LookupSlotLoop.admit_prompt: decode_gap needs a question that is not 1 mod k + 1 = {self.k + 1} tokens "
+                             f"long, not {len(ids)}")
+        j = self._admit(s, self._admit_arena(past), ids[0], position0, max_new, params, seed, history, stop_ids, trunk, corpus, ids)
+        q, n = len(ids), -(-len(ids) // (self.k + 1))
+        self.len0[j] += q                                # (the rows in front of the first decoded token, as behind a serial prefill)
+        self._prefill[j] = (q, n)
+        if decode_gap:
+            self._gaps.setdefault(self._start[j] + n - 1, []).append((s, int(decode_gap)))
+        return j
+
+    def prefill_replays(self, j: int) -> int:
+        """The replays sequence ``j``'s in-loop prefill takes, ``ceil(q / (k + 1))`` (0: it was prefilled before it entered)."""
+        return self._prefill[j][1]
+
+    def first_step(self, j: int) -> int:
+        """The first replay whose record can carry a token of sequence ``j``: its start, or the last replay of its in-loop prefill.
+        ``tokens(j, i)`` is empty for every earlier i because nothing has been drawn yet -- not because the sequence is over."""
+        return self._start[j] + max(self._prefill[j][1] - 1, 0)
+
+    @torch.inference_mode()
+    def enqueue(self) -> int:
+        i = super().enqueue()
+        for s, gap in self._gaps.pop(i, ()):             # (stream-ordered behind replay i, which drew the slot's first token)
+            self.st["pos"][s, :1] += gap
+        return i
+
+    def _length_after(self, j: int, consumed: int) -> int:
+        """(a sequence that ends inside its in-loop prefill consumed nothing: its arena goes back to the staged rows)"""
+        return self.len0[j] + consumed if consumed >= 0 else self.len0[j] - self._prefill[j][0]
+
+    def _admit_check(self, s: int, corpus, token, max_new: int, question=None):
+        hist = (lookup_admit_history(corpus, token, max_new, self.hist_cap) if question is None else
+                lookup_prompt_history(corpus, question, max_new, self.hist_cap))
         prev = self._slot_seq[s]
         if prev is not None and prev not in self._retired:
             raise RuntimeError(f"LookupSlotLoop.admit: the sequence in slot {s} was not retired")
         return [j for j in self._slot_seq if j is not None and j not in self._retired], {"hist_len": len(hist)}, hist
 
-    def _arm(self, block, arr, off: int, hist) -> None:
+    def _arm(self, block, arr, off: int, hist, question=None) -> None:
         """(the history ids behind the bitmap; the launch reads the bytes of THIS admission only)"""
         arr[off:off + 4 * len(hist)].view(np.int32)[:] = np.asarray(hist, dtype=np.int32)
-        _native.lookup_slot_arm(block, off + ((4 * len(hist) + 7) & ~7), self._arm_state, self.S, self.k, self.hist_cap)
+        nbytes, s = off + ((4 * len(hist) + 7) & ~7), self._arm_header.from_buffer(arr).slot
+        for gaps in self._gaps.values():                 # (a gap owed to the slot's previous sequence, killed inside its prefill)
+            gaps[:] = [g for g in gaps if g[0] != s]
+        if question is not None:
+            _native.lookup_slot_arm_prompt(block, nbytes, self._arm_state, self.st["forced"], len(question) - 1, self.S, self.k,
+                                           self.hist_cap)
+            return
+        if self.prompt_rows:                             # (forced rows a killed prefill left behind: this sequence has none)
+            self.st["forced"][s: s + 1].fill_(0)
+        _native.lookup_slot_arm(block, nbytes, self._arm_state, self.S, self.k, self.hist_cap)
 
     def _entered(self, j: int, prev, max_new: int, stop_ids) -> None:
         if prev is not None:
             self._end[prev] = self.n
         self._end.append(None)
+        self._prefill.append((0, 0))
 
     def _set_length(self, a, length: int) -> None:
         a.length = length
@@ -1035,7 +1124,8 @@ class LookupSlotLoop(_SlotLoopHost):
 
     def tokens(self, j: int, i: int):
         """The tokens sequence ``j`` emitted at step ``i`` (empty: the sequence was over, or had no budget left).  ``i`` is the global
-        replay index -- empty before the sequence's start and from the replay its slot's next sequence entered (``each=True``)."""
+        replay index -- empty before the sequence's start and from the replay its slot's next sequence entered (``each=True``),
+        and before ``first_step(j)``, while an in-loop prefill has not drawn the first token yet."""
         if i < self._start[j] or (self._end[j] is not None and i >= self._end[j]):
             return []
         self.events[i][2].synchronize()
@@ -1047,6 +1137,13 @@ class LookupSlotLoop(_SlotLoopHost):
         """``SlotLoop.kill``; nothing once the slot holds a later sequence."""
         if self._end[j] is None:
             super().kill(j)
+
+
+class LookupSlotLoopPrompt(LookupSlotLoop):
+    """``LookupSlotLoop(each=True)`` whose step takes forced rows (``lookup_slot_loop(prompt_rows=True)``): the state
+    holds ``forced``, the captured step runs the ``_prompt`` entries and ``admit_prompt`` works."""
+
+    prompt_rows = True
 
 
 class LookupSlotLoopQ8(_ImageRows, LookupSlotLoop):
@@ -1123,6 +1220,20 @@ def check_slot_kv(kv: str, share_trunk: bool = False, lookup: int = 0, head_dim:
         raise ValueError(f"slot_kv='int8' is implemented for head_dim 128 only (pc_attn_decode_slots_q8); head_dim = {head_dim}")
     if not_batched is not None:
         raise ValueError(f"slot_kv='int8' needs a batch decoded in the device loop, and this one is not: {not_batched}")
+
+
+def check_loop_prefill(loop_prefill: bool, drafts: int, kv: str = "fp16", why: Optional[str] = None) -> None:
+    """``ValueError`` naming the conflict for ``serve(loop_prefill=True)`` where it cannot run -- raised before anything is
+    allocated.  Pure.  ``drafts``: the k ``serve`` runs the lookup form with (``_serve_drafts``; 0: it does not, ``why`` says
+    why where there is a reason beyond ``lookup`` being off)."""
+    if not loop_prefill:
+        return
+    if int(drafts) <= 0:
+        raise ValueError("loop_prefill=True needs the lookup form of the serving loop (serve(lookup=k), k > 0: a question is fed "
+                         "through the k draft rows of the step), and it does not run: " + (why or "lookup is off"))
+    if kv == "int8":
+        raise ValueError("loop_prefill=True and slot_kv='int8' exclude each other (question rows are appended as fp16 rows; "
+                         "forced rows over int8 images are not implemented)")
 
 
 def check_slot_keep_arenas(keep_arenas: bool, kv: str, generate_batch: bool = False) -> None:
@@ -2865,7 +2976,7 @@ class LlamaHIP:
                          slots: Optional[int] = None, max_keys: Optional[int] = None, share_trunk: bool = False,
                          min_trunk: Optional[int] = None, trunks=None, each: bool = False, slot_index=None, params=None, seeds=None,
                          histories=None, hist_cap: Optional[int] = None, kv: str = "fp16",
-                         keep_arenas: bool = True) -> Optional["LookupSlotLoop"]:
+                         keep_arenas: bool = True, prompt_rows: bool = False) -> Optional["LookupSlotLoop"]:
         """``slot_loop`` with prompt-lookup drafts: up to ``k + 1`` greedy tokens per sequence and step (``LookupSlotLoop``).
         ``corpora[j]``: the ids sequence j's drafts may copy from besides its own output (``lookup_loop``'s ``corpus_ids``).  None
         where ``slot_loop`` gives None, where the model has no lookup step (``lookup_available``) and where ``S * (k + 1)``
@@ -2879,7 +2990,11 @@ class LlamaHIP:
         retired.  ``hist_cap``: the ids a slot's draft history holds, fixed for the loop (default 8192).
         ``kv="int8"`` / ``keep_arenas=False``: ``slot_loop``'s -- the step reads int8 images of the slots' rows
         (``LookupSlotLoopQ8``), without fp16 slot arenas where asked (``LookupSlotLoopQ8Only``); ``max_keys`` then also sizes the
-        images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError."""
+        images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError.
+        ``prompt_rows`` (with ``each``, fp16 arenas): the step takes forced rows and ``LookupSlotLoop.admit_prompt``
+        prefills an admitted request's question inside it.  False: today's loop, graph key and launches."""
+        if prompt_rows and (not each or kv != "fp16"):
+            raise ValueError("lookup_slot_loop: prompt_rows=True needs each=True and kv='fp16'")
         if kv != "fp16" or not keep_arenas:       # (with the mode off nothing is asked of the model here)
             check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, lookup=k, head_dim=getattr(self, "D", None),
                           no_loop=None if self.slot_loop_available() else "the model has no batched decode loop",
@@ -2895,7 +3010,8 @@ class LlamaHIP:
         if front is None:
             return None
         arenas, trunks = front
-        cls = (LookupSlotLoopQ8 if keep_arenas else LookupSlotLoopQ8Only) if kv == "int8" else LookupSlotLoop
+        cls = ((LookupSlotLoopQ8 if keep_arenas else LookupSlotLoopQ8Only) if kv == "int8" else
+               LookupSlotLoopPrompt if prompt_rows else LookupSlotLoop)
         if each:
             return cls(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
                        slot_index, params, seeds, histories, hist_cap)
@@ -2911,7 +3027,7 @@ class LlamaHIP:
         return bool(self.lookup_available() and self.slot_loop_available())
 
     @torch.inference_mode()
-    def _lookup_slot_state(self, S: int, k: int, hist_need: int, each: bool = False) -> dict:
+    def _lookup_slot_state(self, S: int, k: int, hist_need: int, each: bool = False, prompt: bool = False) -> dict:
         """Device words of the (S, k) lookup step (one set per (S, k): the captured steps hold their addresses).  The history
         buffer grows in powers of two; the graph key carries its address."""
         sts = self.__dict__.setdefault("_lookup_slot_sts", {})
@@ -2940,6 +3056,8 @@ class LlamaHIP:
             st.update(params_each=z(S * ctypes.sizeof(_native.SampleParams), torch.uint8), seeds=z(S, torch.int64),
                       bits=z((S, hw), torch.int32), draws=z(S, torch.int32), row_bits=z(R * hw, torch.int32),
                       row_token=z(R, torch.int32))
+        if prompt and "forced" not in st:     # forced rows of the prompt_rows step (pc_lookup_*_slots_prompt)
+            st["forced"] = torch.zeros(S, dtype=torch.int32, device=dev)
         return st
 
     def _lookup_slot_graph(self, loop: "LookupSlotLoop"):
@@ -2951,6 +3069,9 @@ class LlamaHIP:
         if each:
             key += ("each",)
         more = {"each": True} if each else {}
+        if getattr(loop, "prompt_rows", False):
+            key += ("prompt",)
+            more["prompt"] = True
         if loop.kv == "int8":             # the step over int8 images: their rows per plane are an argument of the launches
             key += ("q8", loop.qcap)
             more["qcap"] = loop.qcap
@@ -2979,7 +3100,7 @@ class LlamaHIP:
         return g
 
     def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3, nsplit_trunk: int = 0,
-                              each: bool = False, qcap: int = 0, fresh: bool = False) -> None:
+                              each: bool = False, qcap: int = 0, fresh: bool = False, prompt: bool = False) -> None:
         """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
         k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
         projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop (on the 4-bit
@@ -2987,7 +3108,9 @@ class LlamaHIP:
         ``nsplit_trunk`` > 0: the attention with shared trunks (leader / trunk words of the state).
         ``qcap`` > 0: the step over the slots' int8 images -- ``pc_rope_append_slots_rows_q8`` writes every row into
         image and arena, ``pc_attn_verify_slots_q8`` reads the image and the row's own key; ``fresh``: no arenas, ``st["kv_base"]``
-        holds the fresh-row buffers."""
+        holds the fresh-row buffers.
+        ``prompt``: the two ends are the ``_prompt`` entries over ``st["forced"]`` -- a slot with forced rows feeds
+        its question through the unchanged middle of the step."""
         n = _native
         dev, c = self.device, self.config
         H, Hkv, D, hid, inter = self.H, self.Hkv, self.D, c.hidden_size, c.intermediate_size
@@ -2995,7 +3118,11 @@ class LlamaHIP:
         R = S * (k + 1)
         mt = (R + 15) // 16
         slot = (st["kv_base"], st["cap"], st["len"], st["live"])
-        n.lookup_draft_slots(st["hist"], st["hist_len"], st["ids"], st["pos"], st["ndraft"], st["cap"], st["len"], st["live"], S, k, nmax)
+        if prompt:
+            n.lookup_draft_slots_prompt(st["hist"], st["hist_len"], st["ids"], st["pos"], st["ndraft"], st["cap"], st["len"], st["live"],
+                                        st["forced"], S, k, nmax)
+        else:
+            n.lookup_draft_slots(st["hist"], st["hist_len"], st["ids"], st["pos"], st["ndraft"], st["cap"], st["len"], st["live"], S, k, nmax)
         cs = torch.empty((R, D // 2, 2), dtype=torch.float32, device=dev)
         n.rope_table(st["pos"], self.inv_freq, cs, R, D)
         h16 = torch.empty((R, hid), dtype=self.dtype, device=dev)
@@ -3076,6 +3203,12 @@ class LlamaHIP:
                 n.gemm_skinny(self._w16(lw, "wdown", True), ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
             n.rmsnorm_frag(x, self.norm, xh, xl, R, hid, eps, slabs, pending)
             n.gemm_skinny(self.lm_head_f, xh, xl, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
+        if prompt:                    # ... and the forced rows of a slot that is still fed its question
+            n.lookup_verify_slots_prompt(st["logits"], V, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
+                                         st["row_token"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"], st["cap"],
+                                         st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], st["forced"],
+                                         LookupSlotLoop.RING)
+            return
         if each:                      # the sampler on every row, per slot
             n.lookup_verify_slots_each(st["logits"], V, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
                                        st["row_token"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"], st["cap"],

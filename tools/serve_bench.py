@@ -14,6 +14,11 @@ one process: per K a leg whose corpus is the plain leg's own output of the reque
 and a leg with an empty corpus (nothing to copy but the sequence's own output).  Medians of --repeats; tokens per second over the
 whole run, prefills included, plus replays and tokens per replay.  With ``--slot-kv int8 [--slot-drop-fp16]`` every right-corpus leg
 runs once more over int8 K/V images (serve(lookup=K, slot_kv="int8"[, keep_arenas=False])).
+With ``--loop-prefill`` the legs are, per K and corpus, serve(lookup=K) with serial admission prefills against
+serve(lookup=K, loop_prefill=True), interleaved with the order rotating: tokens per second, replays and the per-request time to the
+first token as median [min .. max].
+
+    python tools/serve_bench.py --lookup 3 7 --loop-prefill --repeats 5 [--out profiles/serve_loop_prefill_bench.json]
 """
 import argparse
 import dataclasses
@@ -106,6 +111,67 @@ def lookup_legs(ge, eng, prompts, lens, ks, repeats, slots, modes=None):
             "legs": out}
 
 
+def loop_prefill_legs(ge, eng, prompts, lens, ks, repeats, slots):
+    """Per k and corpus ('right' / 'none' as in ``lookup_legs``): serve(lookup=k) and serve(lookup=k, loop_prefill=True), interleaved
+    in one process with the order rotating.  -> the result dict: tok/s over the whole run, replays and the time to the first token
+    of the requests admitted into the running loop (those behind the first fill), each as median [min .. max]."""
+    real = type(ge)._lookup_corpus
+    served(ge, eng, prompts, lens)
+    answers = {r: list(t) for r, t in ge.last_serve_tokens.items()}
+    base = GenerationParameters(temperature=0.0, stop_token_ids=[], stop_str=[])
+
+    def leg(k, corpus, in_loop):
+        order = iter(range(len(prompts)))
+        if corpus == "right":
+            ge._lookup_corpus = lambda cache, ids: real(cache, ids) + answers[next(order)]
+        else:
+            ge._lookup_corpus = lambda cache, ids: []
+        ttft = {}
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for r, out in ge.serve(eng, ((p, dataclasses.replace(base, max_new_tokens=n)) for p, n in zip(prompts, lens)),
+                                   stream_interval=10 ** 9, lookup=k, loop_prefill=in_loop):
+                ttft.setdefault(r, out.elapsed_time)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+        finally:
+            ge.__dict__.pop("_lookup_corpus", None)
+        st = ge.last_serve_stats
+        n = sum(len(t) for t in ge.last_serve_tokens.values())
+        same = sum(answers[r] == list(t) for r, t in ge.last_serve_tokens.items())
+        return dict(tok_s=n / dt, replays=st["replays"], tokens=n, ttft=[ttft[r] for r in sorted(ttft) if r >= slots],
+                    loop_prefills=st.get("loop_prefills", 0), same_as_plain=same)
+
+    def mmm(v, nd=1):
+        return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+    legs = [(f"lookup{k}_{c}_{'loop' if il else 'serial'}", k, c, il) for k in ks for c in ("right", "none") for il in (False, True)]
+    for _, k, c, il in legs:
+        leg(k, c, il)                                                 # warm: both (S, k) steps captured
+    runs = {name: [] for name, _, _, _ in legs}
+    for r in range(repeats):
+        for j in range(0, len(legs), 2):                              # (the two legs of a pair side by side, the order rotating)
+            for name, k, c, il in (legs[j:j + 2] if r % 2 == 0 else legs[j:j + 2][::-1]):
+                runs[name].append(leg(k, c, il))
+                print(f"{name}: {runs[name][-1]['tok_s']:.1f} tok/s, {runs[name][-1]['replays']} replays", file=sys.stderr, flush=True)
+    out = {}
+    for name, rs in runs.items():
+        out[name] = {"tok_s": mmm([r["tok_s"] for r in rs]), "replays": mmm([r["replays"] for r in rs], 0), "tokens": rs[-1]["tokens"],
+                     "ttft_ms_admitted": mmm([t for r in rs for t in r["ttft"]], 2), "loop_prefills": rs[-1]["loop_prefills"],
+                     "requests_equal_to_plain": rs[-1]["same_as_plain"]}
+    for name in out:
+        if name.endswith("_loop"):
+            serial = out[name[:-4] + "serial"]
+            out[name]["median_over_serial_median"] = round(out[name]["tok_s"]["median"] / serial["tok_s"]["median"], 3)
+            out[name]["gain_claimed"] = out[name]["tok_s"]["median"] > serial["tok_s"]["max"]
+    return {"shape": "llama2-7b (random init)", "requests": len(prompts), "slots": slots, "max_new_tokens": lens,
+            "how": "greedy; decoded tokens per second over the whole serve run; serve(lookup=k) with serial admission prefills against "
+                   f"serve(lookup=k, loop_prefill=True), one process, pairs interleaved with the order rotating, {repeats} repetitions, "
+                   "median [min .. max]; ttft_ms_admitted: Output.elapsed_time of the first output of every request behind the first "
+                   "fill (serial: the prefill's device time; loop: wall time from admission to the read of the first token); a gain "
+                   "is claimed only where the in-loop median exceeds the serial leg's maximum", "legs": out}
+
+
 def slot_drop_legs(ge, eng, prompts, lens, repeats, slots, fmt_w):
     """serve(slot_kv="int8") and serve(slot_kv="int8", keep_arenas=False), interleaved with the order rotating."""
     legs = {"int8": dict(slot_kv="int8"), "int8_only": dict(slot_kv="int8", keep_arenas=False)}
@@ -139,6 +205,8 @@ def main():
                     help="serve(slot_kv='int8') against serve(slot_kv='int8', keep_arenas=False); --out merges under the weight format")
     ap.add_argument("--slot-kv", default="fp16", help="int8 with --lookup: add serve(lookup=k, slot_kv='int8') legs (and, with "
                                                       "--slot-drop-fp16, keep_arenas=False legs) to the lookup legs")
+    ap.add_argument("--loop-prefill", action="store_true",
+                    help="with --lookup: serve(lookup=k) against serve(lookup=k, loop_prefill=True) (DESIGN 3.30)")
     ap.add_argument("--weight-format", default="fp16", help="fp16 or mxfp4 (with PC_W4_STREAM / PC_W4_MAX_ROWS from the environment)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "serve_bench measures on the GPU"
@@ -154,6 +222,14 @@ def main():
     ge = GenerationEngine(lm)
     assert ge.serve_plan()[0], ge.serve_plan()[1]
     served(ge, eng, prompts, lens)                                    # warm: graphs captured, code objects loaded
+    if args.lookup and args.loop_prefill:
+        res = loop_prefill_legs(ge, eng, prompts, lens, args.lookup, args.repeats, args.slots)
+        res["weight_format"] = args.weight_format
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+        return
     if args.lookup and args.slot_kv == "int8":                         # serve(lookup=k) over fp16 arenas against the int8 modes
         modes = {"int8": dict(slot_kv="int8")}
         if args.slot_drop_fp16:
