@@ -23,6 +23,7 @@ from typing import Generator, List, Optional, Tuple
 
 import torch
 
+from . import modes
 from .model import LanguageModel
 from .model.kv_arena import StagedKV
 from .slot_scheduler import SlotScheduler, split_stop_ids, wants_look_ahead
@@ -368,68 +369,39 @@ class GenerationEngine:
             gc.collect()
 
     # -- several prompts at once ------------------------------------------------------------------
-    MAX_BATCH = 16
+    MAX_BATCH = modes.MAX_BATCH
 
-    def _no_batched_loop(self, greedy: bool, sampled: bool) -> Optional[str]:
-        """Why this model and engine cannot run a batched device loop for greedy and / or sampled sequences, or None."""
+    def _capabilities(self, greedy: bool, sampled: bool) -> modes.Capabilities:
+        """What this model and engine offer a call that decodes greedy and / or sampled sequences (modes.py resolves the call's
+        modes from it): the one place that asks the model.  A model without a method does not have the step."""
         hf = getattr(self.lm, "hf_model", None)
+
+        def says(name: str) -> bool:
+            offered = getattr(hf, name, None)
+            return offered is not None and bool(offered())
+        no_loop = off = None
         if getattr(self.lm, "use_full_position_ids", False):
-            return "the model takes full position ids (per-key positions are re-based on the host every step)"
-        if not hasattr(hf, "slot_loop") or not hf.slot_loop_available():
-            return "the model has no batched decode loop (architecture, int8 weights or PC_DECODE_TAIL=1)"
-        if greedy and not self.device_greedy_loop:
-            return "PC_DEVICE_GREEDY=0"
-        if sampled and not self.device_sample_loop:
-            return "PC_DEVICE_SAMPLE=0"
-        return None
+            no_loop = "the model takes full position ids (per-key positions are re-based on the host every step)"
+        elif not hasattr(hf, "slot_loop") or not hf.slot_loop_available():
+            no_loop = "the model has no batched decode loop (architecture, int8 weights or PC_DECODE_TAIL=1)"
+        elif greedy and not self.device_greedy_loop:
+            off = "PC_DEVICE_GREEDY=0"
+        elif sampled and not self.device_sample_loop:
+            off = "PC_DEVICE_SAMPLE=0"
+        has = hasattr(hf, "lookup_slot_loop")
+        return modes.Capabilities(no_loop, no_loop or off, has, has and says("lookup_available"), says("lookup_slot_q8_available"),
+                                  says("lookup_trunk_available"), getattr(hf, "D", None))
 
-    def _slot_kv(self, slot_kv: Optional[str], share_trunk: bool, lookup: int, batched: bool, why: str, serve: bool = False) -> str:
-        """The K/V mode a batched loop runs with: the argument, else ``PC_SLOT_KV``, else "fp16".  "int8" where the loop cannot
-        run it -- ``check_slot_kv`` (model/llama_hip.py) -- raises ValueError, before anything is asked of the model.  ``serve``:
-        the caller is ``serve``, where "int8" goes with ``lookup`` > 0 on a model that says ``lookup_slot_q8_available()``."""
-        kv = os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv
-        if kv != "fp16":
-            from .model.llama_hip import check_slot_kv
-            hf = getattr(self.lm, "hf_model", None)
-            offered = getattr(hf, "lookup_slot_q8_available", None) if serve else None
-            check_slot_kv(kv, share_trunk=bool(share_trunk), lookup=int(lookup), head_dim=getattr(hf, "D", None),
-                          no_loop=self._no_batched_loop(False, False), not_batched=None if batched else why,
-                          **({"lookup_q8": True} if offered is not None and offered() else {}))
-        return kv
-
-    @staticmethod
-    def _keep_arenas(keep_arenas: Optional[bool], slot_kv: str, generate_batch: bool = False) -> bool:
-        """Whether a batched loop keeps the fp16 slot arenas: the argument, else (``serve``) ``PC_SLOT_KEEP_ARENAS``, else True.
-        False where it cannot run -- ``check_slot_keep_arenas`` (model/llama_hip.py) -- raises ValueError, before anything is
-        allocated."""
-        from .model.llama_hip import check_slot_keep_arenas, parse_keep_arenas
-        if keep_arenas is None:
-            keep_arenas = True if generate_batch else parse_keep_arenas(os.environ.get("PC_SLOT_KEEP_ARENAS"))
-        check_slot_keep_arenas(bool(keep_arenas), slot_kv, generate_batch=generate_batch)
-        return bool(keep_arenas)
+    def _batch_modes(self, n_requests: int, params: GenerationParameters, **kw) -> modes.Modes:
+        return modes.resolve_batch(self._capabilities(params.plain_greedy, not params.plain_greedy), n_requests, params.plain_greedy,
+                                   len(params.stop_token_ids), params.max_new_tokens, **kw)
 
     def batch_plan(self, n_requests: int, params: GenerationParameters, slot_kv: Optional[str] = None) -> Tuple[bool, str]:
         """``(batched, reason)``: whether ``generate_batch`` decodes ``n_requests`` sequences together in one device loop
         (``model/llama_hip.py`` SlotLoop) or runs them one after another through ``generate``, and why.  Host logic only.
         ``slot_kv`` (None: ``PC_SLOT_KV``): with "int8" the reason of a batched plan says that the loop reads int8 K/V images."""
-        batched, why = self._batch_plan(n_requests, params)
-        if batched and (os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv) == "int8":
-            why += ", K/V read from int8 images (slot_kv='int8')"
-        return batched, why
-
-    def _batch_plan(self, n_requests: int, params: GenerationParameters) -> Tuple[bool, str]:
-        if n_requests < 1:
-            return False, "no requests"
-        if n_requests > self.MAX_BATCH:
-            return False, f"more than {self.MAX_BATCH} requests"
-        why = self._no_batched_loop(params.plain_greedy, not params.plain_greedy)
-        if why is not None:
-            return False, why
-        if len(params.stop_token_ids) > 8:
-            return False, "more than 8 stop token ids"
-        if params.max_new_tokens < 2:
-            return False, "nothing to decode after the first token"
-        return True, "one device loop over all sequences"
+        m = self._batch_modes(n_requests, params, share_trunk=False, lookup=0, slot_kv=slot_kv, validate=False)
+        return m.batched, m.reason()
 
     @torch.inference_mode()
     def generate_batch(self, requests, params: GenerationParameters, stream_interval: int = 2,
@@ -462,34 +434,14 @@ class GenerationEngine:
         the slot loop or a batch that is not decoded in the device loop.
         ``keep_arenas=False`` (``serve``'s int8-only residency) raises ValueError here: the callers hand in one live
         arena per sequence, so there is nothing to save."""
-        if share_trunk is None:
-            share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
-        lookup = int(os.environ.get("PC_SLOT_LOOKUP", "0")) if lookup is None else int(lookup)
         requests = [(list(t), list(p), c) for t, p, c in requests]
         hf = getattr(self.lm, "hf_model", None)
-        batched, why = self._batch_plan(len(requests), params)
-        if batched:
-            arenas = [getattr(c, "arena", None) for _, _, c in requests]
-            if not (all(a is not None and a.B == 1 for a in arenas) and len(set(map(id, arenas))) == len(arenas)):
-                kv_batched, kv_why = False, "a cache is not a staged batch-1 arena of its own"
-            else:
-                kv_batched, kv_why = True, why
-        else:
-            kv_batched, kv_why = False, why
-        slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, kv_batched, kv_why)
-        self._keep_arenas(keep_arenas, slot_kv, generate_batch=True)
-        if lookup > 0 and share_trunk:
-            offered = getattr(hf, "lookup_trunk_available", None)
-            if offered is None or not offered():
-                raise ValueError("generate_batch: lookup > 0 and share_trunk=True cannot be combined (no shared-trunk verify step)")
-            if not batched:
-                raise ValueError("generate_batch: lookup > 0 and share_trunk=True cannot be combined (no shared-trunk verify step "
-                                 f"runs for this batch: {why})")
-        if batched:
-            # every cache must be a staged batch-1 arena, no two the same
-            arenas = [getattr(c, "arena", None) for _, _, c in requests]
-            batched = all(a is not None and a.B == 1 for a in arenas) and len(set(map(id, arenas))) == len(arenas)
-        if not batched:
+        # every cache must be a staged batch-1 arena, no two the same
+        arenas = [getattr(c, "arena", None) for _, _, c in requests]
+        own = all(a is not None and a.B == 1 for a in arenas) and len(set(map(id, arenas))) == len(arenas)
+        m = self._batch_modes(len(requests), params, own_arenas=own, share_trunk=share_trunk, lookup=lookup, slot_kv=slot_kv,
+                              keep_arenas=keep_arenas)
+        if not m.batched:
             full = bool(getattr(self.lm, "use_full_position_ids", False))
             for k, (token_ids, position_ids, cache) in enumerate(requests):
                 for out in self.generate(token_ids, position_ids, params, cache, stream_interval, use_full_position_ids=full):
@@ -511,14 +463,14 @@ class GenerationEngine:
                 # the first decoded token sits at position first_free + 1, as in generate
                 first = ([st.past for st in members], [st.new_ids[-1] for st in members], [st.first_free + 1 for st in members],
                          members[0].last_step)
-                if lookup > 0 and plain_greedy and hasattr(hf, "lookup_slot_loop"):
-                    loop = hf.lookup_slot_loop(*first, min(lookup, 15),
+                if m.drafts:
+                    loop = hf.lookup_slot_loop(*first, m.drafts,
                                                [self._lookup_corpus(requests[st.index][2], requests[st.index][0]) for st in members],
-                                               stop_ids=params.stop_token_ids, share_trunk=bool(share_trunk))
+                                               stop_ids=params.stop_token_ids, share_trunk=m.share_trunk)
                 if loop is None:
                     loop = hf.slot_loop(*first, None if plain_greedy else params, [st.seed for st in members],
-                                        [st.output_ids for st in members], params.stop_token_ids, share_trunk=bool(share_trunk),
-                                        **({"kv": slot_kv} if slot_kv != "fp16" else {}))
+                                        [st.output_ids for st in members], params.stop_token_ids, share_trunk=m.share_trunk,
+                                        **m.loop_kwargs(one_token=True))
                 if loop is None:
                     raise RuntimeError("generate_batch: the model refused a batched decode loop over these caches")
                 yield from self._pump_slots(loop, members)
@@ -532,63 +484,18 @@ class GenerationEngine:
     # -- a stream of requests: continuous batching ------------------------------------------------
     def serve_plan(self, lookup: int = 0, slots: Optional[int] = None, slot_kv: Optional[str] = None,
                    keep_arenas: Optional[bool] = None, loop_prefill: bool = False) -> Tuple[bool, str]:
-        """``_serve_plan``; ``slot_kv`` (None: ``PC_SLOT_KV``): with "int8" the reason of a batched plan says that the loop reads
-        int8 K/V images, and with ``keep_arenas=False`` (None: not named) that no slot keeps an fp16 arena.  ``loop_prefill=True``
-        (``serve``'s): the reason of a plan in the lookup form says that admitted requests are prefilled inside the step; where
-        ``serve`` would refuse the mode (``check_loop_prefill``) this raises the same ValueError."""
-        batched, why = self._serve_plan(lookup, slots)
-        if loop_prefill:
-            self._loop_prefill(True, lookup, slots, os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv)
-            why += ", requests admitted into the running loop are prefilled inside its step (loop_prefill=True)"
-        if batched and (os.environ.get("PC_SLOT_KV", "fp16") if slot_kv is None else slot_kv) == "int8":
-            why += ", K/V read from int8 images (slot_kv='int8')"
-            if keep_arenas is not None and not keep_arenas:
-                why += ", no fp16 slot arenas: every prefill runs in one shared arena (keep_arenas=False)"
-        return batched, why
-
-    def _serve_plan(self, lookup: int = 0, slots: Optional[int] = None) -> Tuple[bool, str]:
         """``(batched, reason)``: whether ``serve`` runs its requests through one device loop that admits new prompts as slots free
         up (``model/llama_hip.py`` SlotLoop, ``each=True``), or one after another through ``generate``, and why.  Host logic only.
         Requests carry their own parameters, so both device loops must be on.  ``lookup`` = k > 0 (``serve(lookup=k)`` over
         ``slots`` slots): the reason also says which form of the loop runs -- the one with prompt-lookup drafts
-        (LookupSlotLoop, ``each=True``) or today's one-token loop, and why."""
-        why = self._no_batched_loop(True, True)
-        if why is not None:
-            return False, why
-        k, why = self._serve_drafts(lookup, slots)
-        if k:
-            return True, (f"one device loop with prompt-lookup drafts (lookup, k = {k}): up to k + 1 tokens per sequence and replay, "
-                          "new prompts admitted as slots free up")
-        if why is not None:
-            return True, "one device loop, one token per replay: " + why
-        return True, "one device loop, new prompts admitted as slots free up"
-
-    def _loop_prefill(self, loop_prefill: Optional[bool], lookup: int, slots: Optional[int], slot_kv: str) -> bool:
-        """Whether ``serve`` prefills admitted requests inside the lookup step: the argument, else ``PC_SERVE_LOOP_PREFILL``
-        (default 0).  True where it cannot run -- ``check_loop_prefill`` (model/llama_hip.py) -- raises ValueError, before
-        anything is allocated."""
-        if loop_prefill is None:
-            loop_prefill = os.environ.get("PC_SERVE_LOOP_PREFILL", "0") == "1"
-        if loop_prefill:
-            from .model.llama_hip import check_loop_prefill
-            batched, why = self._serve_plan()
-            k, no_drafts = self._serve_drafts(lookup, slots) if batched else (0, why)
-            check_loop_prefill(True, k, slot_kv, no_drafts)
-        return bool(loop_prefill)
-
-    def _serve_drafts(self, lookup: int, slots: Optional[int]) -> Tuple[int, Optional[str]]:
-        """``(k, None)``: ``serve(lookup=...)`` over ``slots`` slots runs the lookup form with k drafts per sequence and replay (k
-        above 15 is taken as 15); ``(0, why)``: it runs the one-token loop (``why`` None: ``lookup`` is off)."""
-        k = min(int(lookup), 15)
-        if k <= 0:
-            return 0, None
-        hf = getattr(self.lm, "hf_model", None)
-        offered = getattr(hf, "lookup_available", None)
-        if not hasattr(hf, "lookup_slot_loop") or offered is None or not offered():
-            return 0, "the model has no lookup step"
-        if slots is not None and int(slots) * (k + 1) > 64:
-            return 0, f"{int(slots)} slots x (k + 1 = {k + 1}) rows exceed the 64 rows of the weight-streaming projections"
-        return k, None
+        (LookupSlotLoop, ``each=True``) or today's one-token loop, and why.  ``slot_kv`` (None: ``PC_SLOT_KV``): with "int8" the
+        reason of a batched plan says that the loop reads int8 K/V images, and with ``keep_arenas=False`` (None: not named) that
+        no slot keeps an fp16 arena.  ``loop_prefill=True`` (``serve``'s): the reason of a plan in the lookup form says that
+        admitted requests are prefilled inside the step; where ``serve`` would refuse the mode (``check_loop_prefill``) this
+        raises the same ValueError."""
+        m = modes.resolve_serve(self._capabilities(True, True), slots, False, int(lookup), slot_kv, keep_arenas, bool(loop_prefill),
+                                validate=False)                    # (the plan reads PC_SLOT_KV from the environment, nothing else)
+        return m.batched, m.reason()
 
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
@@ -637,20 +544,16 @@ class GenerationEngine:
         already do.  ``last_serve_stats`` gains
         ``loop_prefills`` (requests prefilled inside the loop) and ``step_prefills`` (requests prefilled by a step of their
         own).  ValueError without the lookup form and with ``slot_kv="int8"``."""
-        if share_trunk is None:
-            share_trunk = os.environ.get("PC_SLOT_TRUNK", "0") == "1"
-        lookup = min(int(os.environ.get("PC_SERVE_LOOKUP", "0")) if lookup is None else int(lookup), 15)
-        slot_kv = self._slot_kv(slot_kv, share_trunk, lookup, *self._serve_plan(), serve=True)
-        drop = not self._keep_arenas(keep_arenas, slot_kv)
-        in_loop = self._loop_prefill(loop_prefill, lookup, getattr(cache_engine, "slots", None), slot_kv)
+        m = modes.resolve_serve(self._capabilities(True, True), getattr(cache_engine, "slots", None), share_trunk, lookup, slot_kv,
+                                keep_arenas, loop_prefill)
+        share_trunk, drafts, drop, in_loop = m.share_trunk, m.drafts, not m.keep_arenas, m.loop_prefill
 
         def unpack(req):
             if isinstance(req, (tuple, list)):
                 return req[0], (req[1] if req[1] is not None else params)
             return req, params
 
-        batched, _ = self._serve_plan()
-        if not batched:
+        if not m.batched:
             full = bool(getattr(self.lm, "use_full_position_ids", False))
             for r, req in enumerate(requests):
                 prompt, p = unpack(req)
@@ -661,8 +564,7 @@ class GenerationEngine:
 
         hf = self.lm.hf_model
         S = cache_engine.slots
-        drafts = self._serve_drafts(lookup, S)[0]     # k > 0: the lookup form (serve_plan(lookup, S) names the form and why)
-        sched = SlotScheduler(S, requests, share_trunk=bool(share_trunk))
+        sched = SlotScheduler(S, requests, share_trunk=share_trunk)    # (drafts = k > 0: the lookup form, serve_plan(lookup, S))
         stats = self.last_serve_stats = dict(replays=0, rows=0, live_rows=0, requests=0)
         if drafts:
             stats.update(tokens=0, steps=0)
@@ -756,12 +658,10 @@ class GenerationEngine:
                 loop = hf.lookup_slot_loop(pasts, toks0, poss, max_news, drafts, [st.corpus for st in pending], stop_ids=stops,
                                            slots=S, max_keys=cache_engine.max_ctx_length, trunks=trunks, each=True,
                                            slot_index=slots_, params=paramss, seeds=seeds_, histories=hists,
-                                           hist_cap=2 * cache_engine.max_ctx_length, **({"prompt_rows": True} if in_loop else {}),
-                                           **({"kv": slot_kv} if slot_kv != "fp16" else {}), **({"keep_arenas": False} if drop else {}))
+                                           hist_cap=2 * cache_engine.max_ctx_length, **m.loop_kwargs())
             if loop is None:
                 loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
-                                    max_keys=cache_engine.max_ctx_length, trunks=trunks,
-                                    **({"kv": slot_kv} if slot_kv != "fp16" else {}), **({"keep_arenas": False} if drop else {}))
+                                    max_keys=cache_engine.max_ctx_length, trunks=trunks, **m.loop_kwargs(one_token=True))
             if loop is None:
                 raise RuntimeError("serve: the model refused a batched decode loop over these caches")
             read_k = _reader(loop)[1]                              # (keep_arenas=False admits the rest of the first fill at once)

@@ -18,6 +18,7 @@ from typing import Callable, List, Optional, Tuple
 
 import torch
 
+from ..modes import check_keep_fp16, check_weight_format
 from ..pml import Preprocessor, PreprocessorList, escape_xml  # noqa: F401  (re-exported like the reference)
 from .config import FALCON_SHAPES, MPT_SHAPES, SHAPES, FalconShape, LlamaShape, MptShape
 from .tokenizer import StandInTokenizer
@@ -152,7 +153,7 @@ class _LlamaFamily(LanguageModel):
 
     def __init__(self, name: Optional[str] = None, device: str = "cuda:0", shape: Optional[LlamaShape] = None,
                  weights=None, tokenizer=None, random_init: bool = False, seed: int = 0, **_hf_kwargs):
-        from .llama_hip import LlamaHIP, check_keep_fp16, check_weight_format
+        from .llama_hip import LlamaHIP
         from . import weights as W
 
         fmt, int8 = _weight_format(_hf_kwargs), bool(_hf_kwargs.get("load_in_8bit", False))
@@ -210,7 +211,6 @@ class Falcon(LanguageModel):
                  weights=None, tokenizer=None, random_init: bool = False, seed: int = 0, **_hf_kwargs):
         from .falcon_hip import FalconHIP
         from . import weights as W
-        from .llama_hip import check_weight_format
 
         check_weight_format(_weight_format(_hf_kwargs), False, llama=False)      # (before any weight is read or drawn)
 
@@ -261,7 +261,6 @@ class Mpt(LanguageModel):
                  weights=None, tokenizer=None, random_init: bool = False, seed: int = 0, **_hf_kwargs):
         from .mpt_hip import MptHIP
         from . import weights as W
-        from .llama_hip import check_weight_format
 
         check_weight_format(_weight_format(_hf_kwargs), False, llama=False)      # (before any weight is read or drawn)
 

@@ -23,7 +23,8 @@ import torch
 
 from .. import _native
 from .config import FalconShape
-from .llama_hip import LlamaHIP, check_weight_format
+from ..modes import check_weight_format
+from .llama_hip import LlamaHIP
 
 
 class FalconHIP(LlamaHIP):

@@ -35,6 +35,9 @@ import torch
 import numpy as np
 
 from .. import _native
+# the pure refusals of formats and loop modes live in modes.py (no torch); the names stay importable from here
+from ..modes import (SLOT_KV, WEIGHT_FORMATS, check_keep_fp16, check_loop_prefill, check_slot_keep_arenas,  # noqa: F401
+                     check_slot_kv, check_weight_format, parse_keep_arenas, parse_keep_fp16)
 from .config import LlamaShape
 from .kv_arena import KVArena, StagedKV, arena_from_past, common_trunks
 
@@ -1171,120 +1174,6 @@ class LookupSlotLoopQ8Only(_ImageOnly, LookupSlotLoopQ8):
     residency under the lookup step.  The fresh-row buffers hold the step's ``k + 1`` rows per plane, the cap word of a slot is
     ``qcap`` and ``kv_base`` holds the fresh addresses, so the draft / arm / verify launches are ``LookupSlotLoop``'s; a sequence
     whose image is full ends by the device's "no room for a step" rule."""
-
-
-WEIGHT_FORMATS = ("fp16", "mxfp4")
-
-
-def check_weight_format(weight_format: str, int8_weights: bool, shape=None, llama: bool = True) -> None:
-    """``ValueError`` for a weight format this model cannot load -- raised before anything is allocated."""
-    if weight_format not in WEIGHT_FORMATS:
-        raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, not {weight_format!r}")
-    if weight_format != "mxfp4":
-        return
-    if not llama:
-        raise ValueError("weight_format='mxfp4' is implemented for the Llama family only (not Falcon / MPT)")
-    if int8_weights:
-        raise ValueError("weight_format='mxfp4' and load_in_8bit / int8_weights exclude each other")
-    dims = (("hidden_size", shape.hidden_size), ("intermediate_size", shape.intermediate_size),
-            ("num_attention_heads * head_dim", shape.num_attention_heads * shape.head_dim))
-    for name, v in dims:
-        if v % 128:
-            raise ValueError(f"weight_format='mxfp4' needs {name} to be a multiple of 128 (a 16-byte lane load of the 4-bit "
-                             f"image is four 32-feature MX blocks); {name} = {v}")
-
-
-SLOT_KV = ("fp16", "int8")
-
-
-def check_slot_kv(kv: str, share_trunk: bool = False, lookup: int = 0, head_dim: Optional[int] = None, no_loop: Optional[str] = None,
-                  not_batched: Optional[str] = None, lookup_q8: bool = False) -> None:
-    """``ValueError`` naming the conflict for a ``slot_kv`` / ``kv`` mode the batched decode loop cannot run -- raised before
-    anything is allocated.  Pure.  ``no_loop``: why the model has no slot loop (Falcon / MPT, ``load_in_8bit``,
-    ``PC_DECODE_TAIL=1``), ``not_batched``: why ``batch_plan`` / ``serve_plan`` would not decode this batch in the device loop
-    (None: they would).  ``lookup_q8``: the caller is ``serve`` / ``lookup_slot_loop`` and the model has the lookup step over
-    int8 images (``lookup_slot_q8_available``) -- ``lookup > 0`` is then no conflict."""
-    if kv not in SLOT_KV:
-        raise ValueError(f"slot_kv must be one of {SLOT_KV}, not {kv!r}")
-    if kv != "int8":
-        return
-    if share_trunk:
-        raise ValueError("slot_kv='int8' and share_trunk exclude each other (the shared-trunk attention reads the leader's fp16 "
-                         "arena; int8 images under share_trunk are not implemented)")
-    if int(lookup) > 0 and not lookup_q8:
-        raise ValueError("slot_kv='int8' and lookup > 0 exclude each other (the k + 1 row verify step reads the fp16 arenas; "
-                         "int8 images under lookup are not implemented)")
-    if no_loop is not None:
-        raise ValueError(f"slot_kv='int8' needs the batched decode loop, which this model does not have: {no_loop}")
-    if head_dim is not None and head_dim != 128:
-        raise ValueError(f"slot_kv='int8' is implemented for head_dim 128 only (pc_attn_decode_slots_q8); head_dim = {head_dim}")
-    if not_batched is not None:
-        raise ValueError(f"slot_kv='int8' needs a batch decoded in the device loop, and this one is not: {not_batched}")
-
-
-def check_loop_prefill(loop_prefill: bool, drafts: int, kv: str = "fp16", why: Optional[str] = None) -> None:
-    """``ValueError`` naming the conflict for ``serve(loop_prefill=True)`` where it cannot run -- raised before anything is
-    allocated.  Pure.  ``drafts``: the k ``serve`` runs the lookup form with (``_serve_drafts``; 0: it does not, ``why`` says
-    why where there is a reason beyond ``lookup`` being off)."""
-    if not loop_prefill:
-        return
-    if int(drafts) <= 0:
-        raise ValueError("loop_prefill=True needs the lookup form of the serving loop (serve(lookup=k), k > 0: a question is fed "
-                         "through the k draft rows of the step), and it does not run: " + (why or "lookup is off"))
-    if kv == "int8":
-        raise ValueError("loop_prefill=True and slot_kv='int8' exclude each other (question rows are appended as fp16 rows; "
-                         "forced rows over int8 images are not implemented)")
-
-
-def check_slot_keep_arenas(keep_arenas: bool, kv: str, generate_batch: bool = False) -> None:
-    """``ValueError`` for ``keep_arenas=False`` (int8-only slot residency) where it cannot run -- raised before anything
-    is allocated, behind ``check_slot_kv``'s own refusals of ``kv``.  Pure."""
-    if keep_arenas:
-        return
-    if generate_batch:
-        raise ValueError("keep_arenas=False is not for generate_batch: its callers hand in one live fp16 arena per sequence, so "
-                         "there is nothing to save; serve(slot_kv='int8', keep_arenas=False) prefills every request in one arena")
-    if kv != "int8":
-        raise ValueError(f"keep_arenas=False needs slot_kv='int8' (without the int8 images the fp16 arenas are the only K/V a "
-                         f"slot has); slot_kv = {kv!r}")
-
-
-def parse_keep_arenas(value) -> bool:
-    """``PC_SLOT_KEEP_ARENAS``: unset, empty or ``1`` keeps the fp16 slot arenas under ``slot_kv="int8"``, ``0`` drops them."""
-    if value is None or value in ("", "1"):
-        return True
-    if value == "0":
-        return False
-    raise ValueError(f"PC_SLOT_KEEP_ARENAS must be 0 or 1, not {value!r}")
-
-
-def parse_keep_fp16(value) -> bool:
-    """``PC_W4_KEEP_FP16``: unset, empty or ``1`` keeps the fp16 images of an MXFP4 model's decoder linears, ``0`` drops them."""
-    if value is None or value in ("", "1"):
-        return True
-    if value == "0":
-        return False
-    raise ValueError(f"PC_W4_KEEP_FP16 must be 0 or 1, not {value!r}")
-
-
-def check_keep_fp16(keep_fp16, weight_format: str, env=None) -> bool:
-    """The ``keep_fp16`` a model runs with: the argument, else ``PC_W4_KEEP_FP16`` for an MXFP4 model, else True.  ``ValueError``
-    for a combination in which dropping the fp16 images leaves a path without weights -- raised before anything is allocated."""
-    env = os.environ if env is None else env
-    if keep_fp16 is None:
-        keep_fp16 = parse_keep_fp16(env.get("PC_W4_KEEP_FP16")) if weight_format == "mxfp4" else True
-    if keep_fp16:
-        return True
-    if weight_format != "mxfp4":
-        raise ValueError(f"keep_fp16=False needs weight_format='mxfp4' (the fp16 images are all a weight_format={weight_format!r} "
-                         "model has)")
-    if env.get("PC_W4_STREAM", "1") == "0":
-        raise ValueError("keep_fp16=False and PC_W4_STREAM=0 exclude each other: PC_W4_STREAM=0 builds no 4-bit images, so nothing "
-                         "would be left to expand")
-    if env.get("PC_DENSE_LO8", "0") == "1":
-        raise ValueError("keep_fp16=False and PC_DENSE_LO8=1 exclude each other: the int8 residual-plane GEMM keeps int8 images of the "
-                         "fp16 weights")
-    return False
 
 
 # weight_format="mxfp4": most rows of a step that streams the 4-bit images (PC_W4_MAX_ROWS, clamped to 16..64).  64: at 17, 32, 48

@@ -21,7 +21,8 @@ import torch
 
 from .. import _native
 from .config import MptShape
-from .llama_hip import CausalLMOutput, LlamaHIP, check_weight_format, prime_graph_capture
+from ..modes import check_weight_format
+from .llama_hip import CausalLMOutput, LlamaHIP, prime_graph_capture
 
 _LOG2E = 1.4426950408889634
 
