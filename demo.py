@@ -69,6 +69,10 @@ def main():
     ap.add_argument("--drop-fp16", action="store_true",
                     help="with --weights mxfp4: keep only the 4-bit images of the decoder weights resident (keep_fp16=False; default: "
                          "PC_W4_KEEP_FP16); passes above 64 rows expand each projection just in time")
+    ap.add_argument("--logprobs", type=int, default=None,
+                    help="print every generated token with its log-probability and its N most likely alternatives (0..8), under the "
+                         "model's own distribution: the log-softmax of the raw logits, before temperature, penalty, top-p and top-k "
+                         "(GenerationParameters.logprobs; with --batch for all sequences, with --serve as serve(logprobs=N))")
     a = ap.parse_args()
     skw = dict(keep_arenas=False) if a.slot_drop_fp16 else {}
     wkw = dict(weight_format=a.weights, **(dict(keep_fp16=False) if a.drop_fp16 else {}))
@@ -92,7 +96,8 @@ def main():
     print(f"module KV ({cache_engine.module_kv}, {cache_engine.module_memory} tier): " +
           ", ".join(f"{nm} {b / 2 ** 20:.1f} MiB" for nm, b in cache_engine.module_bytes().items()))
     params = GenerationParameters(temperature=1.0, repetition_penalty=1.0, top_p=0.95, top_k=-1,
-                                  max_new_tokens=a.max_new_tokens, stop_token_ids=lm.stop_token_ids, stop_str=lm.stop_str)
+                                  max_new_tokens=a.max_new_tokens, stop_token_ids=lm.stop_token_ids, stop_str=lm.stop_str,
+                                  logprobs=a.logprobs)
     prompt = Prompt(prompt_text, preproc)
     for no_cache in (False, True, False):       # the first pass also warms the hipGraph / allocator
         token_ids, position_ids, cache_time, cache = cache_engine.process(
@@ -106,6 +111,11 @@ def main():
               f"gather {cache_time:7.3f} ms | first forward {last.elapsed_time:8.3f} ms | "
               f"TTFT {cache_time + last.elapsed_time:8.3f} ms | {a.max_new_tokens} tokens in {last.response_time:8.2f} ms")
     print("Assistant:", (last.new_text[:120] + " ...") if last else "")
+    if last is not None and last.logprobs is not None:
+        for r in last.logprobs:                  # one line per token: the token, then its alternatives by log-probability
+            alts = "  ".join(f"{lm.decode([i])!r} {lp:.3f}" for i, lp in r.top)
+            print(f"  {lm.decode([r.token])!r:>16} {r.logprob:9.3f}" + (f"   | {alts}" if alts else ""))
+        print(f"  mean log-probability {sum(r.logprob for r in last.logprobs) / len(last.logprobs):.3f} over {len(last.logprobs)} tokens")
     if a.batch:
         import time
         # the same module selection with N different questions, one staged buffer (slot) each, decoded in one device loop
@@ -148,7 +158,7 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk, lookup=a.lookup,
-                                              slot_kv=a.slot_kv, **skw, **pkw):
+                                              slot_kv=a.slot_kv, logprobs=a.logprobs, **skw, **pkw):
                 lasts[r] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

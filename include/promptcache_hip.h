@@ -1071,6 +1071,27 @@ int pc_lookup_verify_slots_prompt(const float* logits, int64_t ldl, int32_t voca
                                   const int32_t* stop_ids, int32_t* ring, int32_t* counters, int32_t* forced, int32_t ring_cap,
                                   void* stream);
 
+/* ---- per-token log-probabilities (csrc/pc_logprob.hip; no reference counterpart) -----------------------------------------------------
+ * pc_token_logprobs: for each of `rows` rows of fp32 logits [rows][vocab] (row stride ldl elements, 4-byte aligned only, ldl may be
+ * odd), the log-probability of the row's token and of the top_n most likely tokens.  Exactly one of tok64 / tok32 is non-null; the
+ * token of row r is tok[r * tok_stride].  1 <= rows <= 64, 0 <= top_n <= PC_LOGPROBS_MAX_TOP, top_n < vocab < 2^24, ldl >= vocab,
+ * tok_stride >= 1.
+ *   The distribution is the log-softmax of the RAW logits, the model's own: m = max of the row, s = sum exp(x - m) in fp32,
+ *   lp(j) = (x[j] - m) - log(s).  It comes BEFORE temperature, repetition penalty, top-p and top-k: what a sampler made of the row
+ *   does not enter (a token that top-k would have removed still has its finite log-probability here).
+ *   out_ids int32 [rows][1 + top_n], out_lp float [rows][1 + top_n]: entry 0 is the row's token and its lp, entries 1 .. top_n the
+ *   top_n most likely tokens ordered by (value descending, index ascending) -- "lowest index among equal maxima", extended to the
+ *   whole order.  The row's token may appear among them again.
+ *   -inf entries contribute 0 to s; NaN entries are treated as -inf everywhere (they rank as -inf, in index order, with lp -inf).
+ *   A row whose maximum is not finite (no finite entry, or a +inf) writes NaN log-probabilities and ids -1 in every entry.
+ *   A token outside [0, vocab) writes id -1 and lp NaN in entry 0 and leaves entries 1 .. top_n correct: the guard for pad rows,
+ *   whose token is unspecified, and for the stale rows of idle slots.
+ * One launch, one workgroup per row; no state, no counter: nothing but the two output arrays is written (ordinary vector stores),
+ * and the result of a row depends on that row alone.  Argument errors -> PC_ERR_ARG with nothing launched. */
+#define PC_LOGPROBS_MAX_TOP 8
+int pc_token_logprobs(const float* logits, int64_t ldl, int32_t vocab, int32_t rows, const int64_t* tok64, const int32_t* tok32,
+                      int64_t tok_stride, int32_t top_n, int32_t* out_ids, float* out_lp, void* stream);
+
 /* Diagnostics used by the GPU test-suite: dumps the MFMA C/D lane map and the LDS transpose-read
  * map the attention kernel relies on (probe_kernel in csrc/pc_misc.hip). */
 /* dev hook (tools/gemm_trace.py): weight-streaming launches issued by this thread stamp per-wave wall-clock times

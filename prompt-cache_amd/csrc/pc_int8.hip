@@ -252,12 +252,13 @@ constexpr int kMaxCols = 512;       // outlier columns handled per batch of the 
 constexpr int kCorrRows = 16;       // activation rows staged per pass (one per row slot of the workgroup)
 constexpr int kCorrCols = 16;       // output columns per workgroup of the correction kernel
 
-template <bool FRAG>
+// `frag` (uniform over the launch): x / codes are fragment planes, not row-major rows -- it only chooses the offset of a staged
+// element, so the two layouts share one kernel
 __global__ __launch_bounds__(256) void outlier_corr_kernel(const unsigned char* __restrict__ flags, int K, const _Float16* __restrict__ x,
                                                            const _Float16* __restrict__ codes, int64_t ldx, const float* __restrict__ x_scale,
                                                            const signed char* __restrict__ cbt, int64_t ldt, const float* __restrict__ w_scale,
                                                            const int32_t* __restrict__ row_perm, int T, int N, float* __restrict__ corr,
-                                                           int64_t ldc, int32_t* __restrict__ has) {
+                                                           int64_t ldc, int32_t* __restrict__ has, int frag) {
     __shared__ int cols[kMaxCols];
     __shared__ int cnt[257];
     __shared__ __attribute__((aligned(16))) unsigned char lf[16384];       // the flag bytes (K <= 16384)
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(256) void outlier_corr_kernel(const unsigned char* 
             // out of LDS: with the loads inside the column loop a 600-column batch took 400 us
             for (int e = tid; e < nt * nb; e += 256) {
                 const int tt = e / nb, j = e - tt * nb;
-                const int64_t xo = FRAG ? frag_off(t0 + tt, cols[j], KS) : (int64_t)(t0 + tt) * ldx + cols[j];
+                const int64_t xo = frag ? frag_off(t0 + tt, cols[j], KS) : (int64_t)(t0 + tt) * ldx + cols[j];
                 xl[tt][j] = x[xo];
                 cl[tt][j] = codes[xo];
             }
@@ -408,12 +409,9 @@ PC_EXPORT int pc_outlier_corr(const void* flags, int32_t K, const void* x, const
                "pc_outlier_corr: null pointer or short strides");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(pc_ceil_div(N, kCorrCols));
-    if (frag)
-        hipLaunchKernelGGL((outlier_corr_kernel<true>), grid, dim3(256), 0, s, (const unsigned char*)flags, K, (const _Float16*)x,
-                           (const _Float16*)codes, ldx, x_scale, (const signed char*)w_codes_t, ldt, w_scale, row_perm, T, N, corr, ldc, has);
-    else
-        hipLaunchKernelGGL((outlier_corr_kernel<false>), grid, dim3(256), 0, s, (const unsigned char*)flags, K, (const _Float16*)x,
-                           (const _Float16*)codes, ldx, x_scale, (const signed char*)w_codes_t, ldt, w_scale, row_perm, T, N, corr, ldc, has);
+    hipLaunchKernelGGL(outlier_corr_kernel, grid, dim3(256), 0, s, (const unsigned char*)flags, K, (const _Float16*)x,
+                       (const _Float16*)codes, ldx, x_scale, (const signed char*)w_codes_t, ldt, w_scale, row_perm, T, N, corr, ldc, has,
+                       frag ? 1 : 0);
     return pc_check_launch("outlier_corr_kernel");
 }
 

@@ -260,6 +260,7 @@ SIGNATURES = {
     "pc_gemm_dense": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     "pc_gemm_dense_qkv_rope": (C.c_int, [_vp, _vp]),
     "pc_gemm_dense_ws": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "pc_token_logprobs": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
 
 # Entry points of -DPC_DEV_SWEEPS builds only (csrc/pc_dev.h: measured negative results kept for A/B; not in the product library
@@ -1298,6 +1299,27 @@ def sample_advance(logits, vocab: int, params, history, ids, pos, past, ring, co
                                   past.data_ptr(), ring.data_ptr(), counter.data_ptr(), ring.numel(), _ptr(processed_out),
                                   current_stream() if stream is None else stream)
     check(rc, "pc_sample_advance")
+
+
+LOGPROBS_MAX_TOP = 8            # PC_LOGPROBS_MAX_TOP
+
+
+def token_logprobs(logits, ldl: int, vocab: int, rows: int, tokens, tok_stride: int, top_n: int, out_ids, out_lp,
+                   stream: Optional[int] = None) -> None:
+    """Log-softmax of the RAW fp32 ``logits`` rows (before temperature, penalty, top-p, top-k) at each row's token and at its ``top_n``
+    most likely tokens (pc_token_logprobs).  ``tokens``: int64 or int32 device tensor, row r's token at ``tokens[r * tok_stride]``;
+    ``out_ids`` int32 / ``out_lp`` fp32 ``[rows][1 + top_n]``: entry 0 the row's token, then the alternatives by (value descending,
+    index ascending)."""
+    import torch
+    t64 = tokens.dtype == torch.int64
+    assert t64 or tokens.dtype == torch.int32, tokens.dtype
+    assert out_ids.dtype == torch.int32 and out_lp.dtype == torch.float32 and logits.dtype == torch.float32
+    assert out_ids.numel() >= rows * (1 + top_n) and out_lp.numel() >= rows * (1 + top_n)
+    assert tokens.numel() > (rows - 1) * tok_stride and logits.numel() >= (rows - 1) * ldl + vocab
+    rc = load().pc_token_logprobs(logits.data_ptr(), ldl, vocab, rows, tokens.data_ptr() if t64 else None,
+                                  None if t64 else tokens.data_ptr(), tok_stride, top_n, out_ids.data_ptr(), out_lp.data_ptr(),
+                                  current_stream() if stream is None else stream)
+    check(rc, "pc_token_logprobs")
 
 
 # ---- LLM.int8 (pc_int8.hip) -------------------------------------------------------------------------------------------

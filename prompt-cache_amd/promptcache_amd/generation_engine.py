@@ -39,6 +39,12 @@ class GenerationParameters:
     stop_token_ids: List[int] = field(default_factory=list)
     stop_str: List[str] = field(default_factory=list)
     echo: bool = True
+    # None: off.  n in 0..8: every generated token comes with its log-probability and those of the n most likely tokens, under the
+    # model's own distribution -- the log-softmax of the raw logits, BEFORE temperature, repetition penalty, top-p and top-k
+    logprobs: Optional[int] = None
+
+    def __post_init__(self):
+        modes.check_logprobs(self.logprobs, what="GenerationParameters.logprobs")
 
     @property
     def greedy(self) -> bool:
@@ -71,11 +77,24 @@ def is_partial_stop(output: str, stop_str: str) -> bool:
 
 
 @dataclass
+class TokenLogprob:
+    """One generated token: its id, its log-probability under the model's own distribution (the log-softmax of the raw logits,
+    before temperature, repetition penalty, top-p and top-k) and the ``GenerationParameters.logprobs`` most likely tokens of that
+    step as ``(id, logprob)``, by (logprob descending, id ascending); the token itself may be among them."""
+    token: int
+    logprob: float
+    top: List[Tuple[int, float]] = field(default_factory=list)
+
+
+@dataclass
 class Output:
     text: str
     new_text: str
     response_time: float = 0.0
     elapsed_time: float = 0.0
+    # ``GenerationParameters.logprobs``: one entry per token generated so far, stop id included -- cumulative like ``new_text``, but
+    # a stop string cuts the text, not the list.  None when not asked for.
+    logprobs: Optional[List[TokenLogprob]] = None
 
 
 class _Timer:
@@ -107,21 +126,29 @@ class _Stream:
         self.device_stops = params.stop_token_ids if device_stops is None else device_stops
         self.total_ms = self.ttft_ms = 0.0
         self.last_step, self.done = params.max_new_tokens - 1, False
+        self.want_lp = getattr(params, "logprobs", None)      # n: every token comes with a record (``emit``'s ``lp``)
+        self.lps: Optional[List[TokenLogprob]] = None if self.want_lp is None else []
 
-    def emit(self, token: int) -> Optional[Output]:
+    def emit(self, token: int, lp=None) -> Optional[Output]:
         """Take the next token: append it, test the stop ids, and at a streaming point (every ``stream_interval`` tokens, the last
         step, a stop id) render the text, cut it at a stop string and hold it back while its tail may still grow into one.
-        Sets ``done``; -> the Output to yield, if any.  The step is the number of tokens taken before this one."""
+        Sets ``done``; -> the Output to yield, if any.  The step is the number of tokens taken before this one.
+        ``lp``: the token's record ``(token, logprob, [(id, logprob), ...])`` where the parameters ask for log-probabilities -- kept
+        with its first ``logprobs`` alternatives (a serving loop's step ranks as many as ``serve(logprobs=...)`` said)."""
         step = len(self.new_ids)
         self.output_ids.append(token)
         self.new_ids.append(token)
+        if self.lps is not None:
+            if lp is None:
+                raise RuntimeError("a token arrived without its log-probabilities although GenerationParameters.logprobs asks for them")
+            self.lps.append(TokenLogprob(int(token), float(lp[1]), [(int(a), float(b)) for a, b in lp[2][:self.want_lp]]))
         fin = token in self.params.stop_token_ids
         out = None
         if step % self.stream_interval == 0 or step == self.last_step or fin:
             text, new_text, hit, partial = self.render(self.output_ids, self.new_ids, self.params.stop_str)
             fin = fin or hit
             if not partial:
-                out = Output(text, new_text, self.total_ms, self.ttft_ms)
+                out = Output(text, new_text, self.total_ms, self.ttft_ms, None if self.lps is None else list(self.lps))
         self.done = fin or step >= self.last_step
         return out
 
@@ -143,6 +170,16 @@ def _reader(loop):
         token = loop.token(*at)
         return [] if token is None else [token]
     return one, 0
+
+
+def _first_logprobs(hf, logits_row, token: int, n: Optional[int]):
+    """The record of a token drawn on the host side from ``logits_row`` (the prefill's last row, a stepped forward's row): one
+    eager launch (``LlamaHIP.token_logprobs``).  None when not asked for; a model without the call is an error, not a fallback."""
+    if n is None:
+        return None
+    if not hasattr(hf, "token_logprobs"):
+        raise RuntimeError("GenerationParameters.logprobs needs a model with token_logprobs (pc_token_logprobs)")
+    return hf.token_logprobs(logits_row, [token], n)[0]
 
 
 class GenerationEngine:
@@ -208,8 +245,9 @@ class GenerationEngine:
 
     # -- the two pumps ----------------------------------------------------------------------------
     @staticmethod
-    def _pump(loop, total: int):
-        """Read a single-sequence device loop: yields ``(token, ms)`` until ``total`` tokens came or a step is empty.  ``ms`` is the
+    def _pump(loop, total: int, want_lp: bool = False):
+        """Read a single-sequence device loop: yields ``(token, ms)`` -- ``(token, ms, record)`` with ``want_lp``, the only case in
+        which the loop is asked for ``logprobs(i)`` -- until ``total`` tokens came or a step is empty.  ``ms`` is the
         step's device time on its first token and 0.0 on the others.  Every step of such a loop is one hipGraph replay that also
         picks the token(s) and feeds the next replay (model/llama_hip.py GreedyLoop, SampleLoop: one token; LookupLoop,
         SampleLookupLoop: 1..k+1 tokens).  The host keeps ONE replay in flight ahead of the step it reads, so the GPU never waits
@@ -226,8 +264,9 @@ class GenerationEngine:
             toks, ms = read(i), loop.elapsed_ms(i)
             if not toks:
                 return
-            for token in toks:
-                yield token, ms
+            lps = loop.logprobs(i) if want_lp else None
+            for t, token in enumerate(toks):
+                yield (token, ms, lps[t]) if want_lp else (token, ms)
                 ms = 0.0
             got += len(toks)
             i += 1
@@ -238,7 +277,8 @@ class GenerationEngine:
         loop) is done; yields ``(index, Output)``.  One replay ahead as in ``_pump``, while the step in flight cannot exhaust
         every budget.  A sequence ends at a stop id or its budget, which the device sees too, at an empty step (the device
         switched the slot off) or for a reason only the host knows (``_Stream.ended_on_the_host``): then the host switches
-        the slot off between replays (``loop.kill``) and drops the rest of the step."""
+        the slot off between replays (``loop.kill``) and drops the rest of the step.  A loop is asked for ``logprobs(j, i)`` only
+        for a stream whose parameters ask for them."""
         read, k = _reader(loop)
         i = 0
         while not all(st.done for st in seqs):
@@ -256,8 +296,9 @@ class GenerationEngine:
                     st.done = True
                     continue
                 st.total_ms += ms
-                for token in toks:
-                    out = st.emit(token)
+                lps = loop.logprobs(j, i) if st.lps is not None else None
+                for t, token in enumerate(toks):
+                    out = st.emit(token, None if lps is None else lps[t])
                     kill = st.ended_on_the_host(token)
                     if kill and not k:                             # (a one-token loop is told before the yield, a multi-token
                         loop.kill(j)                               # loop after it: each as it was before there was one pump)
@@ -280,13 +321,15 @@ class GenerationEngine:
             token = self._pick(st.params.get_logits_processor()(None, logits[:, -1, :])[0], True)
         else:
             token = self.lm.hf_model.sample_token(logits[0, -1], st.params, st.seed, st.output_ids)
-        return st.emit(token)
+        return st.emit(token, _first_logprobs(getattr(self.lm, "hf_model", None), logits[0, -1], token, st.want_lp))
 
     # -- the generator ----------------------------------------------------------------------------
     @torch.inference_mode()
     def generate(self, token_ids: List[int], position_ids: List[int], params: GenerationParameters,
                  cache=None, stream_interval: int = 2, use_full_position_ids: bool = False
                  ) -> Generator[Output, None, None]:
+        n_lp = modes.check_logprobs(params.logprobs, what="GenerationParameters.logprobs")
+        lp_kw = {} if n_lp is None else {"logprobs": n_lp}      # (a loop is handed nothing new when they are off)
         processors = params.get_logits_processor()
         prompt_positions = list(position_ids)
         first_free = max(prompt_positions) + 1
@@ -322,7 +365,8 @@ class GenerationEngine:
                 positions = (prompt_positions + list(range(first_free, first_free + step))) if use_full_position_ids \
                     else [first_free + step]
                 logits, past, ms = self._forward([st.new_ids[-1]], positions, past)
-                yield pick(logits), ms
+                token = pick(logits)
+                yield (token, ms) if n_lp is None else (token, ms, _first_logprobs(hf, logits[0, -1], token, n_lp))
 
         try:
             if params.max_new_tokens < 1:
@@ -337,7 +381,8 @@ class GenerationEngine:
                 print(f"Prefill latency: {ms:.2f} ms")
             if want_sample:
                 want_sample = hf.can_loop(past)
-            out = st.emit(pick(logits))
+            token = pick(logits)
+            out = st.emit(token, _first_logprobs(hf, logits[0, -1], token, n_lp))
             if out is not None:
                 yield out
             # 2. a device loop, where there is one and something is left to decode
@@ -347,15 +392,15 @@ class GenerationEngine:
                 if want_lookup or want_lookup_sample:
                     sampled = dict(params=params, seed=seed, history_ids=st.output_ids) if want_lookup_sample else {}
                     loop = hf.lookup_loop(past, token, position, st.last_step, min(self.lookup, 15),
-                                          self._lookup_corpus(cache, token_ids), **sampled)
+                                          self._lookup_corpus(cache, token_ids), **sampled, **lp_kw)
                 elif want_loop:
-                    loop = hf.greedy_loop(past, token, position, params.max_new_tokens)
+                    loop = hf.greedy_loop(past, token, position, params.max_new_tokens, **lp_kw)
                 else:
-                    loop = hf.sample_loop(past, token, position, params.max_new_tokens, params, seed, st.output_ids)
+                    loop = hf.sample_loop(past, token, position, params.max_new_tokens, params, seed, st.output_ids, **lp_kw)
             # 3. the rest: that loop's tokens, or one forward per token
-            for token, ms in (host_steps() if loop is None else self._pump(loop, st.last_step)):
+            for token, ms, *lp in (host_steps() if loop is None else self._pump(loop, st.last_step, n_lp is not None)):
                 st.total_ms += ms
-                out = st.emit(token)
+                out = st.emit(token, *lp)
                 if out is not None:
                     yield out
                 if st.done:                                        # (before the source is asked for more)
@@ -433,7 +478,12 @@ class GenerationEngine:
         an arena MORE memory per slot.  ValueError with ``share_trunk``, ``lookup`` > 0, head_dim other than 128, a model without
         the slot loop or a batch that is not decoded in the device loop.
         ``keep_arenas=False`` (``serve``'s int8-only residency) raises ValueError here: the callers hand in one live
-        arena per sequence, so there is nothing to save."""
+        arena per sequence, so there is nothing to save.
+        ``params.logprobs`` = n covers all sequences: the first tokens through ``LlamaHIP.token_logprobs``, the rest
+        from the loop's own node (``slot_loop(logprobs=n)`` / ``lookup_slot_loop(logprobs=n)``); one ``generate`` after another
+        keeps them."""
+        n_lp = modes.check_logprobs(params.logprobs, what="GenerationParameters.logprobs")
+        lp_kw = {} if n_lp is None else {"logprobs": n_lp}      # (a model from before the option is handed nothing new)
         requests = [(list(t), list(p), c) for t, p, c in requests]
         hf = getattr(self.lm, "hf_model", None)
         # every cache must be a staged batch-1 arena, no two the same
@@ -466,11 +516,11 @@ class GenerationEngine:
                 if m.drafts:
                     loop = hf.lookup_slot_loop(*first, m.drafts,
                                                [self._lookup_corpus(requests[st.index][2], requests[st.index][0]) for st in members],
-                                               stop_ids=params.stop_token_ids, share_trunk=m.share_trunk)
+                                               stop_ids=params.stop_token_ids, share_trunk=m.share_trunk, **lp_kw)
                 if loop is None:
                     loop = hf.slot_loop(*first, None if plain_greedy else params, [st.seed for st in members],
                                         [st.output_ids for st in members], params.stop_token_ids, share_trunk=m.share_trunk,
-                                        **m.loop_kwargs(one_token=True))
+                                        **m.loop_kwargs(one_token=True), **lp_kw)
                 if loop is None:
                     raise RuntimeError("generate_batch: the model refused a batched decode loop over these caches")
                 yield from self._pump_slots(loop, members)
@@ -500,7 +550,7 @@ class GenerationEngine:
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
               share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None,
-              keep_arenas: Optional[bool] = None, loop_prefill: Optional[bool] = None
+              keep_arenas: Optional[bool] = None, loop_prefill: Optional[bool] = None, logprobs: Optional[int] = None
               ) -> Generator[Tuple[int, Output], None, None]:
         """Continuous batching over ``cache_engine.slots`` slots.  ``requests``: any iterable -- it may be lazy -- of ``Prompt`` or
         ``(Prompt, GenerationParameters)``; ``params`` is the default for bare prompts.  Requests are numbered in the order they
@@ -543,15 +593,27 @@ class GenerationEngine:
         appended without the serial prefill's residual tail, so logits differ from the serial flow at the level decoded rows
         already do.  ``last_serve_stats`` gains
         ``loop_prefills`` (requests prefilled inside the loop) and ``step_prefills`` (requests prefilled by a step of their
-        own).  ValueError without the lookup form and with ``slot_kv="int8"``."""
+        own).  ValueError without the lookup form and with ``slot_kv="int8"``.
+        ``logprobs`` = n in 0..8 (None: ``PC_SERVE_LOGPROBS``, unset: off): the requests are lazy and the step is
+        captured once, so the capacity is a mode of the loop -- its step carries the log-probability node at ``top_n = n``.  A
+        request whose ``params.logprobs`` is m <= n gets m alternatives per token, one with None gets ``Output.logprobs = None``, and
+        one that asks for more than n -- or asks at all while this is off -- raises ValueError naming ``serve(logprobs=...)`` before
+        its prefill.  Works with ``lookup``, ``share_trunk``, ``slot_kv="int8"`` and ``keep_arenas=False``; ValueError together with
+        ``loop_prefill`` (``modes.check_logprobs``: a request admitted that way draws its first token inside the step from a forced
+        row)."""
         m = modes.resolve_serve(self._capabilities(True, True), getattr(cache_engine, "slots", None), share_trunk, lookup, slot_kv,
-                                keep_arenas, loop_prefill)
+                                keep_arenas, loop_prefill, logprobs=logprobs)
         share_trunk, drafts, drop, in_loop = m.share_trunk, m.drafts, not m.keep_arenas, m.loop_prefill
 
         def unpack(req):
-            if isinstance(req, (tuple, list)):
-                return req[0], (req[1] if req[1] is not None else params)
-            return req, params
+            """-> (prompt, params) of a request; its ``logprobs`` must fit what the loop was built for."""
+            prompt, p = (req[0], req[1] if req[1] is not None else params) if isinstance(req, (tuple, list)) else (req, params)
+            want = None if p is None else modes.check_logprobs(getattr(p, "logprobs", None), what="GenerationParameters.logprobs")
+            if want is not None and (m.logprobs is None or want > m.logprobs):
+                raise ValueError(f"serve: a request asks for logprobs={want}, and the loop "
+                                 + ("carries no log-probability node" if m.logprobs is None else f"ranks {m.logprobs} alternatives")
+                                 + f": call serve(logprobs=n) with n >= {want} (or set PC_SERVE_LOGPROBS)")
+            return prompt, p
 
         if not m.batched:
             full = bool(getattr(self.lm, "use_full_position_ids", False))
@@ -701,8 +763,9 @@ class GenerationEngine:
                         st.total_ms += ms
                         if not st.new_ids:                         # (loop_prefill: the first token, from the ring)
                             st.ttft_ms = st.total_ms = (time.perf_counter() - st.t_admit) * 1e3
-                        for token in toks:
-                            out = st.emit(token)
+                        lps = loop.logprobs(st.k, i) if st.lps is not None else None
+                        for t, token in enumerate(toks):
+                            out = st.emit(token, None if lps is None else lps[t])
                             if read_k:
                                 stats["tokens"] += 1
                             if out is not None:

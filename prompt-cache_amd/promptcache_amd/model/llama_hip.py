@@ -36,8 +36,8 @@ import numpy as np
 
 from .. import _native
 # the pure refusals of formats and loop modes live in modes.py (no torch); the names stay importable from here
-from ..modes import (SLOT_KV, WEIGHT_FORMATS, check_keep_fp16, check_loop_prefill, check_slot_keep_arenas,  # noqa: F401
-                     check_slot_kv, check_weight_format, parse_keep_arenas, parse_keep_fp16)
+from ..modes import (SLOT_KV, WEIGHT_FORMATS, check_keep_fp16, check_logprobs, check_loop_prefill,  # noqa: F401
+                     check_slot_keep_arenas, check_slot_kv, check_weight_format, parse_keep_arenas, parse_keep_fp16)
 from .config import LlamaShape
 from .kv_arena import KVArena, StagedKV, arena_from_past, common_trunks
 
@@ -124,6 +124,30 @@ class CausalLMOutput:
     past_key_values: Optional[StagedKV]
 
 
+def logprob_records(ids, lp) -> list:
+    """Host records of pc_token_logprobs' two output arrays (``[R][1 + n]``, on the host): per row ``(token, logprob, [(id,
+    logprob), ...])`` -- entry 0, then the n alternatives by (value descending, index ascending)."""
+    return [(int(i[0]), float(l[0]), [(int(a), float(b)) for a, b in zip(i[1:], l[1:])]) for i, l in zip(ids.tolist(), lp.tolist())]
+
+
+class _LogprobRing:
+    """The host side of a step's log-probability node (``logprobs=n``): the node leaves ``[rows][1 + n]`` ids and
+    log-probabilities in fixed device buffers of the loop state, and ``copy(r)`` -- called right behind the replay, where the token
+    ring is copied -- takes them into pinned ring row ``r``.  Stream order makes a device-side ring unnecessary."""
+
+    def __init__(self, dev: dict, ring: int):
+        self.dev = dev
+        self.ids = torch.zeros((ring,) + tuple(dev["ids"].shape), dtype=torch.int32, pin_memory=True)
+        self.lp = torch.zeros((ring,) + tuple(dev["lp"].shape), dtype=torch.float32, pin_memory=True)
+
+    def copy(self, r: int) -> None:
+        self.ids[r].copy_(self.dev["ids"], non_blocking=True)
+        self.lp[r].copy_(self.dev["lp"], non_blocking=True)
+
+    def records(self, r: int, row0: int, count: int) -> list:
+        return logprob_records(self.ids[r, row0:row0 + count], self.lp[r, row0:row0 + count])
+
+
 class GreedyLoop:
     """Greedy decode steps that never leave the GPU (reference loop: generation_engine.py:123-168, greedy branch).
 
@@ -131,13 +155,19 @@ class GreedyLoop:
     step's logits and writes it -- with position + 1 and past length + 1 -- into the device words the next replay reads
     its inputs from.  The host only enqueues replays (as far ahead as it likes) and picks tokens up from a small ring
     through pinned memory when it needs them for stop conditions; there is no ``int(argmax)`` sync, no H2D fill and no
-    logits copy per token.  ``enqueue()`` -> slot index; ``token(i)`` waits for slot i only."""
+    logits copy per token.  ``enqueue()`` -> slot index; ``token(i)`` waits for slot i only.
+    ``logprobs`` = n (None: off, and then nothing below exists): the step gains one node behind the advance,
+    ``pc_token_logprobs`` over the row the advance just read at the token it left in ``ids[0]``; ``logprobs(i)`` -> the one
+    record of ``token(i)``."""
 
     RING = 4096
 
     @torch.inference_mode()
-    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, ctr0: int = 0):
+    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, ctr0: int = 0,
+                 logprobs: Optional[int] = None):
         self.m = model
+        self.lp_n = check_logprobs(logprobs)
+        self._lp = None if self.lp_n is None else _LogprobRing(model._lp_state(("loop",), 1, self.lp_n), self.RING)
         past_len = arena.length
         need = past_len + max_new + 2
         if need > arena.cap:
@@ -183,6 +213,8 @@ class GreedyLoop:
         i = self.n
         r = (self.ctr0 + i) % self.RING
         self.host[r: r + 1].copy_(st["ring"][r: r + 1], non_blocking=True)
+        if self._lp is not None:
+            self._lp.copy(r)
         done = torch.cuda.Event()
         done.record()
         self.events.append((e0, e1, done))
@@ -194,6 +226,11 @@ class GreedyLoop:
     def token(self, i: int) -> int:
         self.events[i][2].synchronize()
         return int(self.host[(self.ctr0 + i) % self.RING])
+
+    def logprobs(self, i: int) -> list:
+        """One record per token of ``token(i)``: ``[(token, logprob, [(id, logprob)] * n)]`` (a loop built with ``logprobs=n``)."""
+        self.events[i][2].synchronize()
+        return self._lp.records((self.ctr0 + i) % self.RING, 0, 1)
 
     def close(self, consumed: int) -> None:
         """The generation ended after ``consumed`` of the enqueued steps were used: a look-ahead replay enqueued past the
@@ -211,7 +248,7 @@ class GreedyLoop:
         return e0.elapsed_time(e1)
 
     def _graph(self, arena: KVArena, past_len: int):
-        return self.m._loop_graph(arena, past_len)
+        return self.m._loop_graph(arena, past_len, logprobs=self.lp_n)
 
 
 def _history_bits(ids, vocab: int) -> torch.Tensor:
@@ -252,12 +289,12 @@ class SampleLoop(GreedyLoop):
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, params, seed: int,
-                 history_ids):
-        super().__init__(model, arena, token, position, max_new, ctr0=1)
+                 history_ids, logprobs: Optional[int] = None):
+        super().__init__(model, arena, token, position, max_new, ctr0=1, logprobs=logprobs)
         model._sample_state_fill(self.st, params, seed, history_ids)
 
     def _graph(self, arena: KVArena, past_len: int):
-        return self.m._loop_graph(arena, past_len, sample=True)
+        return self.m._loop_graph(arena, past_len, sample=True, logprobs=self.lp_n)
 
 
 class LookupLoop:
@@ -282,10 +319,14 @@ class LookupLoop:
     graph_tag = ()                   # appended to the step's graph key (a subclass with another last stage)
 
     @torch.inference_mode()
-    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3):
+    def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3,
+                 logprobs: Optional[int] = None):
         if not 1 <= k < self.ROWS_MAX:
             raise ValueError(f"LookupLoop: k = {k} outside 1..{self.ROWS_MAX - 1}")
         self.m, self.k, self.nmax = model, int(k), int(nmax)
+        # logprobs = n: one more stage behind the verify, over the k + 1 rows at the tokens it left in its int32 row scratch
+        self.lp_n = check_logprobs(logprobs)
+        self._lp = None if self.lp_n is None else _LogprobRing(model._lp_state(("lookup",), k + 1, self.lp_n), self.RING)
         arena.materialize()
         len0 = arena.length
         need = len0 + max_new + k + 2
@@ -321,7 +362,11 @@ class LookupLoop:
         out = m._forward_skinny(st["ids"][:k + 1], st["pos"][:k + 1], st["past"], self.arena, 1, k + 1, self.kv_ceiling - (k + 1),
                                 False, None)
         self._verify(out, V)
+        if self._lp is not None:
+            m._lp_node(self._lp.dev, out, k + 1, st[self.row_tokens], 1, self.lp_n)
         return out
+
+    row_tokens = "amax"              # the int32 scratch the verify stage leaves every row's token in
 
     def _verify(self, out, V: int) -> None:
         """The last stage of a step: which rows' tokens are emitted, and the state advance."""
@@ -348,6 +393,8 @@ class LookupLoop:
         i = self.n
         r = i % self.RING
         self.host[r].copy_(self.ring[r], non_blocking=True)
+        if self._lp is not None:
+            self._lp.copy(r)
         done = torch.cuda.Event()
         done.record()
         self.events.append((e0, e1, done))
@@ -362,6 +409,11 @@ class LookupLoop:
         rec = self.host[i % self.RING]
         c = int(rec[0])
         return [int(t) for t in rec[1:1 + c]]
+
+    def logprobs(self, i: int) -> list:
+        """One record per token of ``tokens(i)``, in its order: rows ``i < emit`` of the step (a loop built with ``logprobs=n``)."""
+        self.events[i][2].synchronize()
+        return self._lp.records(i % self.RING, 0, int(self.host[i % self.RING][0]))
 
     def close(self, consumed_tokens: int) -> None:
         """The generation used ``consumed_tokens`` of the tokens the enqueued steps produced: the arena's length becomes the
@@ -388,11 +440,12 @@ class SampleLookupLoop(LookupLoop):
     graph serves every parameter set; protocol, memory-safety argument and the stepped mode are ``LookupLoop``'s."""
 
     graph_tag = ("sample",)
+    row_tokens = "row_token"
 
     @torch.inference_mode()
     def __init__(self, model: "LlamaHIP", arena: KVArena, token: int, position: int, max_new: int, k: int, corpus_ids, params,
-                 seed: int, history_ids, nmax: int = 3):
-        super().__init__(model, arena, token, position, max_new, k, corpus_ids, nmax)
+                 seed: int, history_ids, nmax: int = 3, logprobs: Optional[int] = None):
+        super().__init__(model, arena, token, position, max_new, k, corpus_ids, nmax, logprobs)
         st = self.st
         model._lookup_sample_state(st)
         model._sample_state_fill(st, params, seed, history_ids)
@@ -483,7 +536,19 @@ class _SlotLoopHost:
     MAX_ROWS = 64                    # rows of one step, S * (k + 1): what the weight-streaming projections take
     k = 0                            # draft rows per slot
     kv = "fp16"                      # what the step's attention reads: the fp16 arenas, or int8 images of them (SlotLoop(kv="int8"))
+    lp_n = None                      # logprobs = n: the step ends in the log-probability node at top_n = n
+    _lp = None
+    prompt_rows = False
     ctr0 = 0                         # the device step counter at replay 0 (step i's record lands in ring row (ctr0 + i) % RING)
+
+    @classmethod
+    def with_logprobs(cls, logprobs: Optional[int], *args, **kw):
+        """``cls(*args, **kw)`` whose step ends in the log-probability node at ``top_n = logprobs`` (None: plain ``cls(...)``).  The
+        option is in place before ``__init__`` builds state and graph key, and the constructors keep their signatures."""
+        loop = cls.__new__(cls)
+        loop.lp_n = check_logprobs(logprobs, cls.prompt_rows)
+        loop.__init__(*args, **kw)
+        return loop
 
     def _build(self, model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each,
                max_keys, corpora=None, hist_cap=None) -> None:
@@ -520,6 +585,8 @@ class _SlotLoopHost:
             self.qcap, self.kvq = model._slot_kvq(st, S, self._image_rows(arenas, max_news, max_keys))
         model._live_loop = self
         self.logits = st["logits"]
+        if self.lp_n is not None:
+            self._lp = _LogprobRing(model._lp_state(self._lp_tag(), S * (k + 1), self.lp_n), self.RING)
         self.host = torch.zeros((self.RING, S) + self._record, dtype=torch.int32, pin_memory=True)
         self._ring = st["ring"].view((S, self.RING) + self._record)
         if each:
@@ -671,6 +738,8 @@ class _SlotLoopHost:
         if i >= self.RING:
             self._ring_row_reused(i - self.RING)         # (row r still holds step i - RING)
         self.host[r].copy_(self._ring[:, r], non_blocking=True)
+        if self._lp is not None:
+            self._lp.copy(r)
         done = torch.cuda.Event()
         done.record()
         self.events[i] = (e0, e1, done)
@@ -769,7 +838,11 @@ class SlotLoop(_SlotLoopHost):
         return self.m._slot_state(self.S)
 
     def _graph(self):
-        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap if self.kv == "int8" else 0)
+        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap if self.kv == "int8" else 0,
+                                  logprobs=self.lp_n)
+
+    def _lp_tag(self):
+        return ("slots", self.S)
 
     def _fill_state(self, col, tokens, positions, max_new, params, seeds, histories, stop_ids) -> None:
         """The state words of the loop over ``pc_sample_advance_slots``: one parameter block and one stop list for all slots."""
@@ -862,6 +935,13 @@ class SlotLoop(_SlotLoopHost):
             return None
         return int(self.host[(self.ctr0 + i) % self.RING][self.idx[k]])
 
+    def logprobs(self, k: int, i: int) -> list:
+        """One record per token of ``token(k, i)``: ``[(token, logprob, [(id, logprob)] * n)]``, empty where ``token`` gives None (a
+        loop built with ``logprobs=n``; the row of an idle slot is stale and never handed out)."""
+        if self.token(k, i) is None:
+            return []
+        return self._lp.records((self.ctr0 + i) % self.RING, self.idx[k], 1)
+
 
 class SlotLoopQ8(SlotLoop):
     """``SlotLoop`` whose attention reads int8 images of the slots' K / V rows (``LlamaHIP.slot_loop(kv="int8")``):
@@ -929,7 +1009,7 @@ class SlotLoopQ8Only(_ImageOnly, SlotLoopQ8):
     same ``max_keys`` a sequence's tokens are that loop's, bit for bit."""
 
     def _graph(self):
-        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap, fresh=True)
+        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap, fresh=True, logprobs=self.lp_n)
 
 
 class LookupSlotLoop(_SlotLoopHost):
@@ -1007,6 +1087,9 @@ class LookupSlotLoop(_SlotLoopHost):
     def _graph(self):
         self.m._lo_mode = 0                # appended rows carry no residual planes, as in default decode
         return self.m._lookup_slot_graph(self)
+
+    def _lp_tag(self):
+        return ("slots", "lookup", self.S, self.k)
 
     def _fill_state(self, col, tokens, positions, max_new, params, seeds, histories, stop_ids) -> None:
         """The state words of the loop over ``pc_lookup_verify_slots``: greedy, one stop list for all slots."""
@@ -1135,6 +1218,11 @@ class LookupSlotLoop(_SlotLoopHost):
         rec = self.host[i % self.RING][self.idx[j]]
         c = int(rec[0])
         return [int(t) for t in rec[1:1 + c]]
+
+    def logprobs(self, j: int, i: int) -> list:
+        """One record per token of ``tokens(j, i)``, in its order: rows ``i < emit`` of the slot's k + 1 rows (a loop built with
+        ``logprobs=n``)."""
+        return self._lp.records(i % self.RING, self.idx[j] * (self.k + 1), len(self.tokens(j, i)))
 
     def kill(self, j: int) -> None:
         """``SlotLoop.kill``; nothing once the slot holds a later sequence."""
@@ -2470,14 +2558,67 @@ class LlamaHIP:
         _native.sample_advance(logits_row, V, st["params"], st["hist"], st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
         return int(st["ids"][0])
 
-    def _loop_graph(self, arena: KVArena, past_len: int, sample: bool = False):
+    # ---- per-token log-probabilities (pc_token_logprobs) -----------------------------------------------------
+    def _lp_state(self, tag: tuple, rows: int, top_n: int) -> dict:
+        """The fixed output buffers of a step's log-probability node: ``ids`` int32 / ``lp`` fp32 ``[rows][1 + top_n]``, one pair
+        per (loop state ``tag``, rows, top_n) -- the captured steps hold their addresses, and the graph keys carry ``top_n``."""
+        sts = self.__dict__.setdefault("_lp_sts", {})
+        st = sts.get((tag, rows, top_n))
+        if st is None:
+            dev = self.device
+            if not sts:
+                # first launch of the kernel outside any capture (code-object load): stateless, on a scratch row of zeros
+                V = self.config.vocab_size
+                _native.token_logprobs(torch.zeros(V, dtype=torch.float32, device=dev), V, V, 1, torch.zeros(1, dtype=torch.int64, device=dev),
+                                       1, 0, torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+            st = sts[(tag, rows, top_n)] = dict(ids=torch.full((rows, 1 + top_n), -1, dtype=torch.int32, device=dev),
+                                                lp=torch.full((rows, 1 + top_n), float("nan"), dtype=torch.float32, device=dev))
+        return st
+
+    def _lp_node(self, lp: dict, logits, rows: int, tokens, stride: int, top_n: int) -> None:
+        """The node: the log-softmax of the RAW ``logits`` rows the sampler just read (it leaves them untouched: no step hands it a
+        ``processed_out``) at the tokens its last node left in ``tokens``, into the fixed buffers ``lp``."""
+        V = self.config.vocab_size
+        _native.token_logprobs(logits, V, V, rows, tokens, stride, top_n, lp["ids"], lp["lp"])
+
+    @torch.inference_mode()
+    def token_logprobs(self, logits_rows: torch.Tensor, tokens, top_n: int) -> list:
+        """One eager launch of pc_token_logprobs on rows the caller already has (``[vocab]`` or ``[R][vocab]`` logits, ``tokens``: one
+        id per row) -> host records ``[(token, logprob, [(id, logprob)] * top_n)]``.  The log-probabilities are the model's own: the
+        log-softmax of the raw logits, before temperature, repetition penalty, top-p and top-k.  The first token of a generation
+        (the prefill's last row) and the stepped paths come through here."""
+        top_n = check_logprobs(int(top_n))
+        V = self.config.vocab_size
+        x = logits_rows.reshape(-1, logits_rows.shape[-1])
+        if x.shape[1] != V:
+            raise ValueError(f"token_logprobs: rows of {x.shape[1]} logits, vocab_size = {V}")
+        if not x.is_cuda or x.dtype != torch.float32 or x.stride(1) != 1:
+            x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        toks = torch.as_tensor([int(t) for t in tokens], dtype=torch.int64).to(x.device)
+        if toks.numel() != x.shape[0]:
+            raise ValueError(f"token_logprobs: {toks.numel()} tokens for {x.shape[0]} rows")
+        out = []
+        for r0 in range(0, x.shape[0], 64):
+            r = min(64, x.shape[0] - r0)
+            ids = torch.empty((r, 1 + top_n), dtype=torch.int32, device=x.device)
+            lp = torch.empty((r, 1 + top_n), dtype=torch.float32, device=x.device)
+            _native.token_logprobs(x[r0:], x.stride(0), V, r, toks[r0:], 1, top_n, ids, lp)
+            out += logprob_records(ids.cpu(), lp.cpu())
+        return out
+
+    def _loop_graph(self, arena: KVArena, past_len: int, sample: bool = False, logprobs: Optional[int] = None):
         """The captured graph of ONE greedy (``sample``: sampled) decode step over ``arena`` (forward of the token in the loop
-        state + argmax / draw + state advance), keyed like ``_graphed_skinny``."""
+        state + argmax / draw + state advance), keyed like ``_graphed_skinny``.  ``logprobs`` = n: one more node behind the advance
+        (the key gains ``("logprobs", n)``; None: today's key and launches)."""
         n = _native
         nsplit_key = n.attn_workspace_bytes(1, self.H, self.D, 1, past_len + 1)
         mode = self._lo_mode
         key = ("loop",) + (("sample",) if sample else ()) + (arena.buf.data_ptr(), arena.cap, nsplit_key, self.fuse_norm, self.use_chain, mode,
                arena.tail_lo.data_ptr() if mode else 0, arena.tail_lo.shape[4] if mode else 0)
+        lp = None
+        if logprobs is not None:
+            key += ("logprobs", logprobs)
+            lp = self._lp_state(("loop",), 1, logprobs)
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2501,6 +2642,8 @@ class LlamaHIP:
                 n.sample_advance(out, V, st["params"], st["hist"], st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
             else:
                 n.greedy_advance(out, V, st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
+            if lp is not None:
+                self._lp_node(lp, out, 1, st["ids"], 1, logprobs)
         ent = (g, out)
         self._graphs[key] = ent
         return ent
@@ -2519,18 +2662,20 @@ class LlamaHIP:
         """Whether ``greedy_loop`` / ``sample_loop`` over ``past`` would give a loop (not None)."""
         return self._loop_arena(past) is not None
 
-    def greedy_loop(self, past, token: int, position: int, max_new: int) -> Optional["GreedyLoop"]:
+    def greedy_loop(self, past, token: int, position: int, max_new: int, logprobs: Optional[int] = None) -> Optional["GreedyLoop"]:
         """A device-side greedy decode loop over the arena behind ``past`` (None when this model / cache cannot host one:
-        the caller then steps through ``__call__``)."""
+        the caller then steps through ``__call__``).  ``logprobs`` = n in 0..8: every step also leaves the log-probability of its
+        token and of the n most likely ones under the raw logits (``GreedyLoop.logprobs``); all device loops take it."""
         arena = self._loop_arena(past)
-        return None if arena is None else GreedyLoop(self, arena, token, position, max_new)
+        return None if arena is None else GreedyLoop(self, arena, token, position, max_new, logprobs=logprobs)
 
-    def sample_loop(self, past, token: int, position: int, max_new: int, params, seed: int, history_ids) -> Optional["SampleLoop"]:
+    def sample_loop(self, past, token: int, position: int, max_new: int, params, seed: int, history_ids,
+                    logprobs: Optional[int] = None) -> Optional["SampleLoop"]:
         """A device-side sampled decode loop (``params``: temperature, repetition_penalty, top_p, top_k as in
         GenerationParameters; ``history_ids``: the ids the repetition penalty sees, ``token`` included) over the arena
         behind ``past``, continuing the random stream of ``seed`` at step 1.  None where ``greedy_loop`` gives None."""
         arena = self._loop_arena(past)
-        return None if arena is None else SampleLoop(self, arena, token, position, max_new, params, seed, history_ids)
+        return None if arena is None else SampleLoop(self, arena, token, position, max_new, params, seed, history_ids, logprobs)
 
     # ---- prompt-lookup speculative decoding (LookupLoop) ----------------------------------------------------------------
     def lookup_available(self) -> bool:
@@ -2593,6 +2738,8 @@ class LlamaHIP:
         arena, st, k = loop.arena, loop.st, loop.k
         key = ("loop", "lookup", k, arena.buf.data_ptr(), arena.cap, self._nsplit_key(1, k + 1, loop.kv_ceiling), loop.kv_ceiling,
                loop.nmax, st["hist"].data_ptr(), st["hist"].numel(), self.fuse_norm) + loop.graph_tag
+        if loop.lp_n is not None:
+            key += ("logprobs", loop.lp_n)
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2612,7 +2759,7 @@ class LlamaHIP:
         return ent
 
     def lookup_loop(self, past, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3, params=None,
-                    seed: int = 0, history_ids=None):
+                    seed: int = 0, history_ids=None, logprobs: Optional[int] = None):
         """A device-side greedy decode loop with prompt-lookup drafts (``LookupLoop``: up to ``k + 1`` tokens per step, ``k`` in
         1..15) over the arena behind ``past``.  ``corpus_ids``: the ids the drafts may copy from besides the output itself --
         the context in key order; the history starts as ``corpus_ids ++ [token]``.  ``max_new``: the most tokens the loop
@@ -2623,14 +2770,14 @@ class LlamaHIP:
         if params is not None:
             history_ids = [int(token)] if history_ids is None else history_ids
             if not self.lookup_available():
-                return self.sample_loop(past, token, position, max_new, params, seed, history_ids)
+                return self.sample_loop(past, token, position, max_new, params, seed, history_ids, logprobs)
             arena = self._loop_arena(past)
             return None if arena is None else SampleLookupLoop(self, arena, token, position, max_new, k, corpus_ids, params, seed,
-                                                               history_ids, nmax)
+                                                               history_ids, nmax, logprobs)
         if not self.lookup_available():
-            return self.greedy_loop(past, token, position, max_new)
+            return self.greedy_loop(past, token, position, max_new, logprobs)
         arena = self._loop_arena(past)
-        return None if arena is None else LookupLoop(self, arena, token, position, max_new, k, corpus_ids, nmax)
+        return None if arena is None else LookupLoop(self, arena, token, position, max_new, k, corpus_ids, nmax, logprobs)
 
     # ---- batched decode over slots (SlotLoop) ---------------------------------------------------------------------------
     supports_slot_loop = True       # (a subclass with layer loops of its own says no)
@@ -2645,7 +2792,7 @@ class LlamaHIP:
     def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
                   slots: Optional[int] = None, slot_index=None, share_trunk: bool = False,
                   min_trunk: Optional[int] = None, each: bool = False, max_keys: Optional[int] = None,
-                  trunks=None, kv: str = "fp16", keep_arenas: bool = True) -> Optional["SlotLoop"]:
+                  trunks=None, kv: str = "fp16", keep_arenas: bool = True, logprobs: Optional[int] = None) -> Optional["SlotLoop"]:
         """A batched device-side decode loop over the arenas behind ``pasts`` (one ``past_key_values`` per sequence, each a
         batch-1 arena of its own): sequence k feeds ``tokens[k]`` at position ``positions[k]`` next.  ``params`` None or plain
         greedy: argmax; otherwise the sampled chain with ``seeds[k]`` (the stream continues at step 1) and ``histories[k]``.
@@ -2666,7 +2813,11 @@ class LlamaHIP:
         sizes the images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError.
         ``keep_arenas=False`` (with ``kv="int8"`` only): the loop keeps the images and one fresh-row buffer per slot
         and NO reference to the arenas behind ``pasts`` -- their rows are quantised into the images on entry and the arenas are
-        free afterwards (``SlotLoopQ8Only``); with ``each=True`` one arena can prefill every sequence in turn."""
+        free afterwards (``SlotLoopQ8Only``); with ``each=True`` one arena can prefill every sequence in turn.
+        ``logprobs`` = n in 0..8: the step gains one node behind the advance launch, ``pc_token_logprobs`` over the S
+        logits rows at the tokens in ``ids[b]``; ``SlotLoop.logprobs(k, i)`` hands out the record of ``token(k, i)``.  None: today's
+        graph keys, state and launches."""
+        check_logprobs(logprobs)
         check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, head_dim=self.D,
                       no_loop=None if self.slot_loop_available() else "the model has no batched decode loop")
         check_slot_keep_arenas(keep_arenas, kv)
@@ -2675,7 +2826,8 @@ class LlamaHIP:
             return None
         arenas, trunks = front
         cls = (SlotLoopQ8 if keep_arenas else SlotLoopQ8Only) if kv == "int8" else SlotLoop
-        return cls(self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each, max_keys)
+        return cls.with_logprobs(logprobs, self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index,
+                                 trunks, each, max_keys)
 
     def _slot_loop_front(self, pasts, stop_ids, each: bool, share_trunk: bool, min_trunk, trunks):
         """What ``slot_loop`` and ``lookup_slot_loop`` do before they build their loop -> (arenas, trunks), or None where there is
@@ -2750,7 +2902,8 @@ class LlamaHIP:
             st["fresh"] = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in range(S)]
         return st["fresh"]
 
-    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0, fresh: bool = False):
+    def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0, fresh: bool = False,
+                    logprobs: Optional[int] = None):
         """The captured S-slot decode step.  Everything that changes from step to step or from batch to batch -- arena
         addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch.
         ``nsplit_trunk`` > 0: the step with shared trunks; which slots share what is device data as well (leader / trunk).
@@ -2765,6 +2918,9 @@ class LlamaHIP:
         if fresh:
             key += ("fresh",)
         more = {"fresh": True} if fresh else {}
+        if logprobs is not None:          # one more node behind the advance launch: the key gains its top_n
+            key += ("logprobs", logprobs)
+            more["lp"] = (self._lp_state(("slots", S), S, logprobs), logprobs)
         g = self._graphs.pop(key, None)
         if g is not None:
             self._graphs[key] = g
@@ -2787,7 +2943,7 @@ class LlamaHIP:
         return g
 
     def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0,
-                       fresh: bool = False) -> None:
+                       fresh: bool = False, lp=None) -> None:
         """One decode step over S slots: the <= 16-row projections of ``_layers_norm_fused`` around per-slot RoPE + append
         and attention; logits to ``st["logits"]``, then the advance launch.  ``qcap`` > 0: the attention reads the slots' int8
         images (``pc_attn_decode_slots_q8``) and stages the appended row into them; the arenas are appended to as always.
@@ -2859,13 +3015,16 @@ class LlamaHIP:
         else:
             n.sample_advance_slots(st["logits"], V, V, st["params"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
                                    st["cap"], st["live"], st["budget"], st["stop"], st["ring"], st["ctr"], SlotLoop.RING, S)
+        if lp is not None:            # (buffers, top_n): the log-probabilities of the tokens the advance left in ids[b]
+            self._lp_node(lp[0], st["logits"], S, st["ids"], 1, lp[1])
 
     # ---- prompt-lookup drafts in the slot loop (LookupSlotLoop) ----------------------------------------------------------
     def lookup_slot_loop(self, pasts, tokens, positions, max_new: int, k: int, corpora, nmax: int = 3, stop_ids=(),
                          slots: Optional[int] = None, max_keys: Optional[int] = None, share_trunk: bool = False,
                          min_trunk: Optional[int] = None, trunks=None, each: bool = False, slot_index=None, params=None, seeds=None,
                          histories=None, hist_cap: Optional[int] = None, kv: str = "fp16",
-                         keep_arenas: bool = True, prompt_rows: bool = False) -> Optional["LookupSlotLoop"]:
+                         keep_arenas: bool = True, prompt_rows: bool = False,
+                         logprobs: Optional[int] = None) -> Optional["LookupSlotLoop"]:
         """``slot_loop`` with prompt-lookup drafts: up to ``k + 1`` greedy tokens per sequence and step (``LookupSlotLoop``).
         ``corpora[j]``: the ids sequence j's drafts may copy from besides its own output (``lookup_loop``'s ``corpus_ids``).  None
         where ``slot_loop`` gives None, where the model has no lookup step (``lookup_available``) and where ``S * (k + 1)``
@@ -2881,9 +3040,13 @@ class LlamaHIP:
         (``LookupSlotLoopQ8``), without fp16 slot arenas where asked (``LookupSlotLoopQ8Only``); ``max_keys`` then also sizes the
         images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError.
         ``prompt_rows`` (with ``each``, fp16 arenas): the step takes forced rows and ``LookupSlotLoop.admit_prompt``
-        prefills an admitted request's question inside it.  False: today's loop, graph key and launches."""
+        prefills an admitted request's question inside it.  False: today's loop, graph key and launches.
+        ``logprobs`` = n in 0..8: the step gains one node behind the verify launches, ``pc_token_logprobs`` over the
+        ``S * (k + 1)`` rows at the tokens the verify left in its int32 row scratch; ``LookupSlotLoop.logprobs(j, i)`` hands out the
+        records of ``tokens(j, i)``.  Not with ``prompt_rows`` (ValueError).  None: today's graph keys, state and launches."""
         if prompt_rows and (not each or kv != "fp16"):
             raise ValueError("lookup_slot_loop: prompt_rows=True needs each=True and kv='fp16'")
+        check_logprobs(logprobs, prompt_rows)
         if kv != "fp16" or not keep_arenas:       # (with the mode off nothing is asked of the model here)
             check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, lookup=k, head_dim=getattr(self, "D", None),
                           no_loop=None if self.slot_loop_available() else "the model has no batched decode loop",
@@ -2902,9 +3065,9 @@ class LlamaHIP:
         cls = ((LookupSlotLoopQ8 if keep_arenas else LookupSlotLoopQ8Only) if kv == "int8" else
                LookupSlotLoopPrompt if prompt_rows else LookupSlotLoop)
         if each:
-            return cls(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
-                       slot_index, params, seeds, histories, hist_cap)
-        return cls(self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks)
+            return cls.with_logprobs(logprobs, self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
+                                     slot_index, params, seeds, histories, hist_cap)
+        return cls.with_logprobs(logprobs, self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks)
 
     def lookup_slot_q8_available(self) -> bool:
         """Whether ``lookup_slot_loop(kv="int8")`` can run: the lookup step, the slot step and head_dim 128
@@ -2967,6 +3130,9 @@ class LlamaHIP:
             if getattr(loop, "fresh", None) is not None:
                 key += ("fresh",)
                 more["fresh"] = True
+        if loop.lp_n is not None:         # one more node behind the verify launches: the key gains its top_n
+            key += ("logprobs", loop.lp_n)
+            more["lp"] = (loop._lp.dev, loop.lp_n)
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2989,7 +3155,7 @@ class LlamaHIP:
         return g
 
     def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3, nsplit_trunk: int = 0,
-                              each: bool = False, qcap: int = 0, fresh: bool = False, prompt: bool = False) -> None:
+                              each: bool = False, qcap: int = 0, fresh: bool = False, prompt: bool = False, lp=None) -> None:
         """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
         k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
         projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop (on the 4-bit
@@ -3097,14 +3263,15 @@ class LlamaHIP:
                                          st["row_token"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"], st["cap"],
                                          st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], st["forced"],
                                          LookupSlotLoop.RING)
-            return
-        if each:                      # the sampler on every row, per slot
+        elif each:                    # the sampler on every row, per slot
             n.lookup_verify_slots_each(st["logits"], V, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
                                        st["row_token"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"], st["cap"],
                                        st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
-            return
-        n.lookup_verify_slots(st["logits"], V, V, S, k, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"],
-                              st["cap"], st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
+        else:
+            n.lookup_verify_slots(st["logits"], V, V, S, k, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"],
+                                  st["cap"], st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
+        if lp is not None:            # (buffers, top_n): the log-probabilities of the row tokens the verify left in its int32 scratch
+            self._lp_node(lp[0], st["logits"], R, st["row_token" if each else "amax"], 1, lp[1])
 
     def _ks_buffers(self, hid: int):
         """Scratch slabs + arrival counters of pc_gemm_skinny_ks (shared by every such launch of the model: they run one

@@ -123,6 +123,34 @@ def check_slot_keep_arenas(keep_arenas: bool, kv: str, generate_batch: bool = Fa
                          f"slot has); slot_kv = {kv!r}")
 
 
+LOGPROBS_MAX_TOP = 8         # PC_LOGPROBS_MAX_TOP: the most alternatives pc_token_logprobs ranks per token
+
+
+def check_logprobs(logprobs, loop_prefill: bool = False, what: str = "logprobs") -> Optional[int]:
+    """The ``logprobs`` a call runs with: None (off), or n in 0..8 -- the chosen token's log-probability plus the n most likely
+    alternatives, under the model's own distribution.  ``ValueError`` for anything else and for ``loop_prefill=True`` together with
+    it -- raised before anything runs.  Pure."""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"{what} must be None or an integer in 0..{LOGPROBS_MAX_TOP} (the alternatives per token), not {logprobs!r}")
+    if loop_prefill:
+        raise ValueError("loop_prefill=True and logprobs exclude each other: the first token of a request admitted that way is drawn "
+                         "inside the step from a forced row, whose record the step's log-probability node does not hand out "
+                         "(loop_prefill with logprobs is not implemented)")
+    return int(logprobs)
+
+
+def parse_logprobs(value) -> Optional[int]:
+    """``PC_SERVE_LOGPROBS``: unset or empty is off, else the n of ``serve(logprobs=n)``."""
+    if value is None or value == "":
+        return None
+    try:
+        return int(value)
+    except ValueError:
+        raise ValueError(f"PC_SERVE_LOGPROBS must be an integer in 0..{LOGPROBS_MAX_TOP}, not {value!r}") from None
+
+
 def parse_keep_arenas(value) -> bool:
     """``PC_SLOT_KEEP_ARENAS``: unset, empty or ``1`` keeps the fp16 slot arenas under ``slot_kv="int8"``, ``0`` drops them."""
     return _parse_01("PC_SLOT_KEEP_ARENAS", value)
@@ -160,6 +188,7 @@ class Modes:
     slot_kv: str = "fp16"
     keep_arenas: bool = True
     loop_prefill: bool = False
+    logprobs: Optional[int] = None     # serve: the step carries the log-probability node at top_n = logprobs (None: it does not)
 
     def reason(self) -> str:
         """The plan's text: ``base`` and one clause per mode that is on."""
@@ -170,6 +199,8 @@ class Modes:
             why += ", K/V read from int8 images (slot_kv='int8')"
             if not self.keep_arenas:
                 why += ", no fp16 slot arenas: every prefill runs in one shared arena (keep_arenas=False)"
+        if self.batched and self.logprobs is not None:
+            why += f", per-token log-probabilities with up to {self.logprobs} alternatives (logprobs={self.logprobs})"
         return why
 
     def loop_kwargs(self, one_token: bool = False) -> dict:
@@ -182,6 +213,8 @@ class Modes:
             kw["keep_arenas"] = False
         if self.loop_prefill and not one_token:
             kw["prompt_rows"] = True
+        if self.logprobs is not None:
+            kw["logprobs"] = self.logprobs
         return kw
 
 
@@ -200,10 +233,11 @@ def _serve_drafts(caps: Capabilities, lookup: int, slots: Optional[int]):
 
 def resolve_serve(caps: Capabilities, slots: Optional[int] = None, share_trunk: Optional[bool] = None, lookup: Optional[int] = None,
                   slot_kv: Optional[str] = None, keep_arenas: Optional[bool] = None, loop_prefill: Optional[bool] = None,
-                  env: Optional[Mapping[str, str]] = None, validate: bool = True) -> Modes:
+                  env: Optional[Mapping[str, str]] = None, validate: bool = True, logprobs: Optional[int] = None) -> Modes:
     """``serve``'s modes over ``slots`` slots (None: not known, no row limit applies).  An argument that is None reads the
     environment: ``PC_SLOT_TRUNK`` (default 0), ``PC_SERVE_LOOKUP`` (0), ``PC_SLOT_KV`` ("fp16"), ``PC_SLOT_KEEP_ARENAS`` (1),
-    ``PC_SERVE_LOOP_PREFILL`` (0).  Refusals, in this order: ``check_slot_kv``, ``check_slot_keep_arenas``, ``check_loop_prefill``.
+    ``PC_SERVE_LOOP_PREFILL`` (0), ``PC_SERVE_LOGPROBS`` (unset: off).  Refusals, in this order: ``check_slot_kv``,
+    ``check_slot_keep_arenas``, ``check_loop_prefill``, ``check_logprobs``.
     ``validate=False`` is ``serve_plan``'s reading: ``slot_kv`` is taken as it comes and ``keep_arenas`` None means "not named"
     -- neither is checked and ``PC_SLOT_KEEP_ARENAS`` is not read -- while ``loop_prefill=True`` is refused as in ``serve``."""
     env = os.environ if env is None else env
@@ -223,6 +257,9 @@ def resolve_serve(caps: Capabilities, slots: Optional[int] = None, share_trunk: 
     if loop_prefill is None:
         loop_prefill = env.get("PC_SERVE_LOOP_PREFILL", "0") == "1"
     check_loop_prefill(bool(loop_prefill), drafts, kv, no_drafts)
+    if logprobs is None:
+        logprobs = parse_logprobs(env.get("PC_SERVE_LOGPROBS"))
+    logprobs = check_logprobs(logprobs, bool(loop_prefill), "serve(logprobs=...) / PC_SERVE_LOGPROBS")
     if not batched:
         base = caps.not_batched
     elif drafts:
@@ -232,7 +269,7 @@ def resolve_serve(caps: Capabilities, slots: Optional[int] = None, share_trunk: 
         base = "one device loop, one token per replay: " + no_drafts
     else:
         base = "one device loop, new prompts admitted as slots free up"
-    return Modes(batched, base, bool(share_trunk), lookup, drafts, no_drafts, kv, bool(keep_arenas), bool(loop_prefill))
+    return Modes(batched, base, bool(share_trunk), lookup, drafts, no_drafts, kv, bool(keep_arenas), bool(loop_prefill), logprobs)
 
 
 def resolve_batch(caps: Capabilities, n_requests: int, plain_greedy: bool = True, n_stop_ids: int = 0, max_new_tokens: int = 2,
