@@ -40,11 +40,13 @@ def main():
                     help="also decode N copies of the prompt with different questions together (generate_batch; N <= 16)")
     ap.add_argument("--share-trunk", action="store_true",
                     help="with --batch: read the module rows the N prompts have in common once per step for all of them "
-                         "(with --lookup K as well: once for all K + 1 draft rows of all of them)")
+                         "(with --lookup K as well: once for all K + 1 draft rows of all of them); with --serve N --slot-kv int8: "
+                         "the serving loop reads a group's shared rows once per step from the leader's int8 image "
+                         "(serve(slot_kv='int8', share_trunk=True)); not with --lookup or --slot-drop-fp16 there")
     ap.add_argument("--slot-kv", choices=("fp16", "int8"), default=None,
                     help="with --batch / --serve: what the batched loop's attention reads (default: PC_SLOT_KV, else fp16); int8 = "
                          "int8 images of the slots' K/V rows, about half the bytes per step, the format's accuracy, and 0.516 of a "
-                         "slot buffer MORE memory per slot (the fp16 buffers stay); not with --share-trunk; with --lookup K under "
+                         "slot buffer MORE memory per slot (the fp16 buffers stay); with --share-trunk under --serve only; with --lookup K under "
                          "--serve only (serve(lookup=K, slot_kv='int8'): the K + 1 row step reads the images), not under --batch alone")
     ap.add_argument("--slot-drop-fp16", action="store_true",
                     help="with --serve and --slot-kv int8: no slot keeps an fp16 buffer (keep_arenas=False; default: "
@@ -128,11 +130,13 @@ def main():
         batched, why = gen_engine.batch_plan(len(reqs), params, slot_kv=a.slot_kv)
         # (int8 images under lookup are serve's: generate_batch refuses the pair, so this batch decodes one token per step)
         lookup_b = 0 if a.slot_kv == "int8" and a.lookup else a.lookup
+        # (likewise shared trunks over int8 images, DESIGN 3.33: serve's; this batch reads every slot's own image)
+        share_b = a.share_trunk and a.slot_kv != "int8"
         for _pass in ("warm", "timed"):              # (the first pass captures the batched step)
             lasts = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2, share_trunk=a.share_trunk,
+            for k, out in gen_engine.generate_batch(reqs, params, stream_interval=2, share_trunk=share_b,
                                                      lookup=lookup_b, slot_kv=a.slot_kv):
                 lasts[k] = out
             torch.cuda.synchronize()

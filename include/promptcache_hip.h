@@ -854,6 +854,26 @@ int pc_attn_decode_slots_trunk(const void* q_hi, const void* q_lo, int64_t q_tok
                                const int32_t* trunk, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D, float softmax_scale,
                                int32_t nsplit_own, int32_t nsplit_trunk, void* workspace, int64_t workspace_bytes, void* out_frag_hi,
                                void* out_frag_lo, void* stream);
+/* pc_attn_decode_slots_trunk_q8: pc_attn_decode_slots_q8 for slots that hold the same rows in front, with the leader / trunk words
+ * of pc_attn_decode_slots_trunk.  Slot b has T shared rows when its leader g = leader[b] lies in [0, S), leader[g] == g,
+ * trunk[b] == trunk[g] == T > 0, T <= len[b], T <= qcap and kvq_base[g] != 0; otherwise it has none and is on its own (the plain
+ * attention over its own complete image).  For a live slot with T shared rows, keys [0, T) are rows of the LEADER's image -- read
+ * once for all live members of the group, whether or not the leader is live --, keys [T, len[b]) rows of the slot's own image
+ * (its own rows [0, T) are never read) and key len[b] the fp16 arena row just appended, exact, which the launch also quantises
+ * into row len[b] of the slot's OWN image, as pc_attn_decode_slots_q8 does.  No image row below len[b] is written by anyone.
+ * Three launches that ask one predicate: the trunk (MFMA tiles of 16 (member, query head) columns over the codes, key slices a
+ * function of (T, nsplit_trunk), records 0 .. nsplit_trunk - 1), the own rows (the key axis [T, len] cut into nsplit_own chunks
+ * of ceil((len + 1 - T) / nsplit_own), records nsplit_trunk ..) and the merge in record order.  A member's bits depend on its
+ * own q, its keys, T and the two split counts only -- not on the size of its group, its column in the tile or its slot index.
+ * With leader = -1 everywhere the planes and the staged rows are bit-identical to pc_attn_decode_slots_q8 at nsplit = nsplit_own.
+ * Workspace: pc_attn_decode_slots_trunk_workspace_bytes, 16-byte aligned.  head_dim 128 only.  PC_ERR_ARG with nothing launched:
+ * what pc_attn_decode_slots_q8 or pc_attn_decode_slots_trunk refuses. */
+int pc_attn_decode_slots_trunk_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                                  const int32_t* cap, const int32_t* len, const int32_t* live, const int32_t* leader,
+                                  const int32_t* trunk, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                                  float softmax_scale, int32_t nsplit_own, int32_t nsplit_trunk, void* workspace,
+                                  int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base,
+                                  int32_t qcap, int32_t n_layers, void* stream);
 int pc_sample_advance_slots(const float* logits, int64_t logits_row_stride, int32_t vocab, const pc_sample_params* params_dev,
                             const uint64_t* seeds, uint32_t* history_bits, int64_t* ids, int32_t* pos, int32_t* len,
                             const int32_t* cap, int32_t* live, int32_t* budget, const int32_t* stop_ids, int32_t* ring,

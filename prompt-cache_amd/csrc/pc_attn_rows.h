@@ -23,6 +23,7 @@ struct SlotAttnArgs {
     const uint64_t* kv_base; const int32_t *cap, *len, *live, *leader, *trunk;
     int S, k, layer, H, Hkv; float scale_log2; int ns_own, ns_trunk; float *part_o, *part_ml; _Float16 *of_hi, *of_lo;
     int ns_extra;                    // records behind the own ones that the entry's own kernel writes (pc_attn_verify_slots_q8: 1)
+    const uint64_t* kvq_base; int qcap;   // pc_attn_decode_slots_trunk_q8: the images, whose predicate (slot_trunk_rows_q8) the merge asks
 };
 
 // The argument checks of the four entries, messages prefixed with the entry's `name`, and the split of the workspace into
@@ -422,20 +423,26 @@ __device__ __forceinline__ void attn_rows_tiles_q8(const _Float16* __restrict__ 
 // Merge of the records of a (row, head) in index (= key) order, one workgroup per (head, row), one thread per head dim; k + 1
 // rows per slot, nrec records per (row, head).  leader != nullptr (the entries with shared trunks; uniform over the launch): the
 // first nsplit_t records are the trunk launch's, and a row of a slot on its own (slot_trunk_rows 0) has none: its merge starts at
-// record nsplit_t.  den > 0: every row sees its own key.
+// record nsplit_t.  kvq_base != nullptr (pc_attn_decode_slots_trunk_q8): the shared rows are slot_trunk_rows_q8's, the question the
+// launches of that entry ask.  den > 0: every row sees its own key.
 template <int D>
 __global__ __launch_bounds__(D) void attn_merge_slots_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                                              const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
                                                              const int32_t* __restrict__ live, const int32_t* __restrict__ leader,
                                                              const int32_t* __restrict__ trunk,
                                                              const uint64_t* __restrict__ kv_base, int S, int k, int H, int nsplit_t,
-                                                             int nrec, _Float16* __restrict__ of_hi, _Float16* __restrict__ of_lo) {
+                                                             int nrec, _Float16* __restrict__ of_hi, _Float16* __restrict__ of_lo,
+                                                             const uint64_t* __restrict__ kvq_base, int qcap) {
     const int h = blockIdx.x, r = blockIdx.y, d = threadIdx.x;
     const int b = r / (k + 1);
     if (!lookup_slot_runs(cap, len, live, b, k)) return;
     const int64_t base = ((int64_t)r * H + h) * nrec;
     int s0 = 0;
-    if (leader != nullptr) s0 = slot_trunk_rows(b, S, kv_base, cap, len, leader, trunk) > 0 ? 0 : nsplit_t;
+    if (leader != nullptr) {
+        const int T = kvq_base != nullptr ? slot_trunk_rows_q8(b, S, kvq_base, qcap, len, leader, trunk)
+                                          : slot_trunk_rows(b, S, kv_base, cap, len, leader, trunk);
+        s0 = T > 0 ? 0 : nsplit_t;
+    }
     float ms = pca::kNegBig;
     for (int s = s0; s < nrec; ++s) ms = fmaxf(ms, part_ml[(base + s) * 2]);
     float num = 0.0f, den = 0.0f;

@@ -27,6 +27,19 @@ __device__ __forceinline__ int slot_trunk_rows(int b, int S, const uint64_t* __r
     return (leader[g] == g && T > 0 && T <= cap[g] && kv_base[g] != 0 && trunk[b] == T && T <= len[b]) ? T : 0;
 }
 
+// Shared rows of slot b over int8 IMAGES (pc_attn_decode_slots_trunk_q8): slot_trunk_rows with the leader's image in the place of
+// its arena -- the trunk fits the images' qcap rows per plane and the leader has an image; neither the leader's arena nor its cap
+// word is looked at, since no trunk key is read from an arena.  The trunk launch, the own launch and the merge of that entry all
+// ask here and nowhere else.
+__device__ __forceinline__ int slot_trunk_rows_q8(int b, int S, const uint64_t* __restrict__ kvq_base, int qcap,
+                                                  const int32_t* __restrict__ len, const int32_t* __restrict__ leader,
+                                                  const int32_t* __restrict__ trunk) {
+    const int g = leader[b];
+    if (g < 0 || g >= S) return 0;
+    const int T = trunk[g];
+    return (leader[g] == g && T > 0 && T <= qcap && kvq_base[g] != 0 && trunk[b] == T && T <= len[b]) ? T : 0;
+}
+
 // The accept rule of a prompt-lookup step (pc_lookup_verify, pc_lookup_verify_sample), by one wave.  Lane i holds a = the
 // model's token for row i; the accepted count is the first draft row the model disagrees with (rows at / behind ndraft are
 // pads: never accepted, whatever they hold).  Everything is read before anything is written; the ring record goes first.

@@ -86,17 +86,17 @@ __global__ __launch_bounds__(kThreads) void rope_append_slots_rows_kernel(
 // grid (split, kv head x pass, slot).  A tile column is (draft row i, query head g of the kv head): column index i * G + g inside
 // the slot's (k + 1) * G columns, RT tiles of 16 per pass.  The keys of the slot are [0, n), n = len + k + 1; column (i, .) sees
 // keys below len + i + 1 only -- the mask of the draft rows -- and a column that sees no key of a slice keeps (m = -1e30, l = 0).
-// TRUNK (pc_attn_verify_slots_trunk): a slot with shared rows (slot_trunk_rows) takes keys [t0, n) only -- the keys in front of
-// them are the trunk launch's --, its wave slices are cut from n - t0 and its partials are records rec0 .. rec0 + nsplit - 1 of
-// the nrec records per (row, head).  The mask of the draft rows is unchanged; with t0 = 0 the arithmetic is the plain
-// instantiation's.
-template <int D, int RT, bool TRUNK = false>
+// leader != nullptr (pc_attn_verify_slots_trunk; uniform over the launch -- an argument, not a template flag: the library's
+// instantiation budget, tests/test_kernel_resources.py, is spent on the kernels of pc_attn_decode_slots_trunk_q8): a slot with
+// shared rows (slot_trunk_rows) takes keys [t0, n) only -- the keys in front of them are the trunk launch's --, its wave slices
+// are cut from n - t0 and its partials are records rec0 .. rec0 + nsplit - 1 of the nrec records per (row, head).  The mask of
+// the draft rows is unchanged; with t0 = 0 the arithmetic is the plain launch's (nrec = nsplit, rec0 = 0, null words).
+template <int D, int RT>
 __global__ __launch_bounds__(kThreads, RT > 1 ? 1 : 2) void attn_verify_slots_kernel(
     const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo, int64_t q_ts, const uint64_t* __restrict__ kv_base,
     const int32_t* __restrict__ cap, const int32_t* __restrict__ len, const int32_t* __restrict__ live, int k, int layer, int H,
     int Hkv, float scale_log2, int nsplit, float* __restrict__ part_o, float* __restrict__ part_ml,
-    const int32_t* __restrict__ leader = nullptr, const int32_t* __restrict__ trunk = nullptr, int nrec = 0, int rec0 = 0,
-    int S = 0) {
+    const int32_t* __restrict__ leader, const int32_t* __restrict__ trunk, int nrec, int rec0, int S) {
     __shared__ __attribute__((aligned(16))) char smem[pcr::rows_lds_bytes<D, RT>()];
     const int n = threadIdx.x & 15, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int split = blockIdx.x, b = blockIdx.z;
@@ -117,11 +117,11 @@ __global__ __launch_bounds__(kThreads, RT > 1 ? 1 : 2) void attn_verify_slots_ke
         const int di = pad[rt] ? 0 : c / G, gh = pad[rt] ? 0 : c - di * G;
         lim[rt] = pad[rt] ? 0 : past + di + 1;
         qoff[rt] = (int64_t)(b * (k + 1) + di) * q_ts + (int64_t)(kvh * G + gh) * D;
-        rec[rt] = ((int64_t)(b * (k + 1) + di) * H + kvh * G + gh) * (TRUNK ? nrec : nsplit) + (TRUNK ? rec0 : 0) + split;
+        rec[rt] = ((int64_t)(b * (k + 1) + di) * H + kvh * G + gh) * nrec + rec0 + split;
     }
 
     int t0 = 0;                                      // first key of this launch
-    if constexpr (TRUNK) t0 = slot_trunk_rows(b, S, kv_base, cap, len, leader, trunk);
+    if (leader != nullptr) t0 = slot_trunk_rows(b, S, kv_base, cap, len, leader, trunk);
     int cpw = (nkeys - t0 + nsplit * 4 - 1) / (nsplit * 4);        // keys per wave
     cpw = (cpw + 15) & ~15;
     const int k0 = t0 + (split * 4 + wave) * cpw;
@@ -199,16 +199,17 @@ __global__ __launch_bounds__(kThreads, RT > 1 ? 1 : 2) void attn_verify_trunk_sl
                                        part_o, part_ml);
 }
 
-// own launch of a slot's rows (RT = 2 where its (k + 1) * G columns fill more than one tile)
-template <int D, bool TRUNK>
+// own launch of a slot's rows (RT = 2 where its (k + 1) * G columns fill more than one tile); a plain entry's leader / trunk words
+// are null and its ns_trunk 0: nrec = ns_own, rec0 = 0
+template <int D>
 void launch_verify_own(const SlotAttnArgs& a, hipStream_t st) {
     const int cols = (a.k + 1) * (a.H / a.Hkv), nrec = a.ns_trunk + a.ns_own;
     if (cols <= 16)
-        hipLaunchKernelGGL((attn_verify_slots_kernel<D, 1, TRUNK>), dim3(a.ns_own, a.Hkv, a.S), dim3(kThreads), 0, st, a.q_hi, a.q_lo,
+        hipLaunchKernelGGL((attn_verify_slots_kernel<D, 1>), dim3(a.ns_own, a.Hkv, a.S), dim3(kThreads), 0, st, a.q_hi, a.q_lo,
                            a.q_ts, a.kv_base, a.cap, a.len, a.live, a.k, a.layer, a.H, a.Hkv, a.scale_log2, a.ns_own, a.part_o, a.part_ml,
                            a.leader, a.trunk, nrec, a.ns_trunk, a.S);
     else
-        hipLaunchKernelGGL((attn_verify_slots_kernel<D, 2, TRUNK>), dim3(a.ns_own, a.Hkv * ((cols + 31) / 32), a.S), dim3(kThreads), 0,
+        hipLaunchKernelGGL((attn_verify_slots_kernel<D, 2>), dim3(a.ns_own, a.Hkv * ((cols + 31) / 32), a.S), dim3(kThreads), 0,
                            st, a.q_hi, a.q_lo, a.q_ts, a.kv_base, a.cap, a.len, a.live, a.k, a.layer, a.H, a.Hkv, a.scale_log2, a.ns_own,
                            a.part_o, a.part_ml, a.leader, a.trunk, nrec, a.ns_trunk, a.S);
 }
@@ -227,7 +228,7 @@ template <int D>
 void launch_merge(const SlotAttnArgs& a, bool trunk, hipStream_t st) {
     hipLaunchKernelGGL((pcr::attn_merge_slots_kernel<D>), dim3(a.H, a.S * (a.k + 1)), dim3(D), 0, st, a.part_o, a.part_ml, a.cap,
                        a.len, a.live, trunk ? a.leader : nullptr, a.trunk, a.kv_base, a.S, a.k, a.H, a.ns_trunk,
-                       a.ns_trunk + a.ns_own + a.ns_extra, a.of_hi, a.of_lo);
+                       a.ns_trunk + a.ns_own + a.ns_extra, a.of_hi, a.of_lo, trunk ? a.kvq_base : nullptr, a.qcap);
 }
 
 bool rows_shape_ok(int S, int k) { return S >= 1 && S <= 16 && k >= 0 && k <= 15 && S * (k + 1) <= kMaxRows; }
@@ -307,8 +308,8 @@ PC_EXPORT int pc_attn_verify_slots(const void* q_hi, const void* q_lo, int64_t q
                       S, k, layer, H, Hkv, 0.f, nsplit, 0, nullptr, nullptr, (_Float16*)out_frag_hi, (_Float16*)out_frag_lo};
     if (const int rc = pcr::slot_attn_prepare("pc_attn_verify_slots", true, false, 16, a, D, softmax_scale, workspace, workspace_bytes))
         return rc;
-    if (D == 128) launch_verify_own<128, false>(a, (hipStream_t)stream);
-    else launch_verify_own<64, false>(a, (hipStream_t)stream);
+    if (D == 128) launch_verify_own<128>(a, (hipStream_t)stream);
+    else launch_verify_own<64>(a, (hipStream_t)stream);
     pcr::launch_attn_merge_slots(a, D, false, (hipStream_t)stream);
     return pc_check_launch("attn_verify_slots_kernel");
 }
@@ -331,8 +332,8 @@ PC_EXPORT int pc_attn_verify_slots_trunk(const void* q_hi, const void* q_lo, int
     // trunk launch (RT = 2 where the S slots can fill more than one tile: it halves the passes over the trunk), own launch, merge
     hipStream_t st = (hipStream_t)stream;
     pcr::launch_attn_trunk_slots(a, D, S * (k + 1) * (H / Hkv) <= 16 ? 1 : 2, st);
-    if (D == 128) launch_verify_own<128, true>(a, st);
-    else launch_verify_own<64, true>(a, st);
+    if (D == 128) launch_verify_own<128>(a, st);
+    else launch_verify_own<64>(a, st);
     pcr::launch_attn_merge_slots(a, D, true, st);
     return pc_check_launch("attn_verify_trunk_slots_kernel");
 }

@@ -37,6 +37,12 @@
 // of a fresh-row buffer that is now [P][k + 1][D]) AND as image row len + i; the attention gives draft row i the image keys
 // [0, len + i) and its own key exact -- what the one-row step above computes for the token at that position, whatever the step
 // boundaries and however many drafts were accepted.
+//
+// Shared trunks over images (pc_attn_decode_slots_trunk_q8, model/llama_hip.py SlotLoopQ8 with trunks): slots whose first T rows
+// are the same fp16 rows hold the same image rows [0, T) -- pc_kv_quant_q8_rows is row-local -- so a group's trunk is read once
+// per step, from the leader's image, for all live members (attn_trunk_slots_q8_kernel); every slot reads image rows [T, len) and
+// the exact row of its own and stages that row into its own image (attn_decode_slots_q8_kernel<true>).  One predicate,
+// slot_trunk_rows_q8 (pc_lookup_common.h), is asked by both launches and by the merge.  Image rows below len are written by nobody.
 #include <hip/hip_fp16.h>
 #include <math.h>
 
@@ -150,11 +156,17 @@ __global__ __launch_bounds__(kThreads) void rope_append_slots_q8_kernel(
 __device__ __forceinline__ float code_f32(uint32_t w, int b) { return (float)(int)(int8_t)(w >> (8 * b)); }
 
 // grid (split, query head, slot)
+// TRUNK (pc_attn_decode_slots_trunk_q8): a slot with shared rows (slot_trunk_rows_q8) takes keys [t0, len] only -- image rows
+// [t0, len) of its OWN image and the exact row; its image rows [0, t0) are never read, the keys in front of t0 are the trunk
+// launch's -- and its partials are records rec0 .. rec0 + nsplit - 1 of the nrec records per (slot, head).  t0 <= len: at least the
+// exact key is left.  With t0 = 0 the arithmetic is the plain instantiation's.
+template <bool TRUNK = false>
 __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
     const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo, int64_t q_ts, const uint64_t* __restrict__ kv_base,
     const uint64_t* __restrict__ kvq_base, const int32_t* __restrict__ cap, const int32_t* __restrict__ len,
     const int32_t* __restrict__ live, int layer, int n_layers, int H, int Hkv, int qcap, float scale_log2, int nsplit,
-    float* __restrict__ part_o, float* __restrict__ part_ml, int fresh) {
+    float* __restrict__ part_o, float* __restrict__ part_ml, int fresh, const int32_t* __restrict__ leader = nullptr,
+    const int32_t* __restrict__ trunk = nullptr, int nrec = 0, int rec0 = 0, int S = 0) {
     __shared__ float sm[4][kD + 2];
 
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
@@ -164,8 +176,10 @@ __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
     if (past >= qcap) return;                     // out of contract (the host sizes qcap >= every cap): nothing leaves the image
     const int G = H / Hkv, kvh = h / G;
     const int n = past + 1;                       // keys of this slot: image rows [0, past) and the row just appended
-    const int chunk = (n + nsplit - 1) / nsplit;
-    const int k0 = split * chunk, k1 = min(n, k0 + chunk);
+    int t0 = 0;                                   // first key of this launch (<= past)
+    if constexpr (TRUNK) t0 = slot_trunk_rows_q8(b, S, kvq_base, qcap, len, leader, trunk);
+    const int chunk = (n - t0 + nsplit - 1) / nsplit;
+    const int k0 = t0 + split * chunk, k1 = min(n, k0 + chunk);
     const int kq = min(k1, past);                 // image keys of this slice: [k0, kq)
     const bool has_new = k0 <= past && past < k1; // (uniform over the workgroup)
 
@@ -309,7 +323,7 @@ __global__ __launch_bounds__(kThreads) void attn_decode_slots_q8_kernel(
             den = fmaf(wt, sm[w][kD + 1], den);
             num = fmaf(wt, sm[w][d], num);
         }
-        const int64_t rec = ((int64_t)b * H + h) * nsplit + split;
+        const int64_t rec = TRUNK ? ((int64_t)b * H + h) * nrec + rec0 + split : ((int64_t)b * H + h) * nsplit + split;
         part_o[rec * kD + d] = num;
         if (d == 0) { part_ml[rec * 2] = ms; part_ml[rec * 2 + 1] = den; }
     }
@@ -385,6 +399,79 @@ __global__ __launch_bounds__(kThreads, 2) void attn_verify_slots_q8_kernel(
     }
 }
 
+// ---- shared trunk over images: the keys a group of slots has in common, read once for all members (pc_attn_decode_slots_trunk_q8) -
+// attn_verify_trunk_slots_kernel (pc_lookup_slots.hip) at k = 0 with the tile loop reading codes (pcr::attn_rows_tiles_q8): grid
+// (trunk split, kv head x pass, candidate leader), S * G columns cut into passes; a tile column is (member m, query head g of the kv
+// head), column index m * G + g among nmem * G, 16 per MFMA tile, RT tiles per pass.  The keys [0, T) are rows of the LEADER's image
+// -- read whether or not the leader is live: no step writes an image row below len >= T -- and every column's limit is T.  Members
+// are the live slots of leader gl with 0 <= len < cap, len < qcap -- the slots the own launch works for -- and slot_trunk_rows_q8 > 0,
+// in slot order.  The key slices are a function of (T, nsplit_t), every reduction runs in a fixed order and a column of an MFMA
+// tile depends on that column's B operand only: what a member gets does not depend on how many members the group has, on its place
+// in the tile or on the slot index.  Records 0 .. nsplit_t - 1 of the nrec per (slot, head); pad columns are zero and are never
+// written; no image byte is written.
+template <int RT>
+__global__ __launch_bounds__(kThreads, RT > 1 ? 1 : 2) void attn_trunk_slots_q8_kernel(
+    const _Float16* __restrict__ q_hi, const _Float16* __restrict__ q_lo, int64_t q_ts, const uint64_t* __restrict__ kvq_base,
+    const int32_t* __restrict__ cap, const int32_t* __restrict__ len, const int32_t* __restrict__ live,
+    const int32_t* __restrict__ leader, const int32_t* __restrict__ trunk, int S, int layer, int n_layers, int H, int Hkv, int qcap,
+    float scale_log2, int nsplit_t, int nrec, float* __restrict__ part_o, float* __restrict__ part_ml) {
+    __shared__ __attribute__((aligned(16))) char smem[pcr::rows_lds_bytes<kD, RT>()];
+    const int n = threadIdx.x & 15, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int split = blockIdx.x, gl = blockIdx.z;
+    const int G = H / Hkv, passes = (S * G + 16 * RT - 1) / (16 * RT);
+    const int kvh = blockIdx.y / passes, col0 = (blockIdx.y - kvh * passes) * 16 * RT;
+    const int T = trunk[gl];
+    if (leader[gl] != gl || T <= 0 || T > qcap || kvq_base[gl] == 0) return;  // (no slot_trunk_rows_q8 of this group is non-zero)
+
+    // the member list, in slot order: lane b < S of every wave answers for slot b -- the S slots' words in one round of loads, not
+    // one slot after the other -- and the ballot is the list (the same in every wave: workgroup-uniform)
+    bool mem = false;
+    {
+        const int b = threadIdx.x & 63;
+        if (b < S) {
+            const int past = len[b];
+            mem = leader[b] == gl && live[b] != 0 && past >= 0 && past < cap[b] && past < qcap &&
+                  slot_trunk_rows_q8(b, S, kvq_base, qcap, len, leader, trunk) > 0;
+        }
+    }
+    const uint32_t members = (uint32_t)__ballot(mem);                         // (S <= 16)
+    const int nmem = __popc(members);
+    if (col0 >= nmem * G) return;                    // workgroup-uniform: no member, or no column left for this pass
+
+    // this lane's column of each tile: member, query head, slot (negative: a pad column) -- the slot of member m is the m-th set bit
+    int gh[RT], qr[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int c = col0 + rt * 16 + n, m = c / G;
+        gh[rt] = c - m * G;
+        uint32_t rest = members;
+        for (int j = 0; j < m && rest != 0; ++j) rest &= rest - 1;
+        qr[rt] = (m < nmem && rest != 0) ? __builtin_ctz(rest) : -1;
+    }
+
+    int cpw = (T + nsplit_t * 4 - 1) / (nsplit_t * 4);             // keys per wave
+    cpw = (cpw + 15) & ~15;
+    const int k0 = (split * 4 + wave) * cpw;
+    const int k1 = (k0 + cpw < T) ? k0 + cpw : T;
+
+    int64_t qoff[RT], rec[RT];
+    bool pad[RT];
+    int lim[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        pad[rt] = qr[rt] < 0;
+        const int row = pad[rt] ? 0 : qr[rt], head = kvh * G + (pad[rt] ? 0 : gh[rt]);
+        lim[rt] = pad[rt] ? 0 : T;
+        qoff[rt] = (int64_t)row * q_ts + (int64_t)head * kD;
+        rec[rt] = ((int64_t)row * H + head) * nrec + split;
+    }
+    const int64_t kplane = (int64_t)(layer * 2) * Hkv + kvh, vplane = kplane + Hkv;
+    const char* img = (const char*)(uintptr_t)kvq_base[gl];
+    const float* sbase = (const float*)(img + (int64_t)n_layers * 2 * Hkv * qcap * kD);
+    pcr::attn_rows_tiles_q8<RT>(q_hi, q_lo, qoff, pad, lim, rec, img + kplane * qcap * kD, img + vplane * qcap * kD,
+                                sbase + kplane * qcap, sbase + vplane * qcap, k0, k1, scale_log2, smem, part_o, part_ml);
+}
+
 }  // namespace
 
 namespace {
@@ -401,14 +488,51 @@ int attn_slots_q8(const char* name, int fresh, const void* q_hi, const void* q_l
     SlotAttnArgs a = {(const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len, live, nullptr, nullptr,
                       S, 0, layer, H, Hkv, 0.f, nsplit, 0, nullptr, nullptr, (_Float16*)out_frag_hi, (_Float16*)out_frag_lo};
     if (const int rc = pcr::slot_attn_prepare(name, false, false, 8, a, D, softmax_scale, workspace, workspace_bytes)) return rc;
-    hipLaunchKernelGGL(attn_decode_slots_q8_kernel, dim3(a.ns_own, a.H, a.S), dim3(kThreads), 0, (hipStream_t)stream, a.q_hi, a.q_lo,
-                       a.q_ts, a.kv_base, kvq_base, a.cap, a.len, a.live, a.layer, n_layers, a.H, a.Hkv, qcap, a.scale_log2, a.ns_own,
-                       a.part_o, a.part_ml, fresh);
+    hipLaunchKernelGGL(attn_decode_slots_q8_kernel<false>, dim3(a.ns_own, a.H, a.S), dim3(kThreads), 0, (hipStream_t)stream, a.q_hi,
+                       a.q_lo, a.q_ts, a.kv_base, kvq_base, a.cap, a.len, a.live, a.layer, n_layers, a.H, a.Hkv, qcap, a.scale_log2,
+                       a.ns_own, a.part_o, a.part_ml, fresh, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, 0, 0);
     pcr::launch_attn_merge_slots(a, D, false, (hipStream_t)stream);
     return pc_check_launch("attn_decode_slots_q8_kernel");
 }
 
+// trunk launch of pc_attn_decode_slots_trunk_q8; grid.y follows the kernel's own pass count, ceil(S * G / (16 * RT))
+template <int RT>
+void launch_trunk_q8(const SlotAttnArgs& a, int n_layers, hipStream_t st) {
+    const int passes = pc_ceil_div(a.S * (a.H / a.Hkv), 16 * RT);
+    hipLaunchKernelGGL(attn_trunk_slots_q8_kernel<RT>, dim3(a.ns_trunk, a.Hkv * passes, a.S), dim3(kThreads), 0, st, a.q_hi, a.q_lo,
+                       a.q_ts, a.kvq_base, a.cap, a.len, a.live, a.leader, a.trunk, a.S, a.layer, n_layers, a.H, a.Hkv, a.qcap,
+                       a.scale_log2, a.ns_trunk, a.ns_trunk + a.ns_own, a.part_o, a.part_ml);
+}
+
 }  // namespace
+
+// pc_attn_decode_slots_q8 for slots that share their leading rows: three launches asking slot_trunk_rows_q8 -- the shared rows of
+// every group from the leader's image (attn_trunk_slots_q8_kernel, RT = 2 where the S slots can fill more than one tile), every
+// slot's own image rows and exact row (attn_decode_slots_q8_kernel<true>, which stages the row as the plain entry does), merge.
+PC_EXPORT int pc_attn_decode_slots_trunk_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
+                                            const int32_t* cap, const int32_t* len, const int32_t* live, const int32_t* leader,
+                                            const int32_t* trunk, int32_t S, int32_t layer, int32_t H, int32_t Hkv, int32_t D,
+                                            float softmax_scale, int32_t nsplit_own, int32_t nsplit_trunk, void* workspace,
+                                            int64_t workspace_bytes, void* out_frag_hi, void* out_frag_lo, const uint64_t* kvq_base,
+                                            int32_t qcap, int32_t n_layers, void* stream) {
+    const char* name = "pc_attn_decode_slots_trunk_q8";
+    PC_REQUIRE(D == kD, PC_ERR_ARG, "%s: head_dim must be 128", name);
+    PC_REQUIRE(kvq_base != nullptr, PC_ERR_ARG, "%s: null pointer", name);
+    PC_REQUIRE(qcap >= 1 && n_layers >= 1 && layer < n_layers, PC_ERR_ARG,
+               "%s: qcap >= 1 and 0 <= layer < n_layers (the image's scales start behind all its planes)", name);
+    SlotAttnArgs a = {(const _Float16*)q_hi, (const _Float16*)q_lo, q_token_stride, kv_base, cap, len, live, leader, trunk,
+                      S, 0, layer, H, Hkv, 0.f, nsplit_own, nsplit_trunk, nullptr, nullptr, (_Float16*)out_frag_hi, (_Float16*)out_frag_lo,
+                      0, kvq_base, qcap};
+    if (const int rc = pcr::slot_attn_prepare(name, false, true, 16, a, D, softmax_scale, workspace, workspace_bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (a.S * (a.H / a.Hkv) <= 16) launch_trunk_q8<1>(a, n_layers, st);
+    else launch_trunk_q8<2>(a, n_layers, st);
+    hipLaunchKernelGGL(attn_decode_slots_q8_kernel<true>, dim3(a.ns_own, a.H, a.S), dim3(kThreads), 0, st, a.q_hi, a.q_lo, a.q_ts,
+                       a.kv_base, a.kvq_base, a.cap, a.len, a.live, a.layer, n_layers, a.H, a.Hkv, a.qcap, a.scale_log2, a.ns_own, a.part_o,
+                       a.part_ml, 0, a.leader, a.trunk, a.ns_trunk + a.ns_own, a.ns_trunk, a.S);
+    pcr::launch_attn_merge_slots(a, D, true, st);
+    return pc_check_launch("attn_trunk_slots_q8_kernel");
+}
 
 PC_EXPORT int pc_attn_decode_slots_q8(const void* q_hi, const void* q_lo, int64_t q_token_stride, const uint64_t* kv_base,
                                       const int32_t* cap, const int32_t* len, const int32_t* live, int32_t S, int32_t layer,

@@ -241,6 +241,8 @@ SIGNATURES = {
     "pc_attn_decode_slots_trunk_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "pc_attn_decode_slots_trunk": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
                                              _vp, _i64, _vp, _vp, _vp]),
+    "pc_attn_decode_slots_trunk_q8": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32,
+                                                _i32, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp]),
     "pc_sample_advance_slots": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                                           _vp, _vp]),
     "pc_sample_advance_slots_each": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
@@ -1070,6 +1072,22 @@ def attn_decode_slots_trunk(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, l
                                            workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(),
                                            out_frag[1].data_ptr(), current_stream() if stream is None else stream)
     check(rc, "pc_attn_decode_slots_trunk")
+
+
+def attn_decode_slots_trunk_q8(q_hi, q_lo, q_ts: int, kv_base, cap, length, live, leader, trunk, S: int, layer: int, H: int, Hkv: int,
+                               D: int, softmax_scale: float, nsplit_own: int, nsplit_trunk: int, workspace, out_frag, kvq_base,
+                               qcap: int, n_layers: int, stream: Optional[int] = None) -> None:
+    """``attn_decode_slots_q8`` with shared trunks: keys [0, trunk[b]) of a slot with leader[b] = g are rows of slot g's int8 image,
+    read once for all members of the group; keys [trunk[b], len) rows of the slot's own image, the appended row exact and staged
+    into the slot's own image (pc_attn_decode_slots_trunk_q8; workspace: ``attn_decode_slots_trunk_workspace_bytes``) -> fragment
+    planes (hi, lo)."""
+    rc = load().pc_attn_decode_slots_trunk_q8(q_hi.data_ptr(), q_lo.data_ptr(), q_ts, kv_base.data_ptr(), cap.data_ptr(),
+                                              length.data_ptr(), live.data_ptr(), leader.data_ptr(), trunk.data_ptr(), S, layer, H,
+                                              Hkv, D, softmax_scale, nsplit_own, nsplit_trunk, workspace.data_ptr(),
+                                              workspace.numel() * workspace.element_size(), out_frag[0].data_ptr(),
+                                              out_frag[1].data_ptr(), kvq_base.data_ptr(), qcap, n_layers,
+                                              current_stream() if stream is None else stream)
+    check(rc, "pc_attn_decode_slots_trunk_q8")
 
 
 def lookup_draft_slots(hist, hist_len, ids, pos, ndraft, cap, length, live, S: int, k: int, nmax: int = 3,

@@ -435,7 +435,7 @@ class GenerationEngine:
             off = "PC_DEVICE_SAMPLE=0"
         has = hasattr(hf, "lookup_slot_loop")
         return modes.Capabilities(no_loop, no_loop or off, has, has and says("lookup_available"), says("lookup_slot_q8_available"),
-                                  says("lookup_trunk_available"), getattr(hf, "D", None))
+                                  says("lookup_trunk_available"), getattr(hf, "D", None), says("slot_trunk_q8_available"))
 
     def _batch_modes(self, n_requests: int, params: GenerationParameters, **kw) -> modes.Modes:
         return modes.resolve_batch(self._capabilities(params.plain_greedy, not params.plain_greedy), n_requests, params.plain_greedy,
@@ -574,7 +574,12 @@ class GenerationEngine:
         loop runs.  With ``share_trunk`` the step reads a group's shared rows once for all draft rows of the group.  In the
         lookup form ``last_serve_stats`` gains ``tokens`` (decoded in the loop) and ``steps`` (replays).
         ``slot_kv`` (None: ``PC_SLOT_KV``, default "fp16"): ``generate_batch``'s -- "int8" serves over int8 images of the slots' rows,
-        sized from ``cache_engine.max_ctx_length``; ValueError with ``share_trunk`` or where ``serve_plan`` says no.  Together with
+        sized from ``cache_engine.max_ctx_length``; ValueError where ``serve_plan`` says no.  Together with ``share_trunk`` (DESIGN
+        3.33) the one-token loop reads a group's shared rows once per step from the LEADER's image and every slot's own rows from
+        its own (``LlamaHIP.slot_loop(each=True, kv="int8", trunks=...)``, ``pc_attn_decode_slots_trunk_q8``); grouping, joining and
+        the hold on the leader's slot are ``share_trunk``'s.  ValueError on a model without that step
+        (``slot_trunk_q8_available``), with ``lookup`` > 0 (the lookup step over images has no shared-trunk form) and with
+        ``keep_arenas=False``.  Together with
         ``lookup`` > 0 the lookup step itself reads the images (``LlamaHIP.lookup_slot_loop(kv="int8")``): every draft
         row attends to the quantised rows in front of it and to its own row exactly, so on identical logits the tokens are
         ``serve(slot_kv="int8")``'s; ValueError on a model without that step (``lookup_slot_q8_available``).

@@ -650,6 +650,22 @@ class _SlotLoopHost:
         m = self.m
         _native.kv_quant_q8_rows(a.buf, a.cap, a.length, m.L * 2 * m.Hkv, m.D, self.kvq[s], self.qcap)
 
+    def _trunk_verify_images(self, s: int, leader: int, T: int) -> None:
+        """kv="int8" under ``PC_TRUNK_VERIFY=1``, behind ``_quantise_entry``: rows [0, T) of every plane of the image of slot ``s``
+        -- codes and scales -- must be the bytes of the same rows of its trunk leader's image, which the step reads in their place
+        (``pc_kv_quant_q8_rows`` is row-local, so equal fp16 rows give equal image rows)."""
+        if self.kv != "int8" or leader == s or os.environ.get("PC_TRUNK_VERIFY", "0") != "1":
+            return
+        m = self.m
+        P, qcap, D = m.L * 2 * m.Hkv, self.qcap, m.D
+
+        def rows(img):
+            return img[:P * qcap * D].view(P, qcap, D)[:, :T], img[P * qcap * D:P * qcap * (D + 4)].view(torch.int32).view(P, qcap)[:, :T]
+        (c, sc), (lc, lsc) = rows(self.kvq[s]), rows(self.kvq[leader])
+        if not (torch.equal(c, lc) and torch.equal(sc, lsc)):
+            raise RuntimeError(f"PC_TRUNK_VERIFY: image rows [0, {T}) of the sequence for slot {s} differ from its trunk leader's "
+                               f"(slot {leader})")
+
     def _enter(self, s: int, a, trunk, max_new: int, stop_ids) -> int:
         """Sequence number ``len(arenas)`` sits in slot ``s`` from replay ``n`` on: one more row of every per-sequence table."""
         k, prev = len(self.arenas), self._slot_seq[s]
@@ -706,6 +722,8 @@ class _SlotLoopHost:
                       trunk=T, budget=int(max_new), counter=self.ctr0 + self.n, **extra)
         off = _fill_arm_block(arr, self._arm_header, fields, seed, params, stop_ids, history, m.config.vocab_size)
         self._quantise_entry(s, a)
+        if leader >= 0:
+            self._trunk_verify_images(s, leader, T)
         self._arm(ent[0], arr, off, hist, *more)
         ent[1].record()
         ent[2] = True
@@ -2789,6 +2807,11 @@ class LlamaHIP:
                     not self.int8_weights and not self.llm_int8 and self.fuse_norm and not self.decode_tail and
                     not self.use_chain and self.D in (64, 128) and self.batch_invariant)
 
+    def slot_trunk_q8_available(self) -> bool:
+        """Whether ``slot_loop(each=True, kv="int8", trunks=...)`` runs: the slot loop, and head_dim 128
+        (``pc_attn_decode_slots_trunk_q8``)."""
+        return bool(self.slot_loop_available() and self.D == 128)
+
     def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
                   slots: Optional[int] = None, slot_index=None, share_trunk: bool = False,
                   min_trunk: Optional[int] = None, each: bool = False, max_keys: Optional[int] = None,
@@ -2810,7 +2833,12 @@ class LlamaHIP:
         ``kv="int8"``: the loop keeps an int8 image (the format of ``pc_kv_quant_q8``) of every slot's rows and the
         attention reads that instead of the fp16 arena -- about half the bytes; accuracy is the format's.  The arenas stay
         complete (every decoded row is still appended), so memory GROWS by 0.516 of an arena per slot.  ``max_keys`` then also
-        sizes the images.  Not with ``share_trunk`` / ``trunks`` and head_dim 128 only: ``check_slot_kv`` raises ValueError.
+        sizes the images.  head_dim 128 only: ``check_slot_kv`` raises ValueError.  With ``share_trunk`` / ``trunks`` and
+        ``each=True`` (``slot_trunk_q8_available``): a group's shared rows are read once per step from the LEADER's
+        image, every slot's rows behind them from its own (``pc_attn_decode_slots_trunk_q8``) -- equal fp16 rows give equal image
+        rows, since ``pc_kv_quant_q8_rows`` is row-local; ``PC_TRUNK_VERIFY=1`` compares image rows [0, T) of member and leader
+        byte for byte as a member enters.  Memory is unchanged: every member keeps its own copy.  With ``each=False``, and with
+        ``keep_arenas=False``, the pair raises ValueError.
         ``keep_arenas=False`` (with ``kv="int8"`` only): the loop keeps the images and one fresh-row buffer per slot
         and NO reference to the arenas behind ``pasts`` -- their rows are quantised into the images on entry and the arenas are
         free afterwards (``SlotLoopQ8Only``); with ``each=True`` one arena can prefill every sequence in turn.
@@ -2819,8 +2847,9 @@ class LlamaHIP:
         graph keys, state and launches."""
         check_logprobs(logprobs)
         check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, head_dim=self.D,
-                      no_loop=None if self.slot_loop_available() else "the model has no batched decode loop")
-        check_slot_keep_arenas(keep_arenas, kv)
+                      no_loop=None if self.slot_loop_available() else "the model has no batched decode loop",
+                      trunk_q8=bool(each) and getattr(self, "slot_trunk_q8_available", lambda: False)())
+        check_slot_keep_arenas(keep_arenas, kv, share_trunk=bool(share_trunk) or trunks is not None)
         front = self._slot_loop_front(pasts, stop_ids, each, share_trunk, min_trunk, trunks)
         if front is None:
             return None
@@ -2986,6 +3015,10 @@ class LlamaHIP:
             if fresh:
                 n.attn_decode_slots_q8_fresh(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
                                              self.softmax_scale, nsplit, ws, (ah, al), st["kvq_base"], qcap, self.L)
+            elif qcap and nsplit_trunk:
+                n.attn_decode_slots_trunk_q8(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], st["leader"],
+                                             st["trunk"], S, li, H, Hkv, D, self.softmax_scale, nsplit, nsplit_trunk, ws, (ah, al),
+                                             st["kvq_base"], qcap, self.L)
             elif qcap:
                 n.attn_decode_slots_q8(q16, q16l, H * D, st["kv_base"], st["cap"], st["len"], st["live"], S, li, H, Hkv, D,
                                        self.softmax_scale, nsplit, ws, (ah, al), st["kvq_base"], qcap, self.L)

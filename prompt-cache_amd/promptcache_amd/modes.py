@@ -72,19 +72,25 @@ SLOT_KV = ("fp16", "int8")
 
 
 def check_slot_kv(kv: str, share_trunk: bool = False, lookup: int = 0, head_dim: Optional[int] = None, no_loop: Optional[str] = None,
-                  not_batched: Optional[str] = None, lookup_q8: bool = False) -> None:
+                  not_batched: Optional[str] = None, lookup_q8: bool = False, trunk_q8: bool = False) -> None:
     """``ValueError`` naming the conflict for a ``slot_kv`` / ``kv`` mode the batched decode loop cannot run -- raised before
     anything is allocated.  Pure.  ``no_loop``: why the model has no slot loop (Falcon / MPT, ``load_in_8bit``,
     ``PC_DECODE_TAIL=1``), ``not_batched``: why ``batch_plan`` / ``serve_plan`` would not decode this batch in the device loop
     (None: they would).  ``lookup_q8``: the caller is ``serve`` / ``lookup_slot_loop`` and the model has the lookup step over
-    int8 images (``lookup_slot_q8_available``) -- ``lookup > 0`` is then no conflict."""
+    int8 images (``lookup_slot_q8_available``) -- ``lookup > 0`` is then no conflict.  ``trunk_q8``: the caller is
+    ``serve`` / ``slot_loop(each=True)`` and the model has the shared-trunk attention over int8 images
+    (``slot_trunk_q8_available``) -- ``share_trunk`` is then no conflict in the one-token loop (``lookup`` 0); the
+    lookup step over images has no shared-trunk form."""
     if kv not in SLOT_KV:
         raise ValueError(f"slot_kv must be one of {SLOT_KV}, not {kv!r}")
     if kv != "int8":
         return
-    if share_trunk:
+    if share_trunk and not trunk_q8:
         raise ValueError("slot_kv='int8' and share_trunk exclude each other (the shared-trunk attention reads the leader's fp16 "
                          "arena; int8 images under share_trunk are not implemented)")
+    if share_trunk and int(lookup) > 0:
+        raise ValueError("slot_kv='int8', share_trunk and lookup > 0 exclude each other (the lookup step over int8 images has no "
+                         "shared-trunk form; share_trunk over images is the one-token loop's, pc_attn_decode_slots_trunk_q8)")
     if int(lookup) > 0 and not lookup_q8:
         raise ValueError("slot_kv='int8' and lookup > 0 exclude each other (the k + 1 row verify step reads the fp16 arenas; "
                          "int8 images under lookup are not implemented)")
@@ -110,11 +116,16 @@ def check_loop_prefill(loop_prefill: bool, drafts: int, kv: str = "fp16", why: O
                          "forced rows over int8 images are not implemented)")
 
 
-def check_slot_keep_arenas(keep_arenas: bool, kv: str, generate_batch: bool = False) -> None:
+def check_slot_keep_arenas(keep_arenas: bool, kv: str, generate_batch: bool = False, share_trunk: bool = False) -> None:
     """``ValueError`` for ``keep_arenas=False`` (int8-only slot residency) where it cannot run -- raised before anything
-    is allocated, behind ``check_slot_kv``'s own refusals of ``kv``.  Pure."""
+    is allocated, behind ``check_slot_kv``'s own refusals of ``kv``.  Pure.  ``share_trunk`` (``serve``'s, over int8 images): the
+    one-buffer prefill builds the loop from a single sequence, so no group is founded."""
     if keep_arenas:
         return
+    if share_trunk and kv == "int8":
+        raise ValueError("keep_arenas=False and share_trunk exclude each other under slot_kv='int8': the one-buffer prefill builds "
+                         "the loop from a single sequence, so no group is founded in the first fill (share_trunk over int8 images "
+                         "keeps the fp16 slot arenas)")
     if generate_batch:
         raise ValueError("keep_arenas=False is not for generate_batch: its callers hand in one live fp16 arena per sequence, so "
                          "there is nothing to save; serve(slot_kv='int8', keep_arenas=False) prefills every request in one arena")
@@ -172,6 +183,7 @@ class Capabilities:
     lookup_q8: bool = False             # the lookup step over int8 images (``lookup_slot_q8_available``)
     lookup_trunk: bool = False          # the shared-trunk verify step (``lookup_trunk_available``)
     head_dim: Optional[int] = None
+    trunk_q8: bool = False              # the shared-trunk attention over int8 images (``slot_trunk_q8_available``)
 
 
 @dataclass(frozen=True)
@@ -249,11 +261,11 @@ def resolve_serve(caps: Capabilities, slots: Optional[int] = None, share_trunk: 
     drafts, no_drafts = _serve_drafts(caps, lookup, slots) if batched else (0, caps.not_batched)
     if validate and kv != "fp16":
         check_slot_kv(kv, share_trunk=bool(share_trunk), lookup=lookup, head_dim=caps.head_dim, no_loop=caps.no_loop,
-                      not_batched=caps.not_batched, lookup_q8=caps.lookup_q8)
+                      not_batched=caps.not_batched, lookup_q8=caps.lookup_q8, trunk_q8=caps.trunk_q8)
     if keep_arenas is None:
         keep_arenas = parse_keep_arenas(env.get("PC_SLOT_KEEP_ARENAS")) if validate else True
     if validate:
-        check_slot_keep_arenas(bool(keep_arenas), kv)
+        check_slot_keep_arenas(bool(keep_arenas), kv, share_trunk=bool(share_trunk))
     if loop_prefill is None:
         loop_prefill = env.get("PC_SERVE_LOOP_PREFILL", "0") == "1"
     check_loop_prefill(bool(loop_prefill), drafts, kv, no_drafts)

@@ -20,6 +20,11 @@ B (W + K) / (W + B K) from the weight bytes W a decode step streams and the K/V 
         # torch.cuda.memory_allocated() after the first fill for the fp16 loop, the int8 mode and int8-only -- the latter with
         # every sequence prefilled in ONE arena, measured before the other slots' arenas exist; (b) step time, legs interleaved
         # with the order rotating.  --out merges under "decode" / the weight format.
+    python tools/batch_decode_bench.py --slot-kv int8 --share-trunk [--weight-format mxfp4] [--out profiles/slot_trunk_q8_bench.json]
+        # shared trunks over int8 images (slot_loop(each=True, kv="int8", trunks=...)) beside the unshared int8 loop
+        # and the fp16 shared trunk, S = 4 / 8 / 16, loops built directly (generate_batch refuses the pair); step time, legs
+        # interleaved, next to the byte model (W + S K) / (W + K_t + S K_o).  --out merges under "decode" / the weight format.
+        # --batches 8 --repeats 1: the run to put under rocprofv3 --kernel-trace --stats.
 """
 import argparse
 import json
@@ -268,6 +273,93 @@ def slot_kv_only_bench(args):
     print(json.dumps(result))
 
 
+def slot_trunk_q8_bench(args):
+    """--slot-kv int8 --share-trunk: the each=True slot loop over int8 images without trunks (the baseline), with trunks
+    (slot_loop(each=True, kv="int8", trunks=...)) and, for context, the fp16 loop with trunks; built directly, since
+    generate_batch refuses the pair.  Same process, same prefilled slots, legs interleaved with the order rotating."""
+    from promptcache_amd.model.kv_arena import common_trunks
+    steps, warm = max(args.new, 40), 8
+    fmt_w = args.weight_format
+    lm = Llama2("llama2-7b", device="cuda:0", random_init=True, seed=0, **({"weight_format": fmt_w} if fmt_w != "fp16" else {}))
+    m, c = lm.hf_model, lm.hf_model.config
+    sizes = [int(b) for b in args.batches.split(",")] if args.batches != "1,2,4,8,16" else [4, 8, 16]
+    eng = CacheEngine(4096, lm, slots=max(sizes))
+    fmt = lm.get_formatter()
+    sp, pp = synth.persona_like()
+    eng.add_schema(fmt(sp))
+    prompt = Prompt(pp, [fmt])
+    pre = []                                                                   # per slot: (past, rows after the prefill, token, position)
+    for k in range(max(sizes)):
+        ids, pos, _, cache = eng.process(prompt, slot=k)
+        out = lm(input_ids=torch.tensor([ids], device="cuda:0"), position_ids=torch.tensor([pos], device="cuda:0"),
+                 past_key_values=cache, use_cache=True)
+        past = out.past_key_values
+        pre.append((past, past.arena.length, int(torch.argmax(out.logits[0, -1])), max(pos) + 2))
+    keys = pre[0][1]
+    hid, inter = c.hidden_size, c.intermediate_size
+    dec = 2 * m.L * ((m.H + 2 * m.Hkv) * m.D * hid + m.H * m.D * hid + 3 * inter * hid)          # fp16 bytes of the decoder linears
+    W = (dec * 17 // 64 if fmt_w == "mxfp4" else dec) + 2 * c.vocab_size * hid                     # (4.25 bits per MXFP4 weight)
+    result = {"shape": "llama2-7b (random init)", "weight_format": fmt_w, "prompt": f"persona schema, {keys} keys per slot after the prefill",
+              "steps": steps, "warm_steps_dropped": warm, "repeats": args.repeats, "weight_bytes_per_step": W,
+              "how": "SlotLoop(each=True, max_keys 4096) stepped by hand, greedy; ms per replay from the HIP events around it "
+                     f"(SlotLoop.elapsed_ms), steps {warm}..{steps - 1} of every repetition; legs interleaved, order rotating; median "
+                     "[min .. max]; byte model: (W + S K) / (W + K_t + S K_o) with int8 image bytes; a gain is claimed only where the "
+                     "shared median lies below the unshared leg's minimum", "rows": {}}
+
+    def leg(S, name):
+        pasts = []
+        for past, n0, _, _ in pre[:S]:
+            past.arena.length = n0                                             # (rows behind it are dead: the loop rewrites them)
+            pasts.append(past)
+        trunks = None if name == "int8" else common_trunks([p.arena.layout for p in pasts])
+        loop = m.slot_loop(pasts, [t for _, _, t, _ in pre[:S]], [p for _, _, _, p in pre[:S]], steps + 1, None, [0] * S, [()] * S, (),
+                           slots=S, each=True, max_keys=4096, trunks=trunks, kv="fp16" if name == "fp16_trunk" else "int8")
+        assert (loop.nsplit_trunk > 0) == (name != "int8"), (name, trunks)
+        try:
+            for _ in range(steps):
+                loop.enqueue()
+            toks = [loop.token(0, i) for i in range(steps)]
+            ms = [loop.elapsed_ms(i) for i in range(warm, steps)]
+        finally:
+            loop.close({k: 0 for k in range(S)})
+        return ms, toks, (trunks[0][1] if trunks else 0, loop.nsplit, loop.nsplit_trunk)
+
+    names = ["int8", "int8_trunk", "fp16_trunk"]
+    for S in sizes:
+        times = {name: [] for name in names}
+        same = info = None
+        for r in range(args.repeats + 1):                                       # (repetition 0 captures the graphs: dropped)
+            order = names[r % 3:] + names[:r % 3]
+            got = {name: leg(S, name) for name in order}
+            if r == 0:
+                same = got["int8"][1] == got["int8_trunk"][1]
+                info = got["int8_trunk"][2]
+                continue
+            for name in order:
+                times[name] += got[name][0]
+        row = {name + "_ms": {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "n": len(v)}
+               for name, v in times.items()}
+        T = info[0]
+        K, Kt = m.L * 2 * m.Hkv * keys * (m.D + 4), m.L * 2 * m.Hkv * T * (m.D + 4)
+        u, s = row["int8_ms"], row["int8_trunk_ms"]
+        row.update({"trunk_rows": T, "nsplit_own": info[1], "nsplit_trunk": info[2], "kv_bytes_int8_per_slot": K, "trunk_bytes_int8": Kt,
+                    "byte_model_ratio": round((W + S * K) / (W + Kt + S * (K - Kt)), 3),
+                    "unshared_over_shared": round(u["median"] / s["median"], 3),
+                    "fraction_of_byte_model": round(u["median"] / s["median"] / ((W + S * K) / (W + Kt + S * (K - Kt))), 3),
+                    "shared_median_below_unshared_min": s["median"] < u["min"], "tokens_of_sequence_0_equal": same})
+        result["rows"][str(S)] = row
+        print(json.dumps({str(S): row}), file=sys.stderr, flush=True)
+    if args.out:
+        merged = {}
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                merged = json.loads(fh.read() or "{}")
+        merged.setdefault("decode", {})["weights_" + fmt_w] = result
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(merged, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--new", type=int, default=64, help="greedy tokens per sequence")
@@ -286,6 +378,8 @@ def main():
     if args.slot_drop_fp16:
         assert args.slot_kv == "int8", "--slot-drop-fp16 needs --slot-kv int8"
         return slot_kv_only_bench(args)
+    if args.slot_kv == "int8" and args.share_trunk:
+        return slot_trunk_q8_bench(args)
     if args.slot_kv == "int8":
         return slot_kv_bench(args)
     batches = [int(b) for b in args.batches.split(",")]

@@ -193,8 +193,37 @@ def slot_drop_legs(ge, eng, prompts, lens, repeats, slots, fmt_w):
             "requests_with_equal_tokens": sum(answers["int8"][r] == answers["int8_only"][r] for r in answers["int8"])}
 
 
+def share_trunk_legs(ge, eng, prompts, lens, repeats, slots, fmt_w):
+    """serve(slot_kv="int8") -- the baseline --, serve(slot_kv="int8", share_trunk=True) and, for context, the fp16
+    serve(share_trunk=True), interleaved in one process with the order rotating.  tok/s over the whole run, median [min .. max]; a
+    gain is claimed only where the shared median exceeds the unshared leg's maximum."""
+    legs = {"int8": dict(slot_kv="int8"), "int8_trunk": dict(slot_kv="int8", share_trunk=True), "fp16_trunk": dict(share_trunk=True)}
+    answers = {}
+    for name, kw in legs.items():                                     # warm: every step captured
+        served(ge, eng, prompts, lens, **kw)
+        answers[name] = {r: list(t) for r, t in ge.last_serve_tokens.items()}
+    runs = {name: [] for name in legs}
+    names = list(legs)
+    for r in range(repeats):
+        for name in names[r % len(names):] + names[:r % len(names)]:
+            dt, n, replays, _ = served(ge, eng, prompts, lens, **legs[name])
+            runs[name].append(n / dt)
+            print(f"{name}: {n / dt:.1f} tok/s, {replays} replays", file=sys.stderr, flush=True)
+    out = {name: {"tok_s": {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}}
+           for name, v in runs.items()}
+    out["int8_trunk"]["median_over_int8_median"] = round(out["int8_trunk"]["tok_s"]["median"] / out["int8"]["tok_s"]["median"], 3)
+    out["int8_trunk"]["gain_claimed"] = out["int8_trunk"]["tok_s"]["median"] > out["int8"]["tok_s"]["max"]
+    return {"shape": "llama2-7b (random init)", "weight_format": fmt_w, "requests": len(prompts), "slots": slots, "max_new_tokens": lens,
+            "how": "greedy; decoded tokens per second over the whole serve run, prefills included; legs interleaved in one process, "
+                   f"order rotating, {repeats} repetitions, median [min .. max]", "legs": out,
+            "requests_with_equal_tokens": sum(answers["int8"][r] == answers["int8_trunk"][r] for r in answers["int8"])}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--share-trunk", action="store_true",
+                    help="serve(slot_kv='int8') against serve(slot_kv='int8', share_trunk=True) and the fp16 serve(share_trunk=True) "
+                         "(DESIGN 3.33); --out merges under the weight format and the slot count")
     ap.add_argument("--lookup", type=int, nargs="*", default=[])
     ap.add_argument("--requests", type=int, default=32)
     ap.add_argument("--slots", type=int, default=8)
@@ -222,6 +251,18 @@ def main():
     ge = GenerationEngine(lm)
     assert ge.serve_plan()[0], ge.serve_plan()[1]
     served(ge, eng, prompts, lens)                                    # warm: graphs captured, code objects loaded
+    if args.share_trunk:
+        res = share_trunk_legs(ge, eng, prompts, lens, args.repeats, args.slots, args.weight_format)
+        if args.out:
+            merged = {}
+            if os.path.exists(args.out):
+                with open(args.out) as fh:
+                    merged = json.loads(fh.read() or "{}")
+            merged.setdefault("serve", {})[f"weights_{args.weight_format}_S{args.slots}"] = res
+            with open(args.out, "w") as fh:
+                fh.write(json.dumps(merged, indent=1) + "\n")
+        print(json.dumps(res))
+        return
     if args.lookup and args.loop_prefill:
         res = loop_prefill_legs(ge, eng, prompts, lens, args.lookup, args.repeats, args.slots)
         res["weight_format"] = args.weight_format
