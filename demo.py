@@ -75,6 +75,13 @@ def main():
                     help="print every generated token with its log-probability and its N most likely alternatives (0..8), under the "
                          "model's own distribution: the log-softmax of the raw logits, before temperature, penalty, top-p and top-k "
                          "(GenerationParameters.logprobs; with --batch for all sequences, with --serve as serve(logprobs=N))")
+    ap.add_argument("--ban", type=int, nargs="+", default=None, metavar="ID",
+                    help="token ids that may not be generated (GenerationParameters.banned_token_ids: a logit bias of -inf, applied in "
+                         "front of temperature, penalty, top-p and top-k; with --serve as serve(token_controls=True))")
+    ap.add_argument("--allow", type=int, nargs="+", default=None, metavar="ID",
+                    help="the only token ids that may be generated (GenerationParameters.allowed_token_ids)")
+    ap.add_argument("--min-new", type=int, default=0, metavar="N",
+                    help="hold the stop token ids back for the first N generated tokens (GenerationParameters.min_new_tokens)")
     a = ap.parse_args()
     skw = dict(keep_arenas=False) if a.slot_drop_fp16 else {}
     wkw = dict(weight_format=a.weights, **(dict(keep_fp16=False) if a.drop_fp16 else {}))
@@ -99,7 +106,7 @@ def main():
           ", ".join(f"{nm} {b / 2 ** 20:.1f} MiB" for nm, b in cache_engine.module_bytes().items()))
     params = GenerationParameters(temperature=1.0, repetition_penalty=1.0, top_p=0.95, top_k=-1,
                                   max_new_tokens=a.max_new_tokens, stop_token_ids=lm.stop_token_ids, stop_str=lm.stop_str,
-                                  logprobs=a.logprobs)
+                                  logprobs=a.logprobs, banned_token_ids=a.ban, allowed_token_ids=a.allow, min_new_tokens=a.min_new)
     prompt = Prompt(prompt_text, preproc)
     for no_cache in (False, True, False):       # the first pass also warms the hipGraph / allocator
         token_ids, position_ids, cache_time, cache = cache_engine.process(
@@ -162,7 +169,8 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for r, out in gen_engine.serve(cache_engine, stream(), stream_interval=2, share_trunk=a.share_trunk, lookup=a.lookup,
-                                              slot_kv=a.slot_kv, logprobs=a.logprobs, **skw, **pkw):
+                                              slot_kv=a.slot_kv, logprobs=a.logprobs,
+                                              token_controls=params.token_controls is not None or None, **skw, **pkw):
                 lasts[r] = out
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0

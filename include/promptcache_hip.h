@@ -1112,6 +1112,42 @@ int pc_lookup_verify_slots_prompt(const float* logits, int64_t ldl, int32_t voca
 int pc_token_logprobs(const float* logits, int64_t ldl, int32_t vocab, int32_t rows, const int64_t* tok64, const int32_t* tok32,
                       int64_t tok_stride, int32_t top_n, int32_t* out_ids, float* out_lp, void* stream);
 
+/* ---- token controls: logit_bias, banned / allowed ids, min_new_tokens (csrc/pc_logit_ctl.hip; no reference counterpart) ---------------
+ * pc_logit_adjust: the ADJUSTED copy of S * rows_per_slot rows of fp32 logits, which a sampler then reads in place of the raw rows
+ * (any of the advance / verify entries above, in front of their temperature / penalty / top-p / top-k / greedy rule).  Row
+ * r = b * rows_per_slot + i of `out` is the adjusted form of row r of `logits` under slot b's block ctl[b] and allowed row
+ * allowed_bits[b] (bit j & 31 of word j >> 5 set: token j may be drawn).  Per row, in this order:
+ *   1. a[j] = x[j];
+ *   2. for each of the first n_bias table entries, a[id] = x[id] + bias: one fp32 add, so a bias of -inf is a ban and a NaN stays
+ *      a NaN.  The ids are distinct (host contract); an id outside [0, vocab) is skipped; n_bias is clamped into
+ *      [0, PC_LOGIT_BIAS_MAX];
+ *   3. with use_allowed != 0 (and allowed_bits non-null), every j whose bit is clear: a[j] = -inf -- a biased id included;
+ *   4. while len[b] + i < stop_free_len, a[stop] = -inf for the stop_ids inside [0, vocab).  len[b] is the arena length the decode
+ *      loops already keep (it grows by the tokens emitted; a null `len` reads as 0), i the draft row, so the boundary may fall
+ *      between two rows of one slot.  A sequence that enters with length L0 and must not stop before its m-th generated token
+ *      (the token of its prefill counts as the first) gets stop_free_len = L0 + m - 1; 0 (or anything <= len) is off.
+ * S >= 1, 1 <= rows_per_slot <= 16, S * rows_per_slot <= 64, 1 <= vocab < 2^24, ldl >= vocab (4-byte aligned rows, ldl may be odd:
+ * 16-byte loads where a row's base allows, scalar loads otherwise), `out` 16-byte aligned with ldo >= vocab, ldo % 4 == 0, and not
+ * the logits themselves: it writes out of place, so pc_token_logprobs keeps seeing the model's own rows.  Columns [vocab, ldo) of
+ * `out` are not written.
+ * One launch, grid = column chunks x rows: a workgroup applies only the entries that fall into its columns, and orders the writes
+ * to one element across workgroup barriers.  A row's result depends on that row, its slot's block and len[b] only -- not on other
+ * slots, on live flags or on the slot index.  No state, no counter, no atomic: nothing but `out` is written (ordinary vector
+ * stores).  Argument errors -> PC_ERR_ARG with nothing launched. */
+#define PC_LOGIT_BIAS_MAX 64
+#define PC_LOGIT_STOP_MAX 8
+typedef struct pc_logit_ctl {        /* one per slot, device memory */
+    int32_t n_bias;                  /* 0..64; the kernel clamps */
+    int32_t use_allowed;             /* != 0: a token whose bit is clear in the slot's allowed row becomes -inf */
+    int32_t stop_free_len;           /* stop_ids are -inf on draft row i while len[b] + i < stop_free_len */
+    int32_t pad;
+    int32_t stop_ids[8];             /* unused: -1 */
+    int32_t bias_id[64];             /* distinct (host contract); ids outside [0, vocab) are skipped */
+    float   bias[64];
+} pc_logit_ctl;
+int pc_logit_adjust(const float* logits, int64_t ldl, int32_t vocab, int32_t S, int32_t rows_per_slot, const pc_logit_ctl* ctl,
+                    const uint32_t* allowed_bits, const int32_t* len, float* out, int64_t ldo, void* stream);
+
 /* Diagnostics used by the GPU test-suite: dumps the MFMA C/D lane map and the LDS transpose-read
  * map the attention kernel relies on (probe_kernel in csrc/pc_misc.hip). */
 /* dev hook (tools/gemm_trace.py): weight-streaming launches issued by this thread stamp per-wave wall-clock times

@@ -51,6 +51,16 @@ class SampleParams(C.Structure):
     _fields_ = [("temperature", _f32), ("repetition_penalty", _f32), ("top_p", _f32), ("top_k", _i32), ("seed", C.c_uint64)]
 
 
+LOGIT_BIAS_MAX = 64             # PC_LOGIT_BIAS_MAX
+LOGIT_STOP_MAX = 8              # PC_LOGIT_STOP_MAX
+
+
+class LogitCtl(C.Structure):
+    """``pc_logit_ctl``: one slot's token controls, the device-resident block of pc_logit_adjust."""
+    _fields_ = [("n_bias", _i32), ("use_allowed", _i32), ("stop_free_len", _i32), ("pad", _i32), ("stop_ids", _i32 * 8),
+                ("bias_id", _i32 * 64), ("bias", _f32 * 64)]
+
+
 class SlotArmBlock(C.Structure):
     """``pc_slot_arm_block``: the header of the pinned host block of pc_slot_arm (``hist_words`` uint32 of bitmap follow)."""
     _fields_ = [("slot", _i32), ("cap", _i32), ("kv_base", C.c_uint64), ("len", _i32), ("pos", _i32), ("id", _i64),
@@ -263,6 +273,7 @@ SIGNATURES = {
     "pc_gemm_dense_qkv_rope": (C.c_int, [_vp, _vp]),
     "pc_gemm_dense_ws": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
     "pc_token_logprobs": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "pc_logit_adjust": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 # Entry points of -DPC_DEV_SWEEPS builds only (csrc/pc_dev.h: measured negative results kept for A/B; not in the product library
@@ -1338,6 +1349,37 @@ def token_logprobs(logits, ldl: int, vocab: int, rows: int, tokens, tok_stride: 
                                   None if t64 else tokens.data_ptr(), tok_stride, top_n, out_ids.data_ptr(), out_lp.data_ptr(),
                                   current_stream() if stream is None else stream)
     check(rc, "pc_token_logprobs")
+
+
+def logit_ctl_bytes(bias=(), use_allowed: bool = False, stop_free_len: int = 0, stop_ids=()) -> bytes:
+    """The ``pc_logit_ctl`` image of one slot: ``bias`` = ``[(id, value), ...]`` (distinct ids, at most 64; a ban is ``-inf``),
+    ``stop_ids`` at most 8.  No arguments: the neutral block, under which the adjusted row is the raw row."""
+    bias, stop_ids = list(bias), list(stop_ids)
+    assert len(bias) <= LOGIT_BIAS_MAX and len(stop_ids) <= LOGIT_STOP_MAX and len({int(i) for i, _ in bias}) == len(bias)
+    b = LogitCtl()
+    b.n_bias, b.use_allowed, b.stop_free_len = len(bias), 1 if use_allowed else 0, int(stop_free_len)
+    for j in range(LOGIT_STOP_MAX):
+        b.stop_ids[j] = int(stop_ids[j]) if j < len(stop_ids) else -1
+    for j, (i, v) in enumerate(bias):
+        b.bias_id[j], b.bias[j] = int(i), float(v)
+    return bytes(b)
+
+
+def logit_adjust(logits, ldl: int, vocab: int, S: int, rows_per_slot: int, ctl, allowed, length, out, ldo: int,
+                 stream: Optional[int] = None) -> None:
+    """The adjusted copy of ``S * rows_per_slot`` fp32 ``logits`` rows into ``out`` (pc_logit_adjust): per slot the bias table,
+    allow-list and stop-id suppression of its ``pc_logit_ctl`` block in ``ctl`` (uint8 device tensor, ``S`` blocks).  ``allowed``:
+    uint32 / int32 ``[S][ceil(vocab / 32)]`` or None; ``length``: int32 ``[S]`` (the loops' arena lengths) or None (reads as 0)."""
+    import torch
+    rows = S * rows_per_slot
+    assert logits.dtype == torch.float32 and out.dtype == torch.float32 and ctl.dtype == torch.uint8
+    assert ctl.numel() >= S * C.sizeof(LogitCtl) and logits.numel() >= (rows - 1) * ldl + vocab and out.numel() >= (rows - 1) * ldo + vocab
+    assert allowed is None or (allowed.element_size() == 4 and allowed.numel() >= S * ((vocab + 31) // 32))
+    assert length is None or (length.dtype == torch.int32 and length.numel() >= S)
+    rc = load().pc_logit_adjust(logits.data_ptr(), ldl, vocab, S, rows_per_slot, ctl.data_ptr(),
+                                None if allowed is None else allowed.data_ptr(), None if length is None else length.data_ptr(),
+                                out.data_ptr(), ldo, current_stream() if stream is None else stream)
+    check(rc, "pc_logit_adjust")
 
 
 # ---- LLM.int8 (pc_int8.hip) -------------------------------------------------------------------------------------------

@@ -19,7 +19,7 @@ import gc
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Generator, List, Optional, Tuple
+from typing import Dict, Generator, List, Optional, Tuple
 
 import torch
 
@@ -42,9 +42,27 @@ class GenerationParameters:
     # None: off.  n in 0..8: every generated token comes with its log-probability and those of the n most likely tokens, under the
     # model's own distribution -- the log-softmax of the raw logits, BEFORE temperature, repetition penalty, top-p and top-k
     logprobs: Optional[int] = None
+    # Token controls (all off by default).  They act on the logits row IN FRONT of the chain above -- temperature,
+    # repetition penalty, top-p, top-k, the greedy rule -- and leave ``Output.logprobs`` alone (the model's own distribution).
+    # logit_bias: token id -> a value added to its logit (finite, or -inf: a ban); banned_token_ids: shorthand for -inf, a ban wins
+    # over a finite bias on the same id; together at most modes.LOGIT_BIAS_MAX = 64 distinct ids
+    logit_bias: Optional[Dict[int, float]] = None
+    banned_token_ids: Optional[List[int]] = None
+    # every token NOT listed becomes -inf ("answer with A, B, C or D")
+    allowed_token_ids: Optional[List[int]] = None
+    # the ids in stop_token_ids are -inf for the generated tokens numbered g < min_new_tokens (g = 0: the token drawn from the
+    # prefill; transformers' MinNewTokensLengthLogitsProcessor); stop strings are not affected; at most 8 stop ids with it
+    min_new_tokens: int = 0
 
     def __post_init__(self):
         modes.check_logprobs(self.logprobs, what="GenerationParameters.logprobs")
+        self.token_controls                # (validates: ValueError here, not at the first token)
+
+    @property
+    def token_controls(self) -> Optional[modes.TokenControls]:
+        """The merged, validated token controls (``modes.token_controls``), or None when all four fields are vacuous."""
+        return modes.token_controls(self.logit_bias, self.banned_token_ids, self.allowed_token_ids, self.min_new_tokens,
+                                    self.stop_token_ids)
 
     @property
     def greedy(self) -> bool:
@@ -182,6 +200,24 @@ def _first_logprobs(hf, logits_row, token: int, n: Optional[int]):
     return hf.token_logprobs(logits_row, [token], n)[0]
 
 
+def _adjusted(hf, logits_row, controls, generated: int):
+    """``logits_row`` as the draw of generated token number ``generated`` sees it under ``controls``: one eager launch
+    (``LlamaHIP.adjust_logits``) in front of the argmax / sampler.  None: the row itself; a model without the call is an error, not
+    a fallback."""
+    if controls is None:
+        return logits_row
+    if not hasattr(hf, "adjust_logits"):
+        raise RuntimeError("token controls (logit_bias, banned_token_ids, allowed_token_ids, min_new_tokens) need a model with "
+                           "adjust_logits (pc_logit_adjust)")
+    return hf.adjust_logits(logits_row, controls, generated)
+
+
+def _controls_of(hf, params, loop_prefill: bool = False):
+    """The token controls a request runs with, checked against the model's vocabulary (first use) -> ``TokenControls`` or None."""
+    vocab = getattr(getattr(hf, "config", None), "vocab_size", None)
+    return modes.check_token_controls(params.token_controls, loop_prefill, vocab, len(params.stop_token_ids))
+
+
 class GenerationEngine:
     # decode greedy generations as a device-side loop when the model offers one (PC_DEVICE_GREEDY=0: step through lm())
     device_greedy_loop = os.environ.get("PC_DEVICE_GREEDY", "1") != "0"
@@ -317,11 +353,16 @@ class GenerationEngine:
         st.ttft_ms = st.total_ms = ms
         if self.verbose:
             print(f"Prefill latency: {ms:.2f} ms")
-        if st.params.plain_greedy:
+        hf = getattr(self.lm, "hf_model", None)
+        ctl = _controls_of(hf, st.params)
+        if ctl is not None:                                        # (generated token number 0, under the request's controls)
+            row = _adjusted(hf, logits[0, -1], ctl, 0)
+            token = self._pick(row, True) if st.params.plain_greedy else hf.sample_token(row, st.params, st.seed, st.output_ids)
+        elif st.params.plain_greedy:
             token = self._pick(st.params.get_logits_processor()(None, logits[:, -1, :])[0], True)
         else:
             token = self.lm.hf_model.sample_token(logits[0, -1], st.params, st.seed, st.output_ids)
-        return st.emit(token, _first_logprobs(getattr(self.lm, "hf_model", None), logits[0, -1], token, st.want_lp))
+        return st.emit(token, _first_logprobs(hf, logits[0, -1], token, st.want_lp))
 
     # -- the generator ----------------------------------------------------------------------------
     @torch.inference_mode()
@@ -330,6 +371,9 @@ class GenerationEngine:
                  ) -> Generator[Output, None, None]:
         n_lp = modes.check_logprobs(params.logprobs, what="GenerationParameters.logprobs")
         lp_kw = {} if n_lp is None else {"logprobs": n_lp}      # (a loop is handed nothing new when they are off)
+        ctl = _controls_of(getattr(self.lm, "hf_model", None), params)
+        if ctl is not None:                                     # (the loops draw from the adjusted row)
+            lp_kw["token_controls"] = ctl
         processors = params.get_logits_processor()
         prompt_positions = list(position_ids)
         first_free = max(prompt_positions) + 1
@@ -353,10 +397,13 @@ class GenerationEngine:
                               hasattr(hf, "lookup_available") and hf.lookup_available())
 
         def pick(logits):
+            last = logits[:, -1, :]
+            if ctl is not None:                                    # (the token about to be drawn is number len(new_ids))
+                last = _adjusted(hf, logits[0, -1], ctl, len(st.new_ids))[None, :]
             if want_sample:                                        # (the first token only: the loop draws every later one)
-                return hf.sample_token(logits[0, -1], params, seed, st.output_ids)
+                return hf.sample_token(last[0], params, seed, st.output_ids)
             history = torch.as_tensor([st.output_ids], device=self.lm.device) if params.repetition_penalty > 1.0 else None
-            return self._pick(processors(history, logits[:, -1, :])[0], params.greedy)
+            return self._pick(processors(history, last)[0], params.greedy)
 
         def host_steps():
             nonlocal past
@@ -481,11 +528,17 @@ class GenerationEngine:
         arena per sequence, so there is nothing to save.
         ``params.logprobs`` = n covers all sequences: the first tokens through ``LlamaHIP.token_logprobs``, the rest
         from the loop's own node (``slot_loop(logprobs=n)`` / ``lookup_slot_loop(logprobs=n)``); one ``generate`` after another
-        keeps them."""
+        keeps them.
+        ``params.token_controls`` (``logit_bias``, ``banned_token_ids``, ``allowed_token_ids``, ``min_new_tokens``) cover
+        all sequences the same way: the first tokens through ``LlamaHIP.adjust_logits``, the rest through the loop's own node
+        (``slot_loop(token_controls=...)``), every slot with the same block."""
         n_lp = modes.check_logprobs(params.logprobs, what="GenerationParameters.logprobs")
         lp_kw = {} if n_lp is None else {"logprobs": n_lp}      # (a model from before the option is handed nothing new)
         requests = [(list(t), list(p), c) for t, p, c in requests]
         hf = getattr(self.lm, "hf_model", None)
+        ctl = _controls_of(hf, params)
+        if ctl is not None:                                     # (one parameter set: every slot gets the same block)
+            lp_kw["token_controls"] = ctl
         # every cache must be a staged batch-1 arena, no two the same
         arenas = [getattr(c, "arena", None) for _, _, c in requests]
         own = all(a is not None and a.B == 1 for a in arenas) and len(set(map(id, arenas))) == len(arenas)
@@ -533,7 +586,7 @@ class GenerationEngine:
 
     # -- a stream of requests: continuous batching ------------------------------------------------
     def serve_plan(self, lookup: int = 0, slots: Optional[int] = None, slot_kv: Optional[str] = None,
-                   keep_arenas: Optional[bool] = None, loop_prefill: bool = False) -> Tuple[bool, str]:
+                   keep_arenas: Optional[bool] = None, loop_prefill: bool = False, token_controls: bool = False) -> Tuple[bool, str]:
         """``(batched, reason)``: whether ``serve`` runs its requests through one device loop that admits new prompts as slots free
         up (``model/llama_hip.py`` SlotLoop, ``each=True``), or one after another through ``generate``, and why.  Host logic only.
         Requests carry their own parameters, so both device loops must be on.  ``lookup`` = k > 0 (``serve(lookup=k)`` over
@@ -542,16 +595,18 @@ class GenerationEngine:
         reason of a batched plan says that the loop reads int8 K/V images, and with ``keep_arenas=False`` (None: not named) that
         no slot keeps an fp16 arena.  ``loop_prefill=True`` (``serve``'s): the reason of a plan in the lookup form says that
         admitted requests are prefilled inside the step; where ``serve`` would refuse the mode (``check_loop_prefill``) this
-        raises the same ValueError."""
+        raises the same ValueError.  ``token_controls=True`` (``serve``'s): the reason of a batched plan says that the step carries
+        the token-control node; together with ``loop_prefill=True`` it raises ``serve``'s ValueError."""
         m = modes.resolve_serve(self._capabilities(True, True), slots, False, int(lookup), slot_kv, keep_arenas, bool(loop_prefill),
-                                validate=False)                    # (the plan reads PC_SLOT_KV from the environment, nothing else)
+                                validate=False,                    # (the plan reads PC_SLOT_KV from the environment, nothing else)
+                                token_controls=bool(token_controls))
         return m.batched, m.reason()
 
     @torch.inference_mode()
     def serve(self, cache_engine, requests, params: Optional[GenerationParameters] = None, stream_interval: int = 2,
               share_trunk: Optional[bool] = None, lookup: Optional[int] = None, slot_kv: Optional[str] = None,
-              keep_arenas: Optional[bool] = None, loop_prefill: Optional[bool] = None, logprobs: Optional[int] = None
-              ) -> Generator[Tuple[int, Output], None, None]:
+              keep_arenas: Optional[bool] = None, loop_prefill: Optional[bool] = None, logprobs: Optional[int] = None,
+              token_controls: Optional[bool] = None) -> Generator[Tuple[int, Output], None, None]:
         """Continuous batching over ``cache_engine.slots`` slots.  ``requests``: any iterable -- it may be lazy -- of ``Prompt`` or
         ``(Prompt, GenerationParameters)``; ``params`` is the default for bare prompts.  Requests are numbered in the order they
         are pulled; yields ``(index, Output)``.  A request is pulled when a slot is free: ``cache_engine.process(prompt, slot=k)``,
@@ -605,9 +660,18 @@ class GenerationEngine:
         one that asks for more than n -- or asks at all while this is off -- raises ValueError naming ``serve(logprobs=...)`` before
         its prefill.  Works with ``lookup``, ``share_trunk``, ``slot_kv="int8"`` and ``keep_arenas=False``; ValueError together with
         ``loop_prefill`` (``modes.check_logprobs``: a request admitted that way draws its first token inside the step from a forced
-        row)."""
+        row).
+        ``token_controls`` (None: ``PC_SERVE_TOKEN_CONTROLS``, default 0): the step is captured once, so the
+        token-control node is a mode of the loop -- with it the step runs ``pc_logit_adjust`` in front of its draw, every slot under
+        the block of the request it holds (``logit_bias``, ``banned_token_ids``, ``allowed_token_ids``, ``min_new_tokens`` of its own
+        ``GenerationParameters``; a request without controls gets the neutral block, written at admission like any other, so nothing
+        of the slot's previous request stays).  A request that carries controls while the mode is off raises ValueError naming
+        ``serve(token_controls=...)`` before its prefill.  Works with ``lookup``, ``share_trunk``, ``slot_kv="int8"``,
+        ``keep_arenas=False`` and ``logprobs`` (which stay the raw rows'); ValueError together with ``loop_prefill``
+        (``modes.check_token_controls``: the progress word also counts forced question rows there)."""
         m = modes.resolve_serve(self._capabilities(True, True), getattr(cache_engine, "slots", None), share_trunk, lookup, slot_kv,
-                                keep_arenas, loop_prefill, logprobs=logprobs)
+                                keep_arenas, loop_prefill, logprobs=logprobs, token_controls=token_controls)
+        hf = getattr(self.lm, "hf_model", None)
         share_trunk, drafts, drop, in_loop = m.share_trunk, m.drafts, not m.keep_arenas, m.loop_prefill
 
         def unpack(req):
@@ -618,6 +682,10 @@ class GenerationEngine:
                 raise ValueError(f"serve: a request asks for logprobs={want}, and the loop "
                                  + ("carries no log-probability node" if m.logprobs is None else f"ranks {m.logprobs} alternatives")
                                  + f": call serve(logprobs=n) with n >= {want} (or set PC_SERVE_LOGPROBS)")
+            if p is not None and _controls_of(hf, p, m.loop_prefill) is not None and not m.token_controls:
+                raise ValueError("serve: a request carries token controls (logit_bias, banned_token_ids, allowed_token_ids or "
+                                 "min_new_tokens) and the loop has no token-control node: call serve(token_controls=True) (or set "
+                                 "PC_SERVE_TOKEN_CONTROLS=1)")
             return prompt, p
 
         if not m.batched:
@@ -629,7 +697,6 @@ class GenerationEngine:
                     yield r, out
             return
 
-        hf = self.lm.hf_model
         S = cache_engine.slots
         sched = SlotScheduler(S, requests, share_trunk=share_trunk)    # (drafts = k > 0: the lookup form, serve_plan(lookup, S))
         stats = self.last_serve_stats = dict(replays=0, rows=0, live_rows=0, requests=0)
@@ -667,6 +734,7 @@ class GenerationEngine:
                 st = _Stream(self._render, p, stream_interval, ids, max(pos) + 1, index=index, slot=slot,
                              seed=0 if p.plain_greedy else seed + index, device_stops=split_stop_ids(p.stop_token_ids)[0])
                 tokens[index] = st.new_ids
+                st.ctl = _controls_of(hf, p)
                 if in_loop and loop is not None and admit_prompt(st, list(ids), list(pos), cache):
                     continue
                 if in_loop:
@@ -686,7 +754,8 @@ class GenerationEngine:
                         build_loop()
                 else:
                     trunk = sched.join(slot, st.past.arena.layout) if share_trunk and loop.nsplit_trunk else None
-                    st.k = loop.admit(slot, *loop_args(st), *((st.corpus,) if read_k else ()), trunk=trunk)
+                    st.k = loop.admit(slot, *loop_args(st), *((st.corpus,) if read_k else ()), trunk=trunk,
+                                      **({"controls": st.ctl} if m.token_controls else {}))
                     sched.started(slot, index, loop.n)
                 if drop:
                     st.past = cache = None                         # (the loop holds the rows; the buffer is the next request's)
@@ -721,14 +790,15 @@ class GenerationEngine:
             trunks = sched.group_first_fill(slots_, [st.past.arena.layout for st in pending]) if share_trunk else None
             # (loop_args per sequence -> one list per argument)
             pasts, toks0, poss, max_news, paramss, seeds_, hists, stops = map(list, zip(*map(loop_args, pending)))
+            ctl_kw = {"token_controls": [st.ctl for st in pending]} if m.token_controls else {}    # (on: one block, or None, per sequence)
             if drafts:
                 loop = hf.lookup_slot_loop(pasts, toks0, poss, max_news, drafts, [st.corpus for st in pending], stop_ids=stops,
                                            slots=S, max_keys=cache_engine.max_ctx_length, trunks=trunks, each=True,
                                            slot_index=slots_, params=paramss, seeds=seeds_, histories=hists,
-                                           hist_cap=2 * cache_engine.max_ctx_length, **m.loop_kwargs())
+                                           hist_cap=2 * cache_engine.max_ctx_length, **{**m.loop_kwargs(), **ctl_kw})
             if loop is None:
                 loop = hf.slot_loop(pasts, toks0, poss, max_news, paramss, seeds_, hists, stops, slots=S, slot_index=slots_, each=True,
-                                    max_keys=cache_engine.max_ctx_length, trunks=trunks, **m.loop_kwargs(one_token=True))
+                                    max_keys=cache_engine.max_ctx_length, trunks=trunks, **{**m.loop_kwargs(one_token=True), **ctl_kw})
             if loop is None:
                 raise RuntimeError("serve: the model refused a batched decode loop over these caches")
             read_k = _reader(loop)[1]                              # (keep_arenas=False admits the rest of the first fill at once)

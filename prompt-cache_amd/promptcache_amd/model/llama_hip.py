@@ -36,8 +36,9 @@ import numpy as np
 
 from .. import _native
 # the pure refusals of formats and loop modes live in modes.py (no torch); the names stay importable from here
-from ..modes import (SLOT_KV, WEIGHT_FORMATS, check_keep_fp16, check_logprobs, check_loop_prefill,  # noqa: F401
-                     check_slot_keep_arenas, check_slot_kv, check_weight_format, parse_keep_arenas, parse_keep_fp16)
+from ..modes import (SLOT_KV, WEIGHT_FORMATS, TokenControls, check_keep_fp16, check_logprobs, check_loop_prefill,  # noqa: F401
+                     check_slot_keep_arenas, check_slot_kv, check_token_controls, check_weight_format, parse_keep_arenas,
+                     parse_keep_fp16)
 from .config import LlamaShape
 from .kv_arena import KVArena, StagedKV, arena_from_past, common_trunks
 
@@ -148,7 +149,48 @@ class _LogprobRing:
         return logprob_records(self.ids[r, row0:row0 + count], self.lp[r, row0:row0 + count])
 
 
-class GreedyLoop:
+def logit_ctl_image(controls, vocab: int, stop_free_len: int = 0):
+    """The device image of one slot's token controls -> ``(pc_logit_ctl bytes, allowed row | None)``: the block with
+    ``stop_free_len`` as given (``len_at_entry + min_new_tokens - 1`` for a sequence entering a device loop; 0 where the controls
+    hold no stop ids back) and the uint32 ``[ceil(vocab / 32)]`` row with the bit of every allowed id set.  ``controls`` None: the
+    neutral block, under which the adjusted row is the raw row.  Ids must lie inside the vocabulary (``check_token_controls``)."""
+    if controls is None:
+        return _native.logit_ctl_bytes(), None
+    check_token_controls(controls, vocab=vocab)
+    bits = None
+    if controls.allowed is not None:
+        bits = _history_bits(controls.allowed, vocab).numpy().view(np.uint32)
+    return _native.logit_ctl_bytes(controls.bias, bits is not None, stop_free_len if controls.stop_ids else 0, controls.stop_ids), bits
+
+
+class _TokenControlled:
+    """What every device loop shares for the token-control node: ``with_controls(controls, ...)`` builds the loop with
+    one more node between the lm_head and its advance / verify launch -- ``pc_logit_adjust`` into a fixed ``[rows][V]`` buffer the
+    launch then reads instead of the logits (the log-probability node keeps reading the raw rows).  ``controls``: None -- plain
+    ``cls(...)``, no node, today's graph keys and launches; a ``TokenControls`` for every sequence, a list with one (or None) per
+    sequence, or True: the node with neutral blocks, for a serving loop whose requests bring their own at admission."""
+
+    ctl_on = False                   # the step carries the node (the graph key gains ("ctl",))
+    _controls = None                 # what the slots are filled with when the loop is built
+    _cs = None                       # the node's state: blocks, allowed rows, the adjusted buffer (LlamaHIP._ctl_state)
+
+    @classmethod
+    def with_controls(cls, controls, *args, **kw):
+        """``cls(*args, **kw)`` with the node (None: without).  The option is in place before ``__init__`` builds state and graph
+        key, and the constructors keep their signatures."""
+        loop = cls.__new__(cls)
+        if controls is not None:
+            check_token_controls(TokenControls(), getattr(cls, "prompt_rows", False))
+            loop.ctl_on, loop._controls = True, None if controls is True else controls
+        loop.__init__(*args, **kw)
+        return loop
+
+    def _controls_of(self, j: int):
+        c = self._controls
+        return c[j] if isinstance(c, (list, tuple)) else c
+
+
+class GreedyLoop(_TokenControlled):
     """Greedy decode steps that never leave the GPU (reference loop: generation_engine.py:123-168, greedy branch).
 
     Every step is one replay of a captured hipGraph whose last node (``pc_greedy_advance``) takes the argmax of the
@@ -169,6 +211,9 @@ class GreedyLoop:
         self.lp_n = check_logprobs(logprobs)
         self._lp = None if self.lp_n is None else _LogprobRing(model._lp_state(("loop",), 1, self.lp_n), self.RING)
         past_len = arena.length
+        if self.ctl_on:                  # the first step draws generated token number 1 at arena length past_len
+            self._cs = model._ctl_state(("loop",), 1, 1)
+            model._ctl_fill(self._cs, 0, self._controls, past_len)
         need = past_len + max_new + 2
         if need > arena.cap:
             arena = arena.grown(max(need, 2 * arena.cap))
@@ -248,7 +293,7 @@ class GreedyLoop:
         return e0.elapsed_time(e1)
 
     def _graph(self, arena: KVArena, past_len: int):
-        return self.m._loop_graph(arena, past_len, logprobs=self.lp_n)
+        return self.m._loop_graph(arena, past_len, logprobs=self.lp_n, ctl=self._cs)
 
 
 def _history_bits(ids, vocab: int) -> torch.Tensor:
@@ -294,10 +339,10 @@ class SampleLoop(GreedyLoop):
         model._sample_state_fill(self.st, params, seed, history_ids)
 
     def _graph(self, arena: KVArena, past_len: int):
-        return self.m._loop_graph(arena, past_len, sample=True, logprobs=self.lp_n)
+        return self.m._loop_graph(arena, past_len, sample=True, logprobs=self.lp_n, ctl=self._cs)
 
 
-class LookupLoop:
+class LookupLoop(_TokenControlled):
     """Greedy decode with prompt-lookup drafts, on the device: up to ``k + 1`` tokens per weight stream.
 
     One step = ``pc_lookup_draft`` (copy the ``k`` tokens that followed the most recent earlier occurrence of the history's last
@@ -329,6 +374,9 @@ class LookupLoop:
         self._lp = None if self.lp_n is None else _LogprobRing(model._lp_state(("lookup",), k + 1, self.lp_n), self.RING)
         arena.materialize()
         len0 = arena.length
+        if self.ctl_on:                  # row i of a step draws token number past - len0 + 1 + i
+            self._cs = model._ctl_state(("lookup",), 1, k + 1)
+            model._ctl_fill(self._cs, 0, self._controls, len0)
         need = len0 + max_new + k + 2
         if need > arena.cap:
             arena = arena.grown(max(need, 2 * arena.cap))
@@ -361,17 +409,21 @@ class LookupLoop:
         n.lookup_draft(st["hist"], st["hist_len"], st["ids"], st["pos"], st["ndraft"], k, self.nmax)
         out = m._forward_skinny(st["ids"][:k + 1], st["pos"][:k + 1], st["past"], self.arena, 1, k + 1, self.kv_ceiling - (k + 1),
                                 False, None)
-        self._verify(out, V)
+        if self._cs is not None:         # the verify reads the adjusted rows; the log-probability node keeps the raw ones
+            m._ctl_node(self._cs, out, V, 1, k + 1, st["past"])
+            self._verify(self._cs["out"], V, self._cs["ldo"])
+        else:
+            self._verify(out, V)
         if self._lp is not None:
             m._lp_node(self._lp.dev, out, k + 1, st[self.row_tokens], 1, self.lp_n)
         return out
 
     row_tokens = "amax"              # the int32 scratch the verify stage leaves every row's token in
 
-    def _verify(self, out, V: int) -> None:
+    def _verify(self, out, V: int, ld: Optional[int] = None) -> None:
         """The last stage of a step: which rows' tokens are emitted, and the state advance."""
         st = self.st
-        _native.lookup_verify(out, V, V, self.k + 1, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["past"],
+        _native.lookup_verify(out, V if ld is None else ld, V, self.k + 1, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["past"],
                               st["ndraft"], st["budget"], st["ring"], st["ctr"], self.RING)
 
     @torch.inference_mode()
@@ -451,9 +503,9 @@ class SampleLookupLoop(LookupLoop):
         model._sample_state_fill(st, params, seed, history_ids)
         st["draws"].fill_(1)
 
-    def _verify(self, out, V: int) -> None:
+    def _verify(self, out, V: int, ld: Optional[int] = None) -> None:
         st = self.st
-        _native.lookup_verify_sample(out, V, V, self.k + 1, st["params"], st["bits"], st["row_bits"], st["draws"], st["row_token"],
+        _native.lookup_verify_sample(out, V if ld is None else ld, V, self.k + 1, st["params"], st["bits"], st["row_bits"], st["draws"], st["row_token"],
                                      st["hist"], st["hist_len"], st["ids"], st["pos"], st["past"], st["ndraft"], st["budget"],
                                      st["ring"], st["ctr"], self.RING)
 
@@ -525,7 +577,7 @@ def _fill_arm_block(arr, header, fields: dict, seed: int, params, stop_ids, hist
     return n0 + ((4 * hw + 7) & ~7)
 
 
-class _SlotLoopHost:
+class _SlotLoopHost(_TokenControlled):
     """The host side of a batched device loop, once for ``SlotLoop`` and ``LookupSlotLoop``: slots and arenas,
     shared trunks, the per-sequence tables, admission into a running ``each=True`` loop through a ring of pinned arm blocks, and
     the replay / ring / event protocol ``GenerationEngine`` drives.  What a leaf says itself: the ring record (``_record``), the
@@ -545,10 +597,21 @@ class _SlotLoopHost:
     def with_logprobs(cls, logprobs: Optional[int], *args, **kw):
         """``cls(*args, **kw)`` whose step ends in the log-probability node at ``top_n = logprobs`` (None: plain ``cls(...)``).  The
         option is in place before ``__init__`` builds state and graph key, and the constructors keep their signatures."""
+        return cls.with_options(logprobs, None, *args, **kw)
+
+    @classmethod
+    def with_options(cls, logprobs: Optional[int], controls, *args, **kw):
+        """``with_logprobs`` and ``with_controls`` in one: both options are in place before ``__init__`` runs."""
         loop = cls.__new__(cls)
         loop.lp_n = check_logprobs(logprobs, cls.prompt_rows)
+        if controls is not None:
+            check_token_controls(TokenControls(), cls.prompt_rows)
+            loop.ctl_on, loop._controls = True, None if controls is True else controls
         loop.__init__(*args, **kw)
         return loop
+
+    def _ctl_tag(self):
+        return self._lp_tag()
 
     def _build(self, model, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index, trunks, each,
                max_keys, corpora=None, hist_cap=None) -> None:
@@ -587,6 +650,10 @@ class _SlotLoopHost:
         self.logits = st["logits"]
         if self.lp_n is not None:
             self._lp = _LogprobRing(model._lp_state(self._lp_tag(), S * (k + 1), self.lp_n), self.RING)
+        if self.ctl_on:                   # every slot starts neutral; a sequence's block is written where it enters
+            self._cs = model._ctl_state(self._ctl_tag(), S, k + 1)
+            for s in range(S):
+                model._ctl_fill(self._cs, s, None, 0)
         self.host = torch.zeros((self.RING, S) + self._record, dtype=torch.int32, pin_memory=True)
         self._ring = st["ring"].view((S, self.RING) + self._record)
         if each:
@@ -596,16 +663,21 @@ class _SlotLoopHost:
             nbytes, self._arm_state = self._arm_setup((model.config.vocab_size + 31) // 32)
             self._arm_ring = [[torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True), torch.cuda.Event(), False] for _ in range(4)]
             self._arm_next = 0
+            if self.ctl_on:               # ... and beside every arm block the pinned image of the slot's token controls
+                self._ctl_ring = [model._ctl_pinned() for _ in self._arm_ring]
             seeds = [0] * n if seeds is None else list(seeds)
             histories = [()] * n if histories is None else list(histories)
             for j, (l, T) in enumerate(trunks):
                 self._admit(idx[j], arenas[j], tokens[j], positions[j], max_news[j], paramss[j], seeds[j], histories[j], stops[j],
-                            None if l is None else (idx[l], T), None if corpora is None else corpora[j])
+                            None if l is None else (idx[l], T), None if corpora is None else corpora[j],
+                            controls=self._controls_of(j))
             return
         seats = [self._seat(s, a) for s, a in zip(idx, arenas)]
-        for s, a, trunk, seat in zip(idx, arenas, trunks, seats):
+        for j, (s, a, trunk, seat) in enumerate(zip(idx, arenas, trunks, seats)):
             self._enter(s, seat[0], trunk, max_new, stop_ids)
             self._quantise_entry(s, a)
+            if self.ctl_on:
+                model._ctl_fill(self._cs, s, self._controls_of(j), a.length)
 
         def col(vals, dtype, fill=0):
             t = torch.full((S,), fill, dtype=dtype)
@@ -688,10 +760,16 @@ class _SlotLoopHost:
             raise RuntimeError(f"{name}.admit: the cache is not a staged batch-1 arena")
         return a
 
-    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, trunk, corpus=None, question=None) -> int:
+    def _admit(self, s: int, a, token, position, max_new, params, seed, history, stop_ids, trunk, corpus=None, question=None,
+               controls=None) -> int:
         """``question`` (``LookupSlotLoop.admit_prompt``): the ids still to be prefilled, ``token`` the first of them -- the arena
-        also gets room for their rows, and the leaf's ``_admit_check`` / ``_arm`` see them."""
+        also gets room for their rows, and the leaf's ``_admit_check`` / ``_arm`` see them.  ``controls`` (a loop built with the
+        token-control node): the sequence's ``TokenControls``; None writes the neutral block, so nothing of the slot's previous
+        sequence stays."""
         m, name = self.m, type(self).__name__
+        if controls is not None and not self.ctl_on:
+            raise ValueError(f"{name}.admit: the sequence carries token controls and the loop was built without the node "
+                             "(with_controls / token_controls=True)")
         more = () if question is None else (question,)
         if getattr(m, "_live_loop", None) is not self:
             raise RuntimeError(f"{name}: another device loop on this model took over")
@@ -712,7 +790,7 @@ class _SlotLoopHost:
         stop_ids = [int(t) for t in stop_ids]
         assert len(stop_ids) <= 8, "at most 8 stop ids live on the device (the host kills for the rest)"
         # the next pinned block of the ring, once the launch that read it last has finished
-        ent = self._arm_ring[self._arm_next]
+        ent, ring_i = self._arm_ring[self._arm_next], self._arm_next
         self._arm_next = (self._arm_next + 1) % len(self._arm_ring)
         if ent[2]:
             ent[1].synchronize()
@@ -724,6 +802,8 @@ class _SlotLoopHost:
         self._quantise_entry(s, a)
         if leader >= 0:
             self._trunk_verify_images(s, leader, T)
+        if self.ctl_on:                   # the slot's block and allowed row, on the loop's stream in front of the arm launch: its
+            m._ctl_fill(self._cs, s, controls, a.length, self._ctl_ring[ring_i])   # live = 1 stays the last store
         self._arm(ent[0], arr, off, hist, *more)
         ent[1].record()
         ent[2] = True
@@ -857,7 +937,7 @@ class SlotLoop(_SlotLoopHost):
 
     def _graph(self):
         return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap if self.kv == "int8" else 0,
-                                  logprobs=self.lp_n)
+                                  logprobs=self.lp_n, ctl=self._cs)
 
     def _lp_tag(self):
         return ("slots", self.S)
@@ -894,13 +974,14 @@ class SlotLoop(_SlotLoopHost):
 
     @torch.inference_mode()
     def admit(self, slot_index: int, past, token: int, position: int, max_new: int, params, seed: int, history, stop_ids,
-              trunk=None) -> int:
+              trunk=None, controls=None) -> int:
         """A new sequence into slot ``slot_index`` of a running ``each=True`` loop, from the next replay on: the arena behind ``past``
         feeds ``token`` at ``position`` for at most ``max_new`` steps, with its own ``params`` (None / plain greedy: argmax), random
         stream ``seed`` (continuing at step 1), ``history`` ids and up to 8 ``stop_ids``.  ``trunk = (leader slot, T)``: rows [0, T) are
         read from the arena of that slot.  Only legal when the slot's previous sequence is over on the host mirror (stopped, out of
         budget or killed) and was retired.  -> the new sequence's index."""
-        return self._admit(int(slot_index), self._admit_arena(past), token, position, max_new, params, seed, history, stop_ids, trunk)
+        return self._admit(int(slot_index), self._admit_arena(past), token, position, max_new, params, seed, history, stop_ids, trunk,
+                           controls=controls)
 
     def _admit_check(self, s: int, corpus, token, max_new: int):
         prev = self._slot_seq[s]
@@ -1027,7 +1108,8 @@ class SlotLoopQ8Only(_ImageOnly, SlotLoopQ8):
     same ``max_keys`` a sequence's tokens are that loop's, bit for bit."""
 
     def _graph(self):
-        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap, fresh=True, logprobs=self.lp_n)
+        return self.m._slot_graph(self.S, self.nsplit, self.nsplit_trunk, self.each, self.qcap, fresh=True, logprobs=self.lp_n,
+                                  ctl=self._cs)
 
 
 class LookupSlotLoop(_SlotLoopHost):
@@ -1135,7 +1217,7 @@ class LookupSlotLoop(_SlotLoopHost):
 
     @torch.inference_mode()
     def admit(self, slot_index: int, past, token: int, position: int, max_new: int, params, seed: int, history, stop_ids, corpus,
-              trunk=None) -> int:
+              trunk=None, controls=None) -> int:
         """A new sequence into slot ``slot_index`` of a running ``each=True`` loop, from the next replay on (``SlotLoop.admit``'s
         contract): the arena behind ``past`` feeds ``token`` at ``position`` and may emit ``max_new`` tokens, with its own ``params``
         (None / plain greedy: argmax), random stream ``seed`` (continuing at step 1), penalty ``history`` ids, up to 8
@@ -1143,7 +1225,7 @@ class LookupSlotLoop(_SlotLoopHost):
         buffer is too small).  ``trunk = (leader slot, T)``.  Only legal when the slot's previous sequence was retired.
         -> the new sequence's index."""
         return self._admit(int(slot_index), self._admit_arena(past), token, position, max_new, params, seed, history, stop_ids, trunk,
-                           corpus)
+                           corpus, controls=controls)
 
     @torch.inference_mode()
     def admit_prompt(self, slot_index: int, past, ids, position0: int, max_new: int, params, seed: int, history, stop_ids, corpus,
@@ -2624,7 +2706,73 @@ class LlamaHIP:
             out += logprob_records(ids.cpu(), lp.cpu())
         return out
 
-    def _loop_graph(self, arena: KVArena, past_len: int, sample: bool = False, logprobs: Optional[int] = None):
+    # ---- token controls (pc_logit_adjust) ------------------------------------------------------------------------
+    def _ctl_state(self, tag: tuple, S: int, rows_per_slot: int) -> dict:
+        """The state of a step's token-control node, one per (loop state ``tag``, S, rows per slot): ``ctl`` -- S ``pc_logit_ctl``
+        blocks, ``allowed`` -- int32 ``[S][ceil(V / 32)]``, and ``out``, the fixed fp32 ``[S * rows_per_slot][ldo]`` buffer of adjusted
+        rows that the step's advance / verify launch reads (``ldo``: V rounded up to 4).  The captured steps hold the addresses."""
+        sts = self.__dict__.setdefault("_ctl_sts", {})
+        st = sts.get((tag, S, rows_per_slot))
+        if st is None:
+            dev, V = self.device, self.config.vocab_size
+            ldo, nb = (V + 3) & ~3, ctypes.sizeof(_native.LogitCtl)
+            st = dict(ctl=torch.zeros(S * nb, dtype=torch.uint8, device=dev), allowed=torch.zeros((S, (V + 31) // 32), dtype=torch.int32, device=dev),
+                      out=torch.zeros((S * rows_per_slot, ldo), dtype=torch.float32, device=dev), ldo=ldo, S=S, rows=rows_per_slot)
+            if not sts:
+                # first launch of the kernel outside any capture (code-object load): stateless, on zeroed rows under neutral blocks
+                _native.logit_adjust(torch.zeros((S * rows_per_slot, V), dtype=torch.float32, device=dev), V, V, S, rows_per_slot,
+                                     st["ctl"], st["allowed"], None, st["out"], ldo)
+            sts[(tag, S, rows_per_slot)] = st
+        return st
+
+    def _ctl_pinned(self) -> torch.Tensor:
+        """A pinned host buffer for one slot's image: the ``pc_logit_ctl`` block, then the allowed row."""
+        return torch.zeros(ctypes.sizeof(_native.LogitCtl) + 4 * ((self.config.vocab_size + 31) // 32), dtype=torch.uint8, pin_memory=True)
+
+    def _ctl_fill(self, cs: dict, s: int, controls, len_at_entry: int, pinned: Optional[torch.Tensor] = None) -> None:
+        """Slot ``s`` of the node state ``cs`` takes the image of ``controls`` (None: the neutral block) for a sequence that enters
+        with ``len_at_entry`` arena rows: row ``(s, i)`` of a step at arena length ``len`` draws generated token number
+        ``len - len_at_entry + 1 + i``, so the stop ids are held back while ``len + i < len_at_entry + min_new_tokens - 1``.  Two
+        copies ordered on the current stream; ``pinned`` (``_ctl_pinned``; the caller keeps it until they have run) for a loop that
+        is replaying."""
+        V, nb = self.config.vocab_size, ctypes.sizeof(_native.LogitCtl)
+        free = 0 if controls is None else len_at_entry + controls.min_new_tokens - 1
+        blk, bits = logit_ctl_image(controls, V, free)
+        host = torch.zeros(nb + 4 * cs["allowed"].shape[1], dtype=torch.uint8) if pinned is None else pinned
+        arr = host.numpy()
+        arr[:nb] = np.frombuffer(blk, dtype=np.uint8)
+        arr[nb:].view(np.uint32)[:] = 0 if bits is None else bits
+        cs["ctl"][s * nb:(s + 1) * nb].copy_(host[:nb], non_blocking=pinned is not None)
+        cs["allowed"][s].view(torch.uint8).copy_(host[nb:], non_blocking=pinned is not None)
+
+    def _ctl_node(self, cs: dict, logits, ldl: int, S: int, rows_per_slot: int, length) -> None:
+        """The node: the adjusted copy of the step's raw ``logits`` rows into ``cs["out"]`` under the slots' blocks and the arena
+        lengths in ``length`` (int32 device words: ``past`` of a single-sequence loop, ``len`` of a slot loop)."""
+        _native.logit_adjust(logits, ldl, self.config.vocab_size, S, rows_per_slot, cs["ctl"], cs["allowed"], length, cs["out"], cs["ldo"])
+
+    @torch.inference_mode()
+    def adjust_logits(self, logits_row: torch.Tensor, controls, generated: int = 0) -> torch.Tensor:
+        """One eager launch of pc_logit_adjust on a row the caller already has (``[vocab]`` logits, any float dtype) -> the adjusted
+        fp32 ``[vocab]`` row under ``controls`` for generated token number ``generated`` (0: the token drawn from the prefill): the
+        stop ids are ``-inf`` while ``generated < min_new_tokens``.  The first token of a generation and the host-stepped paths
+        come through here, in front of their argmax / sampler.  ``controls`` None: the row itself."""
+        if controls is None:
+            return logits_row
+        V = self.config.vocab_size
+        if logits_row.numel() != V:
+            raise ValueError(f"adjust_logits: a row of {logits_row.numel()} logits, vocab_size = {V}")
+        x = logits_row.reshape(V)
+        if not x.is_cuda or x.dtype != torch.float32 or x.stride(0) != 1:
+            x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        cs = self._ctl_state(("eager",), 1, 1)
+        blk, bits = logit_ctl_image(controls, V, controls.min_new_tokens - int(generated))     # (len reads as 0)
+        ctl = torch.frombuffer(bytearray(blk), dtype=torch.uint8).to(x.device)
+        allowed = None if bits is None else torch.from_numpy(bits.view(np.int32).copy()).to(x.device)
+        out = torch.empty(cs["ldo"], dtype=torch.float32, device=x.device)
+        _native.logit_adjust(x, V, V, 1, 1, ctl, allowed, None, out, cs["ldo"])
+        return out[:V]
+
+    def _loop_graph(self, arena: KVArena, past_len: int, sample: bool = False, logprobs: Optional[int] = None, ctl=None):
         """The captured graph of ONE greedy (``sample``: sampled) decode step over ``arena`` (forward of the token in the loop
         state + argmax / draw + state advance), keyed like ``_graphed_skinny``.  ``logprobs`` = n: one more node behind the advance
         (the key gains ``("logprobs", n)``; None: today's key and launches)."""
@@ -2637,6 +2785,8 @@ class LlamaHIP:
         if logprobs is not None:
             key += ("logprobs", logprobs)
             lp = self._lp_state(("loop",), 1, logprobs)
+        if ctl is not None:               # one more node in front of the advance, which then reads the adjusted row
+            key += ("ctl",)
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2656,10 +2806,14 @@ class LlamaHIP:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             out = self._forward_skinny(st["ids"], st["pos"], st["past"], arena, 1, 1, past_len, False, None)
+            row = out
+            if ctl is not None:
+                self._ctl_node(ctl, out, V, 1, 1, st["past"])
+                row = ctl["out"]
             if sample:
-                n.sample_advance(out, V, st["params"], st["hist"], st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
+                n.sample_advance(row, V, st["params"], st["hist"], st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
             else:
-                n.greedy_advance(out, V, st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
+                n.greedy_advance(row, V, st["ids"], st["pos"], st["past"], st["ring"], st["ctr"])
             if lp is not None:
                 self._lp_node(lp, out, 1, st["ids"], 1, logprobs)
         ent = (g, out)
@@ -2680,20 +2834,24 @@ class LlamaHIP:
         """Whether ``greedy_loop`` / ``sample_loop`` over ``past`` would give a loop (not None)."""
         return self._loop_arena(past) is not None
 
-    def greedy_loop(self, past, token: int, position: int, max_new: int, logprobs: Optional[int] = None) -> Optional["GreedyLoop"]:
+    def greedy_loop(self, past, token: int, position: int, max_new: int, logprobs: Optional[int] = None,
+                    token_controls=None) -> Optional["GreedyLoop"]:
         """A device-side greedy decode loop over the arena behind ``past`` (None when this model / cache cannot host one:
         the caller then steps through ``__call__``).  ``logprobs`` = n in 0..8: every step also leaves the log-probability of its
-        token and of the n most likely ones under the raw logits (``GreedyLoop.logprobs``); all device loops take it."""
+        token and of the n most likely ones under the raw logits (``GreedyLoop.logprobs``); all device loops take it.
+        ``token_controls`` (a ``TokenControls``): the step gains ``pc_logit_adjust`` in front of the advance, which then
+        takes the argmax of the adjusted row; all device loops take it too.  None: today's graph keys and launches."""
         arena = self._loop_arena(past)
-        return None if arena is None else GreedyLoop(self, arena, token, position, max_new, logprobs=logprobs)
+        return None if arena is None else GreedyLoop.with_controls(token_controls, self, arena, token, position, max_new, logprobs=logprobs)
 
     def sample_loop(self, past, token: int, position: int, max_new: int, params, seed: int, history_ids,
-                    logprobs: Optional[int] = None) -> Optional["SampleLoop"]:
+                    logprobs: Optional[int] = None, token_controls=None) -> Optional["SampleLoop"]:
         """A device-side sampled decode loop (``params``: temperature, repetition_penalty, top_p, top_k as in
         GenerationParameters; ``history_ids``: the ids the repetition penalty sees, ``token`` included) over the arena
         behind ``past``, continuing the random stream of ``seed`` at step 1.  None where ``greedy_loop`` gives None."""
         arena = self._loop_arena(past)
-        return None if arena is None else SampleLoop(self, arena, token, position, max_new, params, seed, history_ids, logprobs)
+        return None if arena is None else SampleLoop.with_controls(token_controls, self, arena, token, position, max_new, params, seed,
+                                                                   history_ids, logprobs)
 
     # ---- prompt-lookup speculative decoding (LookupLoop) ----------------------------------------------------------------
     def lookup_available(self) -> bool:
@@ -2758,6 +2916,8 @@ class LlamaHIP:
                loop.nmax, st["hist"].data_ptr(), st["hist"].numel(), self.fuse_norm) + loop.graph_tag
         if loop.lp_n is not None:
             key += ("logprobs", loop.lp_n)
+        if loop._cs is not None:
+            key += ("ctl",)
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -2777,7 +2937,7 @@ class LlamaHIP:
         return ent
 
     def lookup_loop(self, past, token: int, position: int, max_new: int, k: int, corpus_ids, nmax: int = 3, params=None,
-                    seed: int = 0, history_ids=None, logprobs: Optional[int] = None):
+                    seed: int = 0, history_ids=None, logprobs: Optional[int] = None, token_controls=None):
         """A device-side greedy decode loop with prompt-lookup drafts (``LookupLoop``: up to ``k + 1`` tokens per step, ``k`` in
         1..15) over the arena behind ``past``.  ``corpus_ids``: the ids the drafts may copy from besides the output itself --
         the context in key order; the history starts as ``corpus_ids ++ [token]``.  ``max_new``: the most tokens the loop
@@ -2788,14 +2948,15 @@ class LlamaHIP:
         if params is not None:
             history_ids = [int(token)] if history_ids is None else history_ids
             if not self.lookup_available():
-                return self.sample_loop(past, token, position, max_new, params, seed, history_ids, logprobs)
+                return self.sample_loop(past, token, position, max_new, params, seed, history_ids, logprobs, token_controls)
             arena = self._loop_arena(past)
-            return None if arena is None else SampleLookupLoop(self, arena, token, position, max_new, k, corpus_ids, params, seed,
-                                                               history_ids, nmax, logprobs)
+            return None if arena is None else SampleLookupLoop.with_controls(token_controls, self, arena, token, position, max_new, k,
+                                                                             corpus_ids, params, seed, history_ids, nmax, logprobs)
         if not self.lookup_available():
-            return self.greedy_loop(past, token, position, max_new, logprobs)
+            return self.greedy_loop(past, token, position, max_new, logprobs, token_controls)
         arena = self._loop_arena(past)
-        return None if arena is None else LookupLoop(self, arena, token, position, max_new, k, corpus_ids, nmax, logprobs)
+        return None if arena is None else LookupLoop.with_controls(token_controls, self, arena, token, position, max_new, k, corpus_ids,
+                                                                   nmax, logprobs)
 
     # ---- batched decode over slots (SlotLoop) ---------------------------------------------------------------------------
     supports_slot_loop = True       # (a subclass with layer loops of its own says no)
@@ -2815,7 +2976,8 @@ class LlamaHIP:
     def slot_loop(self, pasts, tokens, positions, max_new: int, params=None, seeds=None, histories=None, stop_ids=(),
                   slots: Optional[int] = None, slot_index=None, share_trunk: bool = False,
                   min_trunk: Optional[int] = None, each: bool = False, max_keys: Optional[int] = None,
-                  trunks=None, kv: str = "fp16", keep_arenas: bool = True, logprobs: Optional[int] = None) -> Optional["SlotLoop"]:
+                  trunks=None, kv: str = "fp16", keep_arenas: bool = True, logprobs: Optional[int] = None,
+                  token_controls=None) -> Optional["SlotLoop"]:
         """A batched device-side decode loop over the arenas behind ``pasts`` (one ``past_key_values`` per sequence, each a
         batch-1 arena of its own): sequence k feeds ``tokens[k]`` at position ``positions[k]`` next.  ``params`` None or plain
         greedy: argmax; otherwise the sampled chain with ``seeds[k]`` (the stream continues at step 1) and ``histories[k]``.
@@ -2844,7 +3006,10 @@ class LlamaHIP:
         free afterwards (``SlotLoopQ8Only``); with ``each=True`` one arena can prefill every sequence in turn.
         ``logprobs`` = n in 0..8: the step gains one node behind the advance launch, ``pc_token_logprobs`` over the S
         logits rows at the tokens in ``ids[b]``; ``SlotLoop.logprobs(k, i)`` hands out the record of ``token(k, i)``.  None: today's
-        graph keys, state and launches."""
+        graph keys, state and launches.
+        ``token_controls``: the step gains ``pc_logit_adjust`` in front of the advance launch, which then reads the
+        adjusted rows -- a ``TokenControls`` for every sequence, a list with one (or None) per sequence, or True: neutral blocks, the
+        sequences bring theirs through ``admit(..., controls=...)``.  None: today's graph keys, state and launches."""
         check_logprobs(logprobs)
         check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, head_dim=self.D,
                       no_loop=None if self.slot_loop_available() else "the model has no batched decode loop",
@@ -2855,8 +3020,8 @@ class LlamaHIP:
             return None
         arenas, trunks = front
         cls = (SlotLoopQ8 if keep_arenas else SlotLoopQ8Only) if kv == "int8" else SlotLoop
-        return cls.with_logprobs(logprobs, self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids, slots, slot_index,
-                                 trunks, each, max_keys)
+        return cls.with_options(logprobs, token_controls, self, arenas, tokens, positions, max_new, params, seeds, histories, stop_ids,
+                                slots, slot_index, trunks, each, max_keys)
 
     def _slot_loop_front(self, pasts, stop_ids, each: bool, share_trunk: bool, min_trunk, trunks):
         """What ``slot_loop`` and ``lookup_slot_loop`` do before they build their loop -> (arenas, trunks), or None where there is
@@ -2932,7 +3097,7 @@ class LlamaHIP:
         return st["fresh"]
 
     def _slot_graph(self, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0, fresh: bool = False,
-                    logprobs: Optional[int] = None):
+                    logprobs: Optional[int] = None, ctl=None):
         """The captured S-slot decode step.  Everything that changes from step to step or from batch to batch -- arena
         addresses included -- is read from the slot state, so one graph per (S, split count) serves every batch.
         ``nsplit_trunk`` > 0: the step with shared trunks; which slots share what is device data as well (leader / trunk).
@@ -2950,6 +3115,9 @@ class LlamaHIP:
         if logprobs is not None:          # one more node behind the advance launch: the key gains its top_n
             key += ("logprobs", logprobs)
             more["lp"] = (self._lp_state(("slots", S), S, logprobs), logprobs)
+        if ctl is not None:               # one more node in front of the advance launch, which then reads the adjusted rows
+            key += ("ctl",)
+            more["ctl"] = ctl
         g = self._graphs.pop(key, None)
         if g is not None:
             self._graphs[key] = g
@@ -2972,7 +3140,7 @@ class LlamaHIP:
         return g
 
     def _forward_slots(self, st: dict, S: int, nsplit: int, nsplit_trunk: int = 0, each: bool = False, qcap: int = 0,
-                       fresh: bool = False, lp=None) -> None:
+                       fresh: bool = False, lp=None, ctl=None) -> None:
         """One decode step over S slots: the <= 16-row projections of ``_layers_norm_fused`` around per-slot RoPE + append
         and attention; logits to ``st["logits"]``, then the advance launch.  ``qcap`` > 0: the attention reads the slots' int8
         images (``pc_attn_decode_slots_q8``) and stages the appended row into them; the arenas are appended to as always.
@@ -3041,12 +3209,16 @@ class LlamaHIP:
             else:
                 n.gemm_skinny(self._w16(lw, "wdown", True), ch, cl, S, hid, inter, n.EPI_ADD, y=x, ldy=hid)           # x += act @ Wd^T
         n.gemm_skinny_norm(self.lm_head_f, x, self.norm, eps, S, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
+        rows, ld = st["logits"], V
+        if ctl is not None:           # the token-control node: the advance reads the adjusted rows
+            self._ctl_node(ctl, st["logits"], V, S, 1, st["len"])
+            rows, ld = ctl["out"], ctl["ldo"]
         if each:
-            n.sample_advance_slots_each(st["logits"], V, V, st["params_each"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
+            n.sample_advance_slots_each(rows, ld, V, st["params_each"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
                                         st["cap"], st["live"], st["budget"], st["stop_each"], st["ring"], st["ctr"], st["draws"],
                                         SlotLoop.RING, S)
         else:
-            n.sample_advance_slots(st["logits"], V, V, st["params"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
+            n.sample_advance_slots(rows, ld, V, st["params"], st["seeds"], st["hist"], st["ids"], st["pos"], st["len"],
                                    st["cap"], st["live"], st["budget"], st["stop"], st["ring"], st["ctr"], SlotLoop.RING, S)
         if lp is not None:            # (buffers, top_n): the log-probabilities of the tokens the advance left in ids[b]
             self._lp_node(lp[0], st["logits"], S, st["ids"], 1, lp[1])
@@ -3057,7 +3229,7 @@ class LlamaHIP:
                          min_trunk: Optional[int] = None, trunks=None, each: bool = False, slot_index=None, params=None, seeds=None,
                          histories=None, hist_cap: Optional[int] = None, kv: str = "fp16",
                          keep_arenas: bool = True, prompt_rows: bool = False,
-                         logprobs: Optional[int] = None) -> Optional["LookupSlotLoop"]:
+                         logprobs: Optional[int] = None, token_controls=None) -> Optional["LookupSlotLoop"]:
         """``slot_loop`` with prompt-lookup drafts: up to ``k + 1`` greedy tokens per sequence and step (``LookupSlotLoop``).
         ``corpora[j]``: the ids sequence j's drafts may copy from besides its own output (``lookup_loop``'s ``corpus_ids``).  None
         where ``slot_loop`` gives None, where the model has no lookup step (``lookup_available``) and where ``S * (k + 1)``
@@ -3076,10 +3248,14 @@ class LlamaHIP:
         prefills an admitted request's question inside it.  False: today's loop, graph key and launches.
         ``logprobs`` = n in 0..8: the step gains one node behind the verify launches, ``pc_token_logprobs`` over the
         ``S * (k + 1)`` rows at the tokens the verify left in its int32 row scratch; ``LookupSlotLoop.logprobs(j, i)`` hands out the
-        records of ``tokens(j, i)``.  Not with ``prompt_rows`` (ValueError).  None: today's graph keys, state and launches."""
+        records of ``tokens(j, i)``.  Not with ``prompt_rows`` (ValueError).  None: today's graph keys, state and launches.
+        ``token_controls``: ``slot_loop``'s -- ``pc_logit_adjust`` over the ``S * (k + 1)`` rows in front of the verify
+        launch, row ``(b, i)`` under slot b's block at arena length ``len[b] + i``.  Not with ``prompt_rows`` (ValueError)."""
         if prompt_rows and (not each or kv != "fp16"):
             raise ValueError("lookup_slot_loop: prompt_rows=True needs each=True and kv='fp16'")
         check_logprobs(logprobs, prompt_rows)
+        if token_controls is not None:    # (``slot_loop``'s ``token_controls``, in front of the verify launch; not with prompt_rows)
+            check_token_controls(TokenControls(), prompt_rows)
         if kv != "fp16" or not keep_arenas:       # (with the mode off nothing is asked of the model here)
             check_slot_kv(kv, share_trunk=bool(share_trunk) or trunks is not None, lookup=k, head_dim=getattr(self, "D", None),
                           no_loop=None if self.slot_loop_available() else "the model has no batched decode loop",
@@ -3098,9 +3274,10 @@ class LlamaHIP:
         cls = ((LookupSlotLoopQ8 if keep_arenas else LookupSlotLoopQ8Only) if kv == "int8" else
                LookupSlotLoopPrompt if prompt_rows else LookupSlotLoop)
         if each:
-            return cls.with_logprobs(logprobs, self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks, True,
-                                     slot_index, params, seeds, histories, hist_cap)
-        return cls.with_logprobs(logprobs, self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys, trunks)
+            return cls.with_options(logprobs, token_controls, self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S,
+                                    max_keys, trunks, True, slot_index, params, seeds, histories, hist_cap)
+        return cls.with_options(logprobs, token_controls, self, arenas, tokens, positions, max_new, k, corpora, nmax, stop_ids, S, max_keys,
+                                trunks)
 
     def lookup_slot_q8_available(self) -> bool:
         """Whether ``lookup_slot_loop(kv="int8")`` can run: the lookup step, the slot step and head_dim 128
@@ -3166,6 +3343,9 @@ class LlamaHIP:
         if loop.lp_n is not None:         # one more node behind the verify launches: the key gains its top_n
             key += ("logprobs", loop.lp_n)
             more["lp"] = (loop._lp.dev, loop.lp_n)
+        if loop._cs is not None:          # one more node in front of the verify launch, which then reads the adjusted rows
+            key += ("ctl",)
+            more["ctl"] = loop._cs
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent
@@ -3188,7 +3368,8 @@ class LlamaHIP:
         return g
 
     def _forward_lookup_slots(self, st: dict, S: int, k: int, nsplit: int, nmax: int = 3, nsplit_trunk: int = 0,
-                              each: bool = False, qcap: int = 0, fresh: bool = False, prompt: bool = False, lp=None) -> None:
+                              each: bool = False, qcap: int = 0, fresh: bool = False, prompt: bool = False, lp=None,
+                              ctl=None) -> None:
         """One lookup step over S slots, ``R = S * (k + 1)`` rows: draft -> per layer {q|k|v plain store, per-slot RoPE + append of
         k + 1 rows, per-slot causal attention, o_proj, gate|up, down} -> lm_head over R rows -> verify.  R <= 16: the norm-folded
         projections of ``_forward_slots``; 17..64 rows: the launch sequence of ``_forward_skinny``'s generic loop (on the 4-bit
@@ -3291,17 +3472,21 @@ class LlamaHIP:
                 n.gemm_skinny(self._w16(lw, "wdown", True), ch, cl, R, hid, inter, n.EPI_STORE, y=slabs, ldy=hid, kslices=KQ)
             n.rmsnorm_frag(x, self.norm, xh, xl, R, hid, eps, slabs, pending)
             n.gemm_skinny(self.lm_head_f, xh, xl, R, V, hid, n.EPI_STORE, y=st["logits"], ldy=V)
+        rows, ld = st["logits"], V
+        if ctl is not None:           # the token-control node: the verify reads the adjusted rows
+            self._ctl_node(ctl, st["logits"], V, S, k + 1, st["len"])
+            rows, ld = ctl["out"], ctl["ldo"]
         if prompt:                    # ... and the forced rows of a slot that is still fed its question
-            n.lookup_verify_slots_prompt(st["logits"], V, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
+            n.lookup_verify_slots_prompt(rows, ld, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
                                          st["row_token"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"], st["cap"],
                                          st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], st["forced"],
                                          LookupSlotLoop.RING)
         elif each:                    # the sampler on every row, per slot
-            n.lookup_verify_slots_each(st["logits"], V, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
+            n.lookup_verify_slots_each(rows, ld, V, S, k, st["params_each"], st["seeds"], st["bits"], st["row_bits"], st["draws"],
                                        st["row_token"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"], st["cap"],
                                        st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
         else:
-            n.lookup_verify_slots(st["logits"], V, V, S, k, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"],
+            n.lookup_verify_slots(rows, ld, V, S, k, st["amax"], st["hist"], st["hist_len"], st["ids"], st["pos"], st["len"],
                                   st["cap"], st["live"], st["ndraft"], st["budget"], st["stop"], st["ring"], st["ctr"], LookupSlotLoop.RING)
         if lp is not None:            # (buffers, top_n): the log-probabilities of the row tokens the verify left in its int32 scratch
             self._lp_node(lp[0], st["logits"], R, st["row_token" if each else "amax"], 1, lp[1])

@@ -162,6 +162,103 @@ def parse_logprobs(value) -> Optional[int]:
         raise ValueError(f"PC_SERVE_LOGPROBS must be an integer in 0..{LOGPROBS_MAX_TOP}, not {value!r}") from None
 
 
+# ---- token controls: logit_bias, banned / allowed ids, min_new_tokens -------------------------------------------------
+LOGIT_BIAS_MAX = 64          # PC_LOGIT_BIAS_MAX: distinct ids of the merged bias table (logit_bias and banned_token_ids)
+LOGIT_STOP_MAX = 8           # PC_LOGIT_STOP_MAX: stop ids min_new_tokens can hold back (what the device loops hold)
+_INF = float("inf")
+
+
+@dataclass(frozen=True)
+class TokenControls:
+    """The merged, validated token controls of one request, as ``pc_logit_adjust`` takes them: ``bias`` = ``((id, value), ...)`` by
+    id, a ban being ``-inf``; ``allowed`` = the sorted ids that may be drawn (None: all); the ids in ``stop_ids`` are ``-inf`` for the
+    generated tokens numbered ``g < min_new_tokens`` (``g = 0``: the token drawn from the prefill)."""
+    bias: tuple = ()                   # ((id, value), ...)
+    allowed: Optional[tuple] = None    # (id, ...)
+    min_new_tokens: int = 0
+    stop_ids: tuple = ()
+
+    def max_id(self) -> int:
+        return max([i for i, _ in self.bias] + list(self.allowed or ()) + list(self.stop_ids) + [-1])
+
+
+def _token_ids(ids, what: str) -> list:
+    out = []
+    for i in ids:
+        if isinstance(i, bool) or not isinstance(i, int) or i < 0:
+            raise ValueError(f"{what} holds {i!r}: token ids are non-negative integers")
+        out.append(int(i))
+    return out
+
+
+def token_controls(logit_bias=None, banned_token_ids=None, allowed_token_ids=None, min_new_tokens: int = 0, stop_token_ids=(),
+                   vocab: Optional[int] = None) -> Optional[TokenControls]:
+    """``GenerationParameters``' four token-control fields, merged and validated -> ``TokenControls``, or None when all four are
+    vacuous (nothing to bias or ban, no allow-list, no stop id to hold back).  ``ValueError``: a bias that is NaN or ``+inf``, an id
+    that is no non-negative integer (with ``vocab``: one outside the vocabulary), more than 64 distinct biased or banned ids, a
+    negative ``min_new_tokens``, ``min_new_tokens > 0`` with more than 8 stop ids, and a set of tokens that can still be drawn --
+    allowed minus banned, minus the stop ids while ``min_new_tokens > 0`` -- that is empty.  A ban wins over a finite bias on the
+    same id.  Pure."""
+    table = {}
+    for i, v in (logit_bias or {}).items():
+        (i,) = _token_ids([i], "logit_bias")
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v == _INF:
+            raise ValueError(f"logit_bias[{i}] = {v!r}: a bias is finite, or -inf (a ban)")
+        table[i] = float(v)
+    for i in _token_ids(banned_token_ids or (), "banned_token_ids"):
+        table[i] = -_INF
+    if len(table) > LOGIT_BIAS_MAX:
+        raise ValueError(f"logit_bias and banned_token_ids name {len(table)} distinct ids, more than LOGIT_BIAS_MAX = {LOGIT_BIAS_MAX}")
+    allowed = None if allowed_token_ids is None else tuple(sorted(set(_token_ids(allowed_token_ids, "allowed_token_ids"))))
+    if isinstance(min_new_tokens, bool) or not isinstance(min_new_tokens, int) or min_new_tokens < 0:
+        raise ValueError(f"min_new_tokens must be a non-negative integer, not {min_new_tokens!r}")
+    stops = tuple(sorted(set(int(t) for t in stop_token_ids))) if min_new_tokens > 0 else ()
+    if len(stops) > LOGIT_STOP_MAX:
+        raise ValueError(f"min_new_tokens > 0 holds back at most {LOGIT_STOP_MAX} stop token ids (what a device loop holds), "
+                         f"not {len(stops)}")
+    stops = tuple(t for t in stops if t >= 0)
+    ctl = TokenControls(tuple(sorted(table.items())), allowed, int(min_new_tokens) if stops else 0, stops)
+    if not ctl.bias and ctl.allowed is None and not ctl.stop_ids:
+        return None
+    check_token_controls(ctl, vocab=vocab)
+    return ctl
+
+
+def check_token_controls(controls: Optional[TokenControls], loop_prefill: bool = False, vocab: Optional[int] = None,
+                         n_stop_ids: int = 0) -> Optional[TokenControls]:
+    """What ``token_controls`` cannot know when the parameters are made: ``ValueError`` for an id outside ``[0, vocab)`` once the
+    vocabulary is known, for an empty set of drawable tokens, for ``loop_prefill=True`` together with controls, and for more than 8
+    stop ids (``n_stop_ids``) together with ``min_new_tokens > 0`` -- raised before anything runs.  None passes.  Pure."""
+    if controls is None:
+        return None
+    if loop_prefill:
+        raise ValueError("loop_prefill=True and token controls (logit_bias, banned_token_ids, allowed_token_ids, min_new_tokens) "
+                         "exclude each other: the progress word min_new_tokens counts from, the slot's arena length, also counts "
+                         "the forced question rows there (loop_prefill with token controls is not implemented)")
+    if controls.min_new_tokens > 0 and max(n_stop_ids, len(controls.stop_ids)) > LOGIT_STOP_MAX:
+        raise ValueError(f"min_new_tokens > 0 holds back at most {LOGIT_STOP_MAX} stop token ids, not {max(n_stop_ids, len(controls.stop_ids))}")
+    if vocab is not None and controls.max_id() >= vocab:
+        raise ValueError(f"token controls name id {controls.max_id()}, outside the vocabulary [0, {vocab})")
+    gone = {i for i, v in controls.bias if v == -_INF} | set(controls.stop_ids)
+    if controls.allowed is not None:
+        left = len(set(controls.allowed) - gone)
+    else:
+        left = 1 if vocab is None else vocab - len(gone)
+    if left < 1:
+        raise ValueError("token controls leave no token that can be drawn (allowed_token_ids minus banned ids"
+                         + (", minus the stop ids while min_new_tokens > 0" if controls.stop_ids else "") + " is empty)")
+    return controls
+
+
+def parse_token_controls(value) -> bool:
+    """``PC_SERVE_TOKEN_CONTROLS``: unset, empty or ``0`` is off, ``1`` on."""
+    if value is None or value in ("", "0"):
+        return False
+    if value == "1":
+        return True
+    raise ValueError(f"PC_SERVE_TOKEN_CONTROLS must be 0 or 1, not {value!r}")
+
+
 def parse_keep_arenas(value) -> bool:
     """``PC_SLOT_KEEP_ARENAS``: unset, empty or ``1`` keeps the fp16 slot arenas under ``slot_kv="int8"``, ``0`` drops them."""
     return _parse_01("PC_SLOT_KEEP_ARENAS", value)
@@ -186,8 +283,15 @@ class Capabilities:
     trunk_q8: bool = False              # the shared-trunk attention over int8 images (``slot_trunk_q8_available``)
 
 
+@dataclass(frozen=True, kw_only=True)
+class _ModeSwitches:
+    """The keyword-only part of ``Modes``: a base class, so that its fields neither move a positional argument of ``Modes(...)`` nor
+    come behind ``logprobs``, the last field of the record."""
+    token_controls: bool = False       # serve: the step carries the token-control node in front of its draw (DESIGN 3.34)
+
+
 @dataclass(frozen=True)
-class Modes:
+class Modes(_ModeSwitches):
     """What ``serve`` / ``generate_batch`` run with, resolved once.  ``batched``: one device loop (False: one ``generate`` after the
     other) and ``base`` says why or which form; ``drafts`` = k > 0: the lookup form (``no_drafts``: why not, None where ``lookup`` is
     off, ``serve`` only); ``lookup`` is the k asked for, in ``serve`` 15 at most."""
@@ -213,6 +317,8 @@ class Modes:
                 why += ", no fp16 slot arenas: every prefill runs in one shared arena (keep_arenas=False)"
         if self.batched and self.logprobs is not None:
             why += f", per-token log-probabilities with up to {self.logprobs} alternatives (logprobs={self.logprobs})"
+        if self.batched and self.token_controls:
+            why += ", per-request logit_bias / banned / allowed ids / min_new_tokens applied in front of the draw (token_controls=True)"
         return why
 
     def loop_kwargs(self, one_token: bool = False) -> dict:
@@ -227,6 +333,8 @@ class Modes:
             kw["prompt_rows"] = True
         if self.logprobs is not None:
             kw["logprobs"] = self.logprobs
+        if self.token_controls:
+            kw["token_controls"] = True
         return kw
 
 
@@ -245,11 +353,13 @@ def _serve_drafts(caps: Capabilities, lookup: int, slots: Optional[int]):
 
 def resolve_serve(caps: Capabilities, slots: Optional[int] = None, share_trunk: Optional[bool] = None, lookup: Optional[int] = None,
                   slot_kv: Optional[str] = None, keep_arenas: Optional[bool] = None, loop_prefill: Optional[bool] = None,
-                  env: Optional[Mapping[str, str]] = None, validate: bool = True, logprobs: Optional[int] = None) -> Modes:
+                  env: Optional[Mapping[str, str]] = None, validate: bool = True, logprobs: Optional[int] = None,
+                  token_controls: Optional[bool] = None) -> Modes:
     """``serve``'s modes over ``slots`` slots (None: not known, no row limit applies).  An argument that is None reads the
     environment: ``PC_SLOT_TRUNK`` (default 0), ``PC_SERVE_LOOKUP`` (0), ``PC_SLOT_KV`` ("fp16"), ``PC_SLOT_KEEP_ARENAS`` (1),
-    ``PC_SERVE_LOOP_PREFILL`` (0), ``PC_SERVE_LOGPROBS`` (unset: off).  Refusals, in this order: ``check_slot_kv``,
-    ``check_slot_keep_arenas``, ``check_loop_prefill``, ``check_logprobs``.
+    ``PC_SERVE_LOOP_PREFILL`` (0), ``PC_SERVE_LOGPROBS`` (unset: off), ``PC_SERVE_TOKEN_CONTROLS`` (0).  Refusals, in this order:
+    ``check_slot_kv``, ``check_slot_keep_arenas``, ``check_loop_prefill``, ``check_logprobs``, ``token_controls`` with
+    ``loop_prefill``.
     ``validate=False`` is ``serve_plan``'s reading: ``slot_kv`` is taken as it comes and ``keep_arenas`` None means "not named"
     -- neither is checked and ``PC_SLOT_KEEP_ARENAS`` is not read -- while ``loop_prefill=True`` is refused as in ``serve``."""
     env = os.environ if env is None else env
@@ -272,6 +382,10 @@ def resolve_serve(caps: Capabilities, slots: Optional[int] = None, share_trunk: 
     if logprobs is None:
         logprobs = parse_logprobs(env.get("PC_SERVE_LOGPROBS"))
     logprobs = check_logprobs(logprobs, bool(loop_prefill), "serve(logprobs=...) / PC_SERVE_LOGPROBS")
+    if token_controls is None:
+        token_controls = parse_token_controls(env.get("PC_SERVE_TOKEN_CONTROLS"))
+    if token_controls:
+        check_token_controls(TokenControls(), bool(loop_prefill))
     if not batched:
         base = caps.not_batched
     elif drafts:
@@ -281,7 +395,8 @@ def resolve_serve(caps: Capabilities, slots: Optional[int] = None, share_trunk: 
         base = "one device loop, one token per replay: " + no_drafts
     else:
         base = "one device loop, new prompts admitted as slots free up"
-    return Modes(batched, base, bool(share_trunk), lookup, drafts, no_drafts, kv, bool(keep_arenas), bool(loop_prefill), logprobs)
+    return Modes(batched, base, bool(share_trunk), lookup, drafts, no_drafts, kv, bool(keep_arenas), bool(loop_prefill), logprobs,
+                 token_controls=bool(token_controls))
 
 
 def resolve_batch(caps: Capabilities, n_requests: int, plain_greedy: bool = True, n_stop_ids: int = 0, max_new_tokens: int = 2,
