@@ -374,8 +374,14 @@ __global__ __launch_bounds__(kRingThreads) void attn_ring_kernel(const AttnParam
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         const float m_new = fmaxf(m_run, mx);
 #endif
-        const float c_ = p.scale_log2, mc = m_new * c_;       // m_run / m_new are in raw-score units, the partials' m in log2 units
-        const float alpha = fast_exp2(m_run * c_ - mc);
+        const float c_ = p.scale_log2;                        // m_run / m_new are in raw-score units, the partials' m in log2 units
+        float mc, alpha;
+        {   // (both products ROUNDED before the subtraction: see soft() of the pipelined pair)
+#pragma clang fp contract(off)
+            mc = m_new * c_;
+            const float mo = m_run * c_;
+            alpha = fast_exp2(mo - mc);
+        }
         float rs = 0.f;
         h8 pb[2], pbl[2];
 #pragma unroll
@@ -487,8 +493,18 @@ __global__ __launch_bounds__(kRingThreads) void attn_ring_kernel(const AttnParam
             mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(acc[2][0], acc[2][1]), fmaxf(acc[2][2], acc[2][3])), fmaxf(fmaxf(acc[3][0], acc[3][1]), fmaxf(acc[3][2], acc[3][3]))));
             mx = fmaxf(mx, __shfl_xor(mx, 16));
             mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m_run, mx), mc = m_new * c_;
-            alpha = fast_exp2(m_run * c_ - mc);
+            const float m_new = fmaxf(m_run, mx);
+            float mc;
+            {
+                // alpha = 2^(round(m_run c) - round(m_new c)): both products ROUNDED, as the mc inside the exponents is.  Contracted
+                // into fma(m_run, c_, -mc) the difference keeps the rounding error of mc, and a row whose max did not move gets
+                // alpha = 2^(+-ulp(mc)/2) instead of 1 -- on l_run in every tile, on O only when some row of the wave moved: l
+                // drifts away from O by up to 2^-21 per tile at |score| ~ 30 log2 units (tests/test_gpu_attn_pins.py, the spikes)
+#pragma clang fp contract(off)
+                mc = m_new * c_;
+                const float mo = m_run * c_;
+                alpha = fast_exp2(mo - mc);
+            }
             moved = m_new > m_run;
             float rs = 0.f;
 #pragma unroll
